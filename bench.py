@@ -10,10 +10,15 @@ One "step" = one pass of the hot path over one batch of synthetic input:
   => 819 200 env-steps per step and per GPU.  Weak scaling: every rank owns 16 384 lanes; one flat-gradient
   all-reduce per optimizer step.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W]
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
   N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE /
   MASTER_* from the env), and as plain `python bench.py --gpus N`: the parent then starts N rank processes itself BEFORE it
   touches the GPU (it never initialises HIP, never re-execs), relays rank 0's JSON line and exits non-zero if a rank fails.
+  A plain run sets up, warms up, times the K steps and reports them.  --full also measures what the headline figure does not
+  need, in extra untimed runs after the timed steps: per-kernel HIP-event timings and rooflines, the rollout / update split,
+  the torch-update comparison of --workload wt256 / wtmod256 and the CPU baseline (unless --no-cpu-baseline).
+  --dump-outputs DIR writes what the last timed step computed (rank 0's trajectory buffer, network weights and update
+  objectives) as DIR/<name>.npy; inputs are seeded, so two builds can be compared output for output.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -135,8 +140,44 @@ def build_stack(device, rank, world, dp):
 
 def one_step(env, agent, buf):
     steps = agent.explore_env(env, buf, LANES * T_EP, 1.0, GAMMA)
-    agent.update_net(buf, LANES * T_EP, BATCH, REPEAT)
-    return steps
+    return steps, agent.update_net(buf, LANES * T_EP, BATCH, REPEAT)
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # array data; with the .npy headers the files stay under 64 MB
+
+
+def step_outputs(agent, buf, upd, prefix=""):
+    """What a caller of one timed step receives: the agent's networks after the update (the fused update writes the module
+    parameters in place), the trajectory / replay buffer the rollout filled and update_net's objectives."""
+    arrays = {}
+    for net in ("act", "cri", "act_target", "cri_target"):
+        module = getattr(agent, net, None)
+        if isinstance(module, torch.nn.Module):
+            arrays.update({f"{prefix}{net}.{k}": v for k, v in module.state_dict().items()})
+    for name in ("state", "action", "noise", "reward", "mask", "done", "other"):
+        if torch.is_tensor(getattr(buf, name, None)):
+            arrays[f"{prefix}buf.{name}"] = getattr(buf, name)
+    arrays[f"{prefix}update_objectives"] = np.asarray(upd, dtype=np.float64)
+    return arrays
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float64 kept, everything else as float32.  Above 60 MiB in all, every
+    array of more than one row keeps the same fraction of its rows (first axis): a sorted np.random.default_rng(0) sample, so the
+    same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    fixed = sum(a.nbytes for a in host.values() if a.ndim == 0 or a.shape[0] <= 1)
+    frac = min(1.0, (DUMP_BUDGET_BYTES - fixed) / max(total - fixed, 1))
+    for name, a in host.items():
+        if frac < 1.0 and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * frac))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def _cpu_model():
@@ -297,9 +338,12 @@ def bench_water_tank(args, device, json_fd):
     agent.fix_K()
     buf = make_buffer(agent, env, lanes * T)
 
+    upd = None
+
     def step():
+        nonlocal upd
         n = agent.explore_env(env, buf, lanes * T, 1.0, GAMMA)
-        agent.update_net(buf, lanes * T, BATCH, REPEAT)
+        upd = agent.update_net(buf, lanes * T, BATCH, REPEAT)
         return n
     for _ in range(args.warmup):
         step()
@@ -308,15 +352,17 @@ def bench_water_tank(args, device, json_fd):
     total = sum(step() for _ in range(args.steps))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    roofline = grad_roofline(agent, lambda: agent.update_net(buf, lanes * T, BATCH, REPEAT), env.state_dim, NET_DIM,
-                             "ppo_minibatch_grad = ppo_fused_dual_kernel<4, modular_actor> + ppo_grad_reduce_kernel (one minibatch of "
-                             "65536 water-tank samples, D = 4)")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(agent, buf, upd))
     out = {"metric": "env-steps/sec (rollout+update), water-tank env, 4096 parallel envs", "value": total / dt,
            "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "water tank Integrator-v2 (reward 'distance'), 4096 lanes x 200-step episodes, "
-                                  "ResidualIntegratorModularPPO net_dim 128, batch 65536, repeat 8"},
-           "roofline": roofline}
+                                  "ResidualIntegratorModularPPO net_dim 128, batch 65536, repeat 8"}}
+    if args.full:
+        out["roofline"] = grad_roofline(agent, lambda: agent.update_net(buf, lanes * T, BATCH, REPEAT), env.state_dim, NET_DIM,
+                                        "ppo_minibatch_grad = ppo_fused_dual_kernel<4, modular_actor> + ppo_grad_reduce_kernel (one "
+                                        "minibatch of 65536 water-tank samples, D = 4)")
     emit(json_fd, out)
 
 
@@ -331,7 +377,7 @@ def bench_water_tank_256(args, device, json_fd, modular=False):
     from pime_amd.elegantrl.run import make_buffer
     lanes, T = 4096, 200
 
-    def run(fused_update, steps, warmup):
+    def run(fused_update, steps, warmup, dump_dir=None):
         # modular: the script's second block (run_watertank_changing.sh:11-18): ResidualIntegratorModularPPO on the Integrator
         # observation, served by the 16-tile family's modular kernels (mlp16m_forward_kernel, ppo16m_kernel) since round 3
         env = gym_control.make_vec(gym_control.WT_INTEGRATOR if modular else gym_control.WT_STACKING.format(10), lanes, device=device,
@@ -348,9 +394,12 @@ def bench_water_tank_256(args, device, json_fd, modular=False):
         agent.fix_K()
         buf = make_buffer(agent, env, lanes * T)
 
+        upd = None
+
         def step():
+            nonlocal upd
             n = agent.explore_env(env, buf, lanes * T, 1.0, GAMMA)
-            agent.update_net(buf, lanes * T, BATCH, REPEAT)
+            upd = agent.update_net(buf, lanes * T, BATCH, REPEAT)
             return n
         for _ in range(warmup):
             step()
@@ -359,9 +408,11 @@ def bench_water_tank_256(args, device, json_fd, modular=False):
         total = sum(step() for _ in range(steps))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if dump_dir:
+            dump_outputs(dump_dir, step_outputs(agent, buf, upd))
         took_hip = bool(agent._packed.get("fused"))
         roof = None
-        if took_hip:
+        if took_hip and args.full:
             roof = grad_roofline(agent, lambda: agent.update_net(buf, lanes * T, BATCH, REPEAT), env.state_dim, 256,
                                  ("ppo_minibatch_grad = ppo16_kernel<16, critic> + ppo16m_kernel (modular actor) + ppo_grad_reduce_kernel"
                                   if modular else
@@ -369,9 +420,8 @@ def bench_water_tank_256(args, device, json_fd, modular=False):
                                  + " (one minibatch of 65536 samples at width 256, streamed 16-tile family)")
         env.close()
         return total / dt, dt / steps * 1e3, took_hip, roof
-    v, ms, hip, roofline = run(True, args.steps, args.warmup)
+    v, ms, hip, roofline = run(True, args.steps, args.warmup, args.dump_outputs)
     assert hip, "width 256 did not take the HIP gradient path"
-    v_t, ms_t, _, _ = run(False, max(1, args.steps // 2), 1)
     name = "Integrator env, ResidualIntegratorModularPPO" if modular else "Stacking10 env"
     out = {"metric": f"env-steps/sec (rollout+update), water-tank {name}, 4096 parallel envs, net_dim 256", "value": v,
            "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
@@ -380,10 +430,12 @@ def bench_water_tank_256(args, device, json_fd, modular=False):
                                    "ResidualIntegratorModularPPO net_dim 256 (run_watertank_changing.sh:11-18), batch 65536, repeat 8")
                       if modular else
                                   ("water tank Stacking10-v2 (30-float observation, reward 'distance'), 4096 lanes x 200-step "
-                                   "episodes, ResidualPPO net_dim 256 (run_watertank_changing.sh), batch 65536, repeat 8")},
-           "roofline": roofline,
-           "torch_update": {"value": v_t, "unit": "env-steps/s", "ms_per_step": ms_t,
-                            "what": "same step, update_net on PyTorch-ROCm autograd + rocBLAS (round 1's width-256 path)"}}
+                                   "episodes, ResidualPPO net_dim 256 (run_watertank_changing.sh), batch 65536, repeat 8")}}
+    if args.full:
+        v_t, ms_t, _, _ = run(False, max(1, args.steps // 2), 1)
+        out["roofline"] = roofline
+        out["torch_update"] = {"value": v_t, "unit": "env-steps/s", "ms_per_step": ms_t,
+                               "what": "same step, update_net on PyTorch-ROCm autograd + rocBLAS (round 1's width-256 path)"}
     emit(json_fd, out)
 
 
@@ -489,46 +541,8 @@ def launcher_selftest(json_fd):
         os.write(json_fd, (json.dumps({"selftest": "launcher", "n_gpus": got_world, "max_t": t, "sum": total}) + "\n").encode())
 
 
-def bench_water_tank_td3(args, device, json_fd, rank=0, world=1, dp=None):
-    """BASELINE config 2 as BASELINE.json words it: water-tank Integrator env, 4096 vectorised instances, residual TD3
-    (AgentResidualTD3: composed from the reference's TD3 pieces, SURVEY.md fact 5).  One step = 200 lock-steps of all lanes
-    (one episode each: 819 200 transitions into the device ring) + 200 TD3 optimizer steps (one per lock-step, the reference's
-    schedule counted per lock-step), batch 4096, net_dim 128; every optimizer step four hand-written launches (pime_td3_step), an
-    update one HIP graph."""
-    from pime_amd import gym_control
-    from pime_amd.elegantrl.agent_residual import AgentResidualTD3
-    from pime_amd.elegantrl.run import make_buffer
-    lanes, T, batch = 4096, 200, 4096
-    env = gym_control.make_vec(gym_control.WT_INTEGRATOR, lanes, device=device, state_mode="mixed", seed=0, reward_type="distance")
-    torch.manual_seed(0)
-    agent = AgentResidualTD3(device=device)
-    agent.init(NET_DIM, env.state_dim, 1)
-    agent.init_residual({"init_K": env.K.reshape(-1, 1)})
-    agent.dp = dp   # data parallel: every rank its own lanes and ring; both gradients of a step all-reduced (ops.FusedTD3.step_dp)
-    if dp is not None:
-        dp.broadcast_module(agent.act, agent.cri)
-        agent.act_target.load_state_dict(agent.act.state_dict()); agent.cri_target.load_state_dict(agent.cri.state_dict())
-        torch.manual_seed(1000 + rank)
-    buf = make_buffer(agent, env, 2 ** 21)
-
-    def step():
-        n = agent.explore_env(env, buf, lanes * T, 1.0, GAMMA)
-        agent.update_net(buf, lanes * T, batch, 1)
-        return n
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize()
-    if dp is not None:
-        dp.barrier()
-    t0 = time.perf_counter()
-    total = sum(step() for _ in range(args.steps))
-    torch.cuda.synchronize()
-    if dp is not None:
-        dp.barrier()
-    dt = time.perf_counter() - t0
-    if dp is not None:
-        dt = dp.max_over_ranks(dt)
-        total = total * world
+def td3_roofline(agent, buf, lanes, T, batch):
+    """--full: the `roofline` block of --workload wt_td3, from two extra, untimed updates."""
     # roofline of the update (92 % of the step): ONE TD3 optimizer step = four hand-written launches (td3_critic_kernel,
     # td3_apply_kernel, td3_actor_kernel, td3_apply_kernel; csrc/td3_fused.hip), the 200 steps of an update replayed as one HIP
     # graph; HIP events around that replay on the stream it runs on.  Algorithmic flops per sample (net_dim 128, D = 4): actor
@@ -569,6 +583,53 @@ def bench_water_tank_td3(args, device, json_fd, rank=0, world=1, dp=None):
                         "update's 200 steps; batch 4096 = 256 workgroups of one 16-sample tile, the eight waves of a workgroup "
                         "(two per SIMD) owning one of a layer's eight output-feature tiles each (v_mfma_f32_16x16x4_f32); the exploration is ONE launch per "
                         "explore call (pime_rollout_offpolicy)"}
+    return roofline
+
+
+def bench_water_tank_td3(args, device, json_fd, rank=0, world=1, dp=None):
+    """BASELINE config 2 as BASELINE.json words it: water-tank Integrator env, 4096 vectorised instances, residual TD3
+    (AgentResidualTD3: composed from the reference's TD3 pieces, SURVEY.md fact 5).  One step = 200 lock-steps of all lanes
+    (one episode each: 819 200 transitions into the device ring) + 200 TD3 optimizer steps (one per lock-step, the reference's
+    schedule counted per lock-step), batch 4096, net_dim 128; every optimizer step four hand-written launches (pime_td3_step), an
+    update one HIP graph."""
+    from pime_amd import gym_control
+    from pime_amd.elegantrl.agent_residual import AgentResidualTD3
+    from pime_amd.elegantrl.run import make_buffer
+    lanes, T, batch = 4096, 200, 4096
+    env = gym_control.make_vec(gym_control.WT_INTEGRATOR, lanes, device=device, state_mode="mixed", seed=0, reward_type="distance")
+    torch.manual_seed(0)
+    agent = AgentResidualTD3(device=device)
+    agent.init(NET_DIM, env.state_dim, 1)
+    agent.init_residual({"init_K": env.K.reshape(-1, 1)})
+    agent.dp = dp   # data parallel: every rank its own lanes and ring; both gradients of a step all-reduced (ops.FusedTD3.step_dp)
+    if dp is not None:
+        dp.broadcast_module(agent.act, agent.cri)
+        agent.act_target.load_state_dict(agent.act.state_dict()); agent.cri_target.load_state_dict(agent.cri.state_dict())
+        torch.manual_seed(1000 + rank)
+    buf = make_buffer(agent, env, 2 ** 21)
+    upd = None
+
+    def step():
+        nonlocal upd
+        n = agent.explore_env(env, buf, lanes * T, 1.0, GAMMA)
+        upd = agent.update_net(buf, lanes * T, batch, 1)
+        return n
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize()
+    if dp is not None:
+        dp.barrier()
+    t0 = time.perf_counter()
+    total = sum(step() for _ in range(args.steps))
+    torch.cuda.synchronize()
+    if dp is not None:
+        dp.barrier()
+    dt = time.perf_counter() - t0
+    if dp is not None:
+        dt = dp.max_over_ranks(dt)
+        total = total * world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(agent, buf, upd))
     out = {"metric": "env-steps/sec (rollout+update), water-tank env, 4096 parallel envs, residual TD3", "value": total / dt,
            "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -577,8 +638,9 @@ def bench_water_tank_td3(args, device, json_fd, rank=0, world=1, dp=None):
                                   (" (one HIP graph per update)" if dp is None else
                                    " per rank (data parallel: five launches + two gradient all-reduces per step, one HIP graph per update where "
                                    "the collective can be captured)"),
-                      "parallelism": f"dp{world}"},
-           "roofline": roofline}
+                      "parallelism": f"dp{world}"}}
+    if args.full:   # every rank: the extra updates all-reduce under data parallelism
+        out["roofline"] = td3_roofline(agent, buf, lanes, T, batch)
     if rank == 0:
         emit(json_fd, out)
 
@@ -617,6 +679,8 @@ def bench_mixed16(args, device, json_fd, rank, world, dp):
         stacks.append((env, agent, buf, torch.cuda.Stream(device=device)))
     torch.manual_seed(1000 + rank)
 
+    upd = [None] * len(stacks)
+
     def step():
         cur = torch.cuda.current_stream()
         total = 0
@@ -626,8 +690,8 @@ def bench_mixed16(args, device, json_fd, rank, world, dp):
                 total += agent.explore_env(env, buf, lanes * env.max_step, 1.0, GAMMA)
         for env, agent, buf, stream in stacks:
             cur.wait_stream(stream)
-        for env, agent, buf, stream in stacks:
-            agent.update_net(buf, lanes * env.max_step, BATCH, REPEAT)
+        for i, (env, agent, buf, stream) in enumerate(stacks):
+            upd[i] = agent.update_net(buf, lanes * env.max_step, BATCH, REPEAT)
         return total
 
     def sync():
@@ -645,8 +709,13 @@ def bench_mixed16(args, device, json_fd, rank, world, dp):
     if dp is not None:
         dt = dp.max_over_ranks(dt)
         total = dp.sum_over_ranks(total)
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        for tag, (env, agent, buf, _), u in zip(("ph.", "wt."), stacks, upd):
+            arrays.update(step_outputs(agent, buf, u, prefix=tag))
+        dump_outputs(args.dump_outputs, arrays)
     roofline = None
-    if dp is None:   # (the event bracket forces the two-graph step sequence: single-rank runs only)
+    if args.full and dp is None:   # (the event bracket forces the two-graph step sequence: single-rank runs only)
         env_w, agent_w, buf_w, _ = stacks[1]
         roofline = grad_roofline(agent_w, lambda: agent_w.update_net(buf_w, lanes * env_w.max_step, BATCH, REPEAT), env_w.state_dim,
                                  NET_DIM, "ppo_minibatch_grad = ppo_fused_dual_kernel<4, modular_actor> + ppo_grad_reduce_kernel (one "
@@ -661,102 +730,18 @@ def bench_mixed16(args, device, json_fd, rank, world, dp):
                                       "Integrator-v2 lanes (reward 'distance') x 200-step episodes, state_mode mixed16 (binary16 "
                                       "I / observation / reward storage, f32 math, f64 x), ensemble ranges x1.5, "
                                       "ResidualIntegratorModularPPO net_dim 128 per family, batch 65536, repeat 8",
-                          "lanes_per_gpu": LANES, "parallelism": f"dp{world}"},
-               "roofline": roofline}
+                          "lanes_per_gpu": LANES, "parallelism": f"dp{world}"}}
+        if args.full:
+            out["roofline"] = roofline
         emit(json_fd, out)
     if dp is not None:
         torch.distributed.destroy_process_group()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--workload", default="ph", choices=["ph", "wt", "wt_td3", "wt256", "wtmod256", "mixed16"],
-                    help="ph: the headline config (BASELINE config 3); wt: config 2, water tank, 4096 lanes x 200 steps "
-                         "(reported for DESIGN.md; the headline metric is the ph line)")
-    ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # no launcher: become one, before anything touches the GPU
-        raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
-
-    # stdout must carry exactly ONE JSON line: libraries that print banners to fd 1 (RCCL prints its version block at
-    # communicator creation) are sent to stderr for the whole run, and the JSON is written to the saved descriptor.
-    sys.stdout.flush()
-    json_fd = os.dup(1)
-    os.dup2(2, 1)
-
-    from pime_amd import dist as pdist
-    rank, world, local = pdist.env_rank_world()
-    if world != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher set WORLD_SIZE={world}")
-    if args.selftest_launcher:
-        return launcher_selftest(json_fd)
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
-    # PIME_BENCH_REHEARSE=1: every rank on cuda:0 with gloo collectives -- a rehearsal of the launcher and the data-parallel
-    # step sequence on a one-GPU box (RCCL refuses two ranks on one device); its numbers mean nothing
-    rehearse = os.environ.get("PIME_BENCH_REHEARSE") == "1"
-    dev_index = 0 if rehearse else local
-    device = f"cuda:{dev_index}"
-    torch.cuda.set_device(dev_index)
-    dp = (pdist.init_from_env(backend="gloo" if rehearse else "nccl", device=device)
-          if (world > 1 or os.environ.get("PIME_FORCE_DP") == "1") else None)
-    if dp is not None:
-        world = torch.distributed.get_world_size()   # the RCCL communicator's size is what the JSON line reports
-
-    if args.workload == "mixed16":
-        return bench_mixed16(args, device, json_fd, rank, world, dp)
-    if args.workload == "wt":
-        return bench_water_tank(args, device, json_fd)
-    if args.workload == "wt256":
-        return bench_water_tank_256(args, device, json_fd)
-    if args.workload == "wtmod256":
-        return bench_water_tank_256(args, device, json_fd, modular=True)
-    if args.workload == "wt_td3":
-        return bench_water_tank_td3(args, device, json_fd, rank, world, dp)
-    env, agent, buf = build_stack(device, rank, world, dp)
-    timer = KernelTimer()
-    # time the hand-written kernels where the agent calls them
-    import pime_amd.ops as ops
-    agent.state_value = timer.wrap("mlp_forward<critic> value pass", agent.state_value)
-    agent.policy_mean = timer.wrap("mlp_forward<modular_actor> rollout", agent.policy_mean)
-    env.step_residual = timer.wrap("ph_step_kernel (fused residual)", env.step_residual)
-    env.rollout = timer.wrap("rollout_ph_kernel (50 steps, one launch)", env.rollout)
-    agent.backend.gae = timer.wrap("gae_scan_kernel", agent.backend.gae)
-    # "ppo_minibatch_grad" (the gradient launches of one minibatch) is timed with HIP events in ONE extra, untimed update
-    # after the measured region: bracketing it forces the two-graph step sequence, while the measured steps replay one
-    # graph per optimizer step.
-
-    def sync():
-        torch.cuda.synchronize()
-        if dp is not None:
-            dp.barrier()
-            torch.cuda.synchronize()
-
-    log("stack built; warmup")
-    for i in range(args.warmup):
-        one_step(env, agent, buf)
-        torch.cuda.synchronize()
-        log(f"warmup step {i} done")
-    sync()
-    timer.enabled = True
-    t_roll = t_upd = 0.0
-    t0 = time.perf_counter()
-    total = 0
-    for _ in range(args.steps):
-        total += one_step(env, agent, buf)
-    sync()
-    dt = time.perf_counter() - t0
-    timer.enabled = False
-    log(f"timed region: {dt:.3f}s for {args.steps} steps")
-    if dp is not None:
-        dt = dp.max_over_ranks(dt)
-        total = dp.sum_over_ranks(total)
-
+def headline_diagnostics(args, env, agent, buf, timer, sync, rank, world):
+    """--full on the headline workload: after the timed steps, the rollout / update split (one extra step), the per-launch
+    time of the gradient launches (two extra updates), the rooflines from the per-kernel HIP events of the timed steps and,
+    unless --no-cpu-baseline, the CPU baseline.  Every rank runs the extra steps (they all-reduce); rank 0 gets the dict."""
     # rollout / update split (one extra untimed step, synchronised between the halves)
     sync()
     a = time.perf_counter()
@@ -778,9 +763,7 @@ def main():
     agent.launch_timer = None
 
     if rank != 0:
-        if dp is not None:
-            torch.distributed.destroy_process_group()
-        return
+        return None
     ks = timer.summary()
     per_step = {k: n * ms / args.steps for k, (n, ms) in ks.items()}
     n_g, ms_g = grad_timer.summary()["ppo_minibatch_grad"]
@@ -850,15 +833,7 @@ def main():
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": env_gbs / HBM_PEAK_GBS,
                         "traffic": pmc_traffic_bytes(["ph_step_kernel"])[0], "algorithmic_bytes_per_launch": PH_STEP_BYTES * LANES,
                         "avg_launch_ms": ms_env, "note": "16384-lane launch moves 1.5 MB: launch-latency bound"}
-    out = {
-        "metric": "env-steps/sec (rollout+update), pH env, 16384 parallel envs",
-        "value": total / dt, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "pH v35, 16384 lanes/GPU x 50-step episodes, ensemble resampled every episode, "
-                               "ResidualIntegratorModularPPO net_dim 128, batch 65536, repeat 8 (100 optimizer steps)",
-                   "lanes_per_gpu": LANES, "episode_len": T_EP, "batch": BATCH, "repeat_times": REPEAT,
-                   "state_mode": "mixed (f32 state, f64 x/A/B/C)", "parallelism": f"dp{world}"},
+    extra = {
         "roofline": roofline,
         "roofline_env": roofline_env,
         "roofline_value_pass": {"kernel": "mlp_forward_kernel<4, critic> (819200 rows)", "bound": "mfma", "achieved": v_tf,
@@ -869,9 +844,122 @@ def main():
     }
     if not args.no_cpu_baseline and world == 1:
         log("cpu baseline (oracle env + torch CPU update) ...")
-        out["cpu_baseline"] = cpu_baseline()
+        extra["cpu_baseline"] = cpu_baseline()
         log("cpu baseline done")
-    emit(json_fd, out)
+    return extra
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-kernel timings and "
+                         "rooflines, the rollout / update split, the torch-update comparison (wt256 / wtmod256), the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 60 MiB)")
+    ap.add_argument("--workload", default="ph", choices=["ph", "wt", "wt_td3", "wt256", "wtmod256", "mixed16"],
+                    help="ph: the headline config (BASELINE config 3); wt: config 2, water tank, 4096 lanes x 200 steps "
+                         "(reported for DESIGN.md; the headline metric is the ph line)")
+    ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # no launcher: become one, before anything touches the GPU
+        raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
+
+    # stdout must carry exactly ONE JSON line: libraries that print banners to fd 1 (RCCL prints its version block at
+    # communicator creation) are sent to stderr for the whole run, and the JSON is written to the saved descriptor.
+    sys.stdout.flush()
+    json_fd = os.dup(1)
+    os.dup2(2, 1)
+
+    from pime_amd import dist as pdist
+    rank, world, local = pdist.env_rank_world()
+    if world != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher set WORLD_SIZE={world}")
+    if args.selftest_launcher:
+        return launcher_selftest(json_fd)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
+    # PIME_BENCH_REHEARSE=1: every rank on cuda:0 with gloo collectives -- a rehearsal of the launcher and the data-parallel
+    # step sequence on a one-GPU box (RCCL refuses two ranks on one device); its numbers mean nothing
+    rehearse = os.environ.get("PIME_BENCH_REHEARSE") == "1"
+    dev_index = 0 if rehearse else local
+    device = f"cuda:{dev_index}"
+    torch.cuda.set_device(dev_index)
+    dp = (pdist.init_from_env(backend="gloo" if rehearse else "nccl", device=device)
+          if (world > 1 or os.environ.get("PIME_FORCE_DP") == "1") else None)
+    if dp is not None:
+        world = torch.distributed.get_world_size()   # the RCCL communicator's size is what the JSON line reports
+
+    if args.workload == "mixed16":
+        return bench_mixed16(args, device, json_fd, rank, world, dp)
+    if args.workload == "wt":
+        return bench_water_tank(args, device, json_fd)
+    if args.workload == "wt256":
+        return bench_water_tank_256(args, device, json_fd)
+    if args.workload == "wtmod256":
+        return bench_water_tank_256(args, device, json_fd, modular=True)
+    if args.workload == "wt_td3":
+        return bench_water_tank_td3(args, device, json_fd, rank, world, dp)
+    env, agent, buf = build_stack(device, rank, world, dp)
+    timer = KernelTimer()
+    if args.full:   # time the hand-written kernels where the agent calls them
+        agent.state_value = timer.wrap("mlp_forward<critic> value pass", agent.state_value)
+        agent.policy_mean = timer.wrap("mlp_forward<modular_actor> rollout", agent.policy_mean)
+        env.step_residual = timer.wrap("ph_step_kernel (fused residual)", env.step_residual)
+        env.rollout = timer.wrap("rollout_ph_kernel (50 steps, one launch)", env.rollout)
+        agent.backend.gae = timer.wrap("gae_scan_kernel", agent.backend.gae)
+    # "ppo_minibatch_grad" (the gradient launches of one minibatch) is timed with HIP events in ONE extra, untimed update
+    # after the measured region: bracketing it forces the two-graph step sequence, while the measured steps replay one
+    # graph per optimizer step.
+
+    def sync():
+        torch.cuda.synchronize()
+        if dp is not None:
+            dp.barrier()
+            torch.cuda.synchronize()
+
+    log("stack built; warmup")
+    for i in range(args.warmup):
+        one_step(env, agent, buf)
+        torch.cuda.synchronize()
+        log(f"warmup step {i} done")
+    sync()
+    timer.enabled = args.full
+    t0 = time.perf_counter()
+    total = 0
+    for _ in range(args.steps):
+        n, upd = one_step(env, agent, buf)
+        total += n
+    sync()
+    dt = time.perf_counter() - t0
+    timer.enabled = False
+    log(f"timed region: {dt:.3f}s for {args.steps} steps")
+    if dp is not None:
+        dt = dp.max_over_ranks(dt)
+        total = dp.sum_over_ranks(total)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(agent, buf, upd))
+    extra = headline_diagnostics(args, env, agent, buf, timer, sync, rank, world) if args.full else {}
+    if rank == 0:
+        out = {
+            "metric": "env-steps/sec (rollout+update), pH env, 16384 parallel envs",
+            "value": total / dt, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "pH v35, 16384 lanes/GPU x 50-step episodes, ensemble resampled every episode, "
+                                   "ResidualIntegratorModularPPO net_dim 128, batch 65536, repeat 8 (100 optimizer steps)",
+                       "lanes_per_gpu": LANES, "episode_len": T_EP, "batch": BATCH, "repeat_times": REPEAT,
+                       "state_mode": "mixed (f32 state, f64 x/A/B/C)", "parallelism": f"dp{world}"},
+        }
+        out.update(extra)
+        emit(json_fd, out)
     if dp is not None:
         torch.distributed.destroy_process_group()
 

@@ -66,8 +66,10 @@ def _hung_ranks(tmp_path, extra_env):
     p = subprocess.Popen([sys.executable, BENCH, "--gpus", "2", "--selftest-launcher"], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE)
     t_end = time.time() + 120
-    while time.time() < t_end and not all(os.path.exists(f"{tag}.{r}") for r in (0, 1)):
+    while time.time() < t_end and p.poll() is None and not all(os.path.exists(f"{tag}.{r}") for r in (0, 1)):
         time.sleep(0.1)
+    assert all(os.path.exists(f"{tag}.{r}") for r in (0, 1)), \
+        f"the ranks never reached their hang (parent exit code {p.poll()}): {p.stderr.read().decode()[-2000:] if p.poll() is not None else ''}"
     pids = [int(open(f"{tag}.{r}").read()) for r in (0, 1)]
     assert all(_session_alive(pid) for pid in pids)
     return p, pids
@@ -85,9 +87,11 @@ def test_sigterm_to_the_parent_leaves_no_rank_behind(tmp_path):
 
 
 def test_deadline_stops_hung_ranks(tmp_path):
+    """The deadline runs from the parent's start, so it must leave the ranks time to import torch and reach their hang first
+    (a few seconds on a cold or busy machine): 30 s."""
     import time
-    p, pids = _hung_ranks(tmp_path, {"PIME_BENCH_DEADLINE_S": "3"})
-    assert p.wait(timeout=60) == 124
+    p, pids = _hung_ranks(tmp_path, {"PIME_BENCH_DEADLINE_S": "30"})
+    assert p.wait(timeout=90) == 124
     assert b"deadline reached" in p.stderr.read()
     time.sleep(0.2)
     assert not any(_session_alive(pid) for pid in pids)

@@ -9,7 +9,7 @@ PIME_TD3_TRACE=1 timeout -k 10 120 python tools/td3_trace.py 2>&1 | grep "td3 tr
 rm -f $OUT/${TAG}.log
 for rep in 1 2 3; do
   for v in "$@"; do
-    r=$(PIME_ALLOW_LIB_OVERRIDE=1 PIME_LIB_PATH=$PWD/variants/$v.so timeout -k 10 200 python bench.py --workload wt_td3 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['value']/1e6,2), 'M', round(d['roofline']['avg_launch_ms']*1e3,2), 'us/step')") || exit 1
+    r=$(PIME_ALLOW_LIB_OVERRIDE=1 PIME_LIB_PATH=$PWD/variants/$v.so timeout -k 10 200 python bench.py --full --workload wt_td3 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['value']/1e6,2), 'M', round(d['roofline']['avg_launch_ms']*1e3,2), 'us/step')") || exit 1
     echo "$v: $r" >> $OUT/${TAG}.log
   done
 done

@@ -11,11 +11,11 @@ for w in 4 8; do
 done
 for rep in 1 2; do
   for w in 4 8; do
-    PIME_TD3_WAVES=$w timeout -k 10 200 python bench.py --workload wt_td3 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_w${w}_$rep.json 2> $OUT/${TAG}_bench_w${w}_$rep.err || { tail -20 $OUT/${TAG}_bench_w${w}_$rep.err; exit 1; }
+    PIME_TD3_WAVES=$w timeout -k 10 200 python bench.py --full --workload wt_td3 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_w${w}_$rep.json 2> $OUT/${TAG}_bench_w${w}_$rep.err || { tail -20 $OUT/${TAG}_bench_w${w}_$rep.err; exit 1; }
     python -c "import json,sys; d=json.load(open('$OUT/${TAG}_bench_w${w}_$rep.json')); print('waves $w rep $rep:', round(d['value']/1e6,2), 'M', round(d['roofline']['avg_launch_ms']*1e3,2), 'us/step')"
   done
 done
 for w in 4 8; do
-  PIME_TD3_WAVES=$w timeout -k 10 200 bash tools/kstats.sh bench.py --workload wt_td3 --steps 3 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_kstats_w$w.txt 2>&1 || { tail -20 $OUT/${TAG}_kstats_w$w.txt; exit 1; }
+  PIME_TD3_WAVES=$w timeout -k 10 200 bash tools/kstats.sh bench.py --full --workload wt_td3 --steps 3 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_kstats_w$w.txt 2>&1 || { tail -20 $OUT/${TAG}_kstats_w$w.txt; exit 1; }
   echo "waves $w"; head -6 $OUT/${TAG}_kstats_w$w.txt
 done
