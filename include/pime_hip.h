@@ -397,10 +397,11 @@ int pime_rollout_offpolicy(pime_env* env, int32_t md, const float* packed_actor,
  * min(cri_target.get_q1_q2), q_label, cri.get_q1_q2, SmoothL1 x 2), obj_critic.backward(), cri_optimizer.step(), the delayed
  * soft_update(cri_target) (:116-124), obj_actor = -cri_target(state, act(state)).mean() (:323-324), obj_actor.backward(),
  * act_optimizer.step() and the delayed soft_update(act_target): FOUR launches (csrc/td3_fused.hip) -- critic gradients
- * (one 16-sample tile per workgroup, its four waves splitting every layer's output features), slab reduction + Adam + soft
+ * (one 16-sample tile per workgroup, its four or eight waves splitting every layer's output features), slab reduction + Adam + soft
  * update of the critic, actor gradients (through the TARGET critic's first head, as the reference has it), the same for the actor.
  * Nets: Actor (net.py:96-110: D -> md ReLU -> md ReLU -> md ReLU -> 1, tanh) and CriticTwin (net.py:305-332: D+1 -> md ReLU -> md
- * ReLU, two linear heads), action_dim 1, D <= 7, md 64 | 128.  The weights are read where they live: every net is ONE flat
+ * ReLU, two linear heads), action_dim 1, 1 <= D <= 31, md 64 | 128 | 256 (width 256: the md x md weights streamed in k-slices,
+ * the Stacking observations' first layers in eight k-steps).  The weights are read where they live: every net is ONE flat
  * float32 tensor in nn.Module parameter order with each tensor starting on a multiple of 4 floats (pime_td3_param_offsets;
  * padding words zero) -- no packed images, nothing to re-pack after a step. */
 typedef struct pime_td3_net {

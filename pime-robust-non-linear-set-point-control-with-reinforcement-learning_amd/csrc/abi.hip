@@ -1186,14 +1186,15 @@ int pime_td3_supported(int32_t D, int32_t action_dim, int32_t md) { return td3_s
 
 int64_t pime_td3_param_floats(int32_t which, int32_t D, int32_t md) {
     if (!td3_supported(D, 1, md) || which < 0 || which > 1) {
-        set_error("pime_td3_param_floats: unsupported net (which %d, D %d, width %d)", which, D, md);
+        set_error("pime_td3_param_floats: unsupported net (which %d, D %d, width %d; served: 1 <= D <= %d, width 64 | 128 | 256)", which, D, md, kTd3MaxD);
         return -1;
     }
     return which == 0 ? td3_actor_off(D, md).total : td3_critic_off(D, md).total;
 }
 
 int pime_td3_param_offsets(int32_t which, int32_t D, int32_t md, int32_t* offsets) {
-    PIME_REQUIRE(offsets && td3_supported(D, 1, md) && (which == 0 || which == 1), "pime_td3_param_offsets: bad arguments");
+    PIME_REQUIRE(offsets && td3_supported(D, 1, md) && (which == 0 || which == 1),
+                 "pime_td3_param_offsets: bad arguments (which %d, D %d, width %d; served: 1 <= D <= %d, width 64 | 128 | 256)", which, D, md, kTd3MaxD);
     if (which == 0) {
         const Td3ActorOff o = td3_actor_off(D, md);
         const int v[8] = {o.W1, o.b1, o.W2, o.b2, o.W3, o.b3, o.w4, o.b4};
@@ -1208,7 +1209,7 @@ int pime_td3_param_offsets(int32_t which, int32_t D, int32_t md, int32_t* offset
 
 int64_t pime_td3_workspace_floats(int32_t D, int32_t md, int32_t B) {
     if (!td3_supported(D, 1, md) || B < 1) {
-        set_error("pime_td3_workspace_floats: unsupported shape (D %d, width %d, batch %d)", D, md, B);
+        set_error("pime_td3_workspace_floats: unsupported shape (D %d, width %d, batch %d; served: 1 <= D <= %d, width 64 | 128 | 256)", D, md, B, kTd3MaxD);
         return -1;
     }
     return td3_workspace_floats(D, md, B);
@@ -1223,7 +1224,7 @@ static int check_td3_net(const pime_td3_net* n, const char* what) {
 
 int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_td3_batch* b, float tau,
                   int32_t update_freq, int32_t soft_mode, int32_t phases, float* workspace, float* loss, pime_stream stream) {
-    PIME_REQUIRE(td3_supported(D, 1, md), "pime_td3_step: no kernel for state_dim %d width %d (D <= %d, width 64 | 128)", D, md, kTd3MaxD);
+    PIME_REQUIRE(td3_supported(D, 1, md), "pime_td3_step: no kernel for state_dim %d width %d (1 <= D <= %d, width 64 | 128 | 256)", D, md, kTd3MaxD);
     if (int rc = check_td3_net(actor, "actor")) return rc;
     if (int rc = check_td3_net(critic, "critic")) return rc;
     PIME_REQUIRE(b && b->state && b->other && b->idx && b->nxt && b->B >= 1, "pime_td3_step: bad pime_td3_batch");
@@ -1238,9 +1239,9 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
     const Td3SlabLayout LA = td3_actor_slab(D, md), LC = td3_critic_slab(D, md);
     float* const slab_c = workspace;
     float* const slab_a = workspace + (size_t)grid * LC.stride;
-    // [2][B][8] gathered rows, by row parity: written by the critic launch of a row, read by its actor launch -- which may still run
+    // [2][B][td3_xg_stride(D)] gathered rows, by row parity: written by the critic launch of a row, read by its actor launch -- which may still run
     // while the critic launch of the NEXT row (other parity) gathers (the caller's two-stream schedule, see include/pime_hip.h)
-    float* const xg = slab_a + (size_t)grid * LA.stride + (size_t)(b->row & 1) * b->B * 8;
+    float* const xg = slab_a + (size_t)grid * LA.stride + (size_t)(b->row & 1) * b->B * td3_xg_stride(D);
     Td3Batch tb{b->state, b->other, b->idx, b->nxt, b->noise, (long long)b->row, b->epoch, b->B, b->noise_seed, b->noise_epoch, b->policy_noise, b->noise_clip};
     auto apply = [&](const pime_td3_net* n, const Td3SlabLayout& L, const float* slab, int slot, int mode) {
         Td3ApplyArgs a{};

@@ -4,10 +4,16 @@
 
 namespace pime {
 
-constexpr int kTd3MaxD = 7;        // state columns: the critic's first layer sees D + 1 <= 8 inputs (two 16x16x4 k-steps)
+constexpr int kTd3MaxD = 31;       // state columns: the critic's first layer sees D + 1 <= 32 inputs (eight 16x16x4 k-steps)
 constexpr int kTd3MaxSlabs = 512;  // workgroups (= partial-gradient slabs) per gradient launch
 
 __host__ __device__ constexpr int td3_align4(int v) { return (v + 3) & ~3; }
+// k-steps of the first layers: 2 while the critic's D + 1 inputs fit 8 columns (pH, water tank: the round-4 kernels), else 8 (32 columns:
+// the Stacking observations).  The gathered input rows (xin in LDS, xg in the workspace) are 4 KF floats wide; the first-layer
+// weight gradients have ceil(4 KF / 16) column tiles.
+__host__ __device__ constexpr int td3_first_ksteps(int D) { return D + 1 <= 8 ? 2 : 8; }
+__host__ __device__ constexpr int td3_xg_stride(int D) { return 4 * td3_first_ksteps(D); }
+__host__ __device__ constexpr int td3_first_tiles(int D) { return (td3_xg_stride(D) + 15) / 16; }
 
 // Flat parameter layout of the two nets: nn.Module parameter order, every tensor starting on a multiple of 4 floats (16-byte
 // vector loads of rows, biases and heads); the padding words are zero and stay zero (their gradient is never written).
@@ -34,7 +40,8 @@ __host__ __device__ inline Td3CriticOff td3_critic_off(int D, int md) {
 }
 
 // One workgroup's partial gradient ("slab").  Weight matrices are BLOCK-major in accumulator order -- element ((a TB + b) 64 + lane) 4 + r
-// is dW[16 a + 4 (lane >> 4) + r][16 b + (lane & 15)] (one 16-byte store per lane and block; the first layers are one column tile, TB = 1)
+// is dW[16 a + 4 (lane >> 4) + r][16 b + (lane & 15)] (one 16-byte store per lane and block; the first layers have td3_first_tiles(D)
+// column tiles: 1 up to D = 7, 2 beyond -- columns past the tensor's are zero in the slab and owned by no element)
 // -- vectors in tensor order; then a 4-float scalar slot ([0] = the loss sum of the group's samples).
 struct Td3Seg {
     int slab_off, n4;      // position (floats) and length (16-byte words) inside a slab
@@ -54,7 +61,7 @@ __host__ __device__ inline Td3SlabLayout td3_actor_slab(int D, int md) {
     int o = 0, k = 0;
     auto mat = [&](int flat, int tb, int ldw) { L.seg[k++] = Td3Seg{o, NT * tb * 64, flat, tb, ldw, ldw, 0}; o += NT * tb * 256; };
     auto vec = [&](int flat, int n) { L.seg[k++] = Td3Seg{o, td3_align4(n) / 4, flat, 0, 0, 0, n}; o += td3_align4(n); };
-    mat(P.W1, 1, D); vec(P.b1, md); mat(P.W2, NT, md); vec(P.b2, md); mat(P.W3, NT, md); vec(P.b3, md); vec(P.w4, md); vec(P.b4, 1);
+    mat(P.W1, td3_first_tiles(D), D); vec(P.b1, md); mat(P.W2, NT, md); vec(P.b2, md); mat(P.W3, NT, md); vec(P.b3, md); vec(P.w4, md); vec(P.b4, 1);
     L.nseg = k; L.scalar_off = o; L.stride = o + 4;
     return L;
 }
@@ -65,7 +72,7 @@ __host__ __device__ inline Td3SlabLayout td3_critic_slab(int D, int md) {
     int o = 0, k = 0;
     auto mat = [&](int flat, int tb, int ldw) { L.seg[k++] = Td3Seg{o, NT * tb * 64, flat, tb, ldw, ldw, 0}; o += NT * tb * 256; };
     auto vec = [&](int flat, int n) { L.seg[k++] = Td3Seg{o, td3_align4(n) / 4, flat, 0, 0, 0, n}; o += td3_align4(n); };
-    mat(P.W1, 1, D + 1); vec(P.b1, md); mat(P.W2, NT, md); vec(P.b2, md); vec(P.q1w, md); vec(P.q1b, 1); vec(P.q2w, md); vec(P.q2b, 1);
+    mat(P.W1, td3_first_tiles(D), D + 1); vec(P.b1, md); mat(P.W2, NT, md); vec(P.b2, md); vec(P.q1w, md); vec(P.q1b, 1); vec(P.q2w, md); vec(P.q2b, 1);
     L.nseg = k; L.scalar_off = o; L.stride = o + 4;
     return L;
 }
@@ -90,7 +97,7 @@ struct Td3GradArgs {
     const float *act, *cri;    // critic launch: TARGET actor, ONLINE critic;  actor launch: ONLINE actor, TARGET critic
     const float* cri_target;   // critic launch only: the target critic
     float* slab;               // [grid][stride]
-    float* xg;                 // [B][8]: the minibatch's state rows (+ action), gathered by the critic launch, read back by the actor launch
+    float* xg;                 // [B][td3_xg_stride(D)]: the minibatch's state rows (+ action), gathered by the critic launch, read back by the actor launch
     int stride, ngroups;
     long long* trace;          // tuning aid (PIME_TD3_TRACE): wall-clock marks of workgroup 0 / thread 0, NULL in production
 };

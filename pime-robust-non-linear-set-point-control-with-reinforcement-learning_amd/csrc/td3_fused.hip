@@ -25,6 +25,11 @@
 // The minibatch rows come from an index table [steps][B]; the row of a step is a launch argument (a captured graph of an update's
 // steps bakes each row into its nodes: no launch advances shared state); the smoothing noise comes from a table of normals (parity
 // tests inject the reference's draws) or from Philox stream 3 in the kernel.
+// Wider shapes: the Stacking observations (D up to 31) take the first layers in eight k-steps instead of two
+// (template KF); width 256 keeps the decomposition -- eight waves, two output tiles each -- but streams the md x md weights in k-slices
+// (Wts / wlayer: a register block of a layer would be 128 VGPRs), forms the md x md weight gradients in column slices, and at KF = 8
+// reads the first-layer weights from global memory (they do not fit beside the chain images in LDS).  The round-4 instantiations
+// (width 64 / 128, D <= 7) compile to the same arithmetic as before.
 #include <cstdlib>
 #include "td3.hpp"
 #include "pime_common.hpp"
@@ -128,6 +133,47 @@ __device__ __forceinline__ void load_wt(const float* __restrict__ W, int t0, int
             for (int r = 0; r < 4; ++r) w[n][kt][r] = W[PIME_TD3_WOFF(o + (16 * kt + r) * (NT * 16) + 16 * n)];
 }
 
+// Width 256 (NT = 16, eight waves, PER = 2): a [PER][NT] register block of one layer's weights is 128 VGPRs, two of them (the next
+// layer's, loaded a layer ahead) plus the activation's in[NT] exceed the 256 VGPRs a wave has at two waves per SIMD.  There the
+// weights are STREAMED: the layer walks its k-tiles in slices of kSliceK, the loads of slice c + 1 in flight while slice c's
+// MFMAs issue (2 x PER x kSliceK x 4 = 64 VGPRs).  Wts<NT, PER, S> is what a wave holds between "load" and "layer": the registers
+// (S = false: the round-4 code, unchanged) or just where the tensor is and whether it is read transposed (S = true).
+constexpr int kSliceK = 4;
+template <int NT, int PER, bool S>
+struct Wts { f32x4_t w[PER][NT]; };
+template <int NT, int PER>
+struct Wts<NT, PER, true> { const float* W; bool tr; };
+
+template <int NT, int PER>
+__device__ __forceinline__ void wload(Wts<NT, PER, false>& w, const float* __restrict__ W, int t0, int lane) { load_w<NT, PER>(W, t0, lane, w.w); }
+template <int NT, int PER>
+__device__ __forceinline__ void wload_t(Wts<NT, PER, false>& w, const float* __restrict__ W, int t0, int lane) { load_wt<NT, PER>(W, t0, lane, w.w); }
+template <int NT, int PER>
+__device__ __forceinline__ void wload(Wts<NT, PER, true>& w, const float* W, int, int) { w.W = W; w.tr = false; }
+template <int NT, int PER>
+__device__ __forceinline__ void wload_t(Wts<NT, PER, true>& w, const float* W, int, int) { w.W = W; w.tr = true; }
+
+// slice c of output tiles t0 .. t0 + PER - 1: k-tiles c kSliceK .. (c + 1) kSliceK - 1, as load_w / load_wt would hold them
+template <int NT, int PER>
+__device__ __forceinline__ void wslice(const float* __restrict__ W, bool tr, int t0, int lane, int c, f32x4_t (&w)[PER][kSliceK]) {
+    constexpr int MD = NT * 16;
+    if (!tr) {
+        const int o = (16 * t0 + (lane & 15)) * MD + 4 * (lane >> 4);
+#pragma unroll
+        for (int n = 0; n < PER; ++n)
+#pragma unroll
+            for (int k = 0; k < kSliceK; ++k) w[n][k] = ld4(W + o + n * 16 * MD + 16 * (c * kSliceK + k));
+    } else {
+        const int o = (4 * (lane >> 4)) * MD + 16 * t0 + (lane & 15);
+#pragma unroll
+        for (int k = 0; k < kSliceK; ++k)
+#pragma unroll
+            for (int n = 0; n < PER; ++n)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) w[n][k][r] = W[o + (16 * (c * kSliceK + k) + r) * MD + 16 * n];
+    }
+}
+
 // out[n] += W in (output tiles t0 .. t0 + PER - 1).  The caller initialises out: bias_get IN FRONT of the barrier that publishes `in`
 // (the bias lives in the small-tensor image; read behind the barrier it was the youngest LDS read in front of the first MFMA, which
 // then waited for all of the activation's reads -- lgkmcnt(0) -- instead of the first), or zero4 for the backward chain.
@@ -151,20 +197,44 @@ __device__ __forceinline__ void layer(const f32x4_t (&w)[PER][NT], const f32x4_t
             for (int n = 0; n < PER; ++n) out[n] = mfma16(w[n][kt][r], in[kt][r], out[n]);
 }
 
-// first layer, fan-in Din <= 8: k-step 0 = input columns 0..3, k-step 1 = columns 4..7.  x0 / x1: this lane's B operands, input
-// column q / 4 + q of sample j (0 beyond Din).
-template <int PER>
+template <int NT, int PER>
+__device__ __forceinline__ void wlayer(const Wts<NT, PER, false>& w, const f32x4_t (&in)[NT], f32x4_t (&out)[PER]) { layer<NT, PER>(w.w, in, out); }
+// the streamed layer: the same MFMAs in the same order as layer()
+template <int NT, int PER>
+__device__ __forceinline__ void wlayer(const Wts<NT, PER, true>& w, const f32x4_t (&in)[NT], f32x4_t (&out)[PER]) {
+    static_assert(NT % kSliceK == 0, "whole k-slices");
+    constexpr int NC = NT / kSliceK;
+    const int lane = threadIdx.x & 63, t0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * PER;
+    f32x4_t buf[2][PER][kSliceK];
+    wslice<NT, PER>(w.W, w.tr, t0, lane, 0, buf[0]);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        if (c + 1 < NC) wslice<NT, PER>(w.W, w.tr, t0, lane, c + 1, buf[(c + 1) & 1]);
+#pragma unroll
+        for (int k = 0; k < kSliceK; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int n = 0; n < PER; ++n) out[n] = mfma16(buf[c & 1][n][k][r], in[c * kSliceK + k][r], out[n]);
+    }
+}
+
+// first layer, fan-in Din <= 4 KF: k-step k = input columns 4 k .. 4 k + 3.  x[k]: this lane's B operand of k-step k, input column
+// 4 k + q of sample j (0 beyond Din).  W: the [md][Din] weights, in the small-tensor image or (width 256, KF = 8) in global memory.
+template <int PER, int KF>
 __device__ __forceinline__ void layer_first(const float* __restrict__ W, const float* __restrict__ bias, int Din, int t0, int lane,
-                                            float x0, float x1, f32x4_t (&out)[PER]) {
+                                            const float (&x)[KF], f32x4_t (&out)[PER]) {
     const int i = lane & 15, q = lane >> 4;
 #pragma unroll
     for (int n = 0; n < PER; ++n) {
         const float* row = W + (size_t)(16 * (t0 + n) + i) * Din;
-        const float a0 = q < Din ? row[q] : 0.f;
-        const float a1 = 4 + q < Din ? row[4 + q] : 0.f;
+        float av[KF];
+#pragma unroll
+        for (int k = 0; k < KF; ++k) av[k] = 4 * k + q < Din ? row[4 * k + q] : 0.f;
         out[n] = ld4(bias + 16 * (t0 + n) + 4 * q);
-        out[n] = mfma16(a0, x0, out[n]);
-        if (Din > 4) out[n] = mfma16(a1, x1, out[n]);
+#pragma unroll
+        for (int k = 0; k < KF; ++k)
+            if (k == 0 || Din > 4 * k) out[n] = mfma16(av[k], x[k], out[n]);
     }
 }
 
@@ -218,17 +288,26 @@ __device__ __forceinline__ void dw_blocks(const float* __restrict__ dz, const fl
             for (int b = 0; b < NT; ++b) acc[n][b] = mfma16(av[n], bv[b], acc[n][b]);
     }
 }
-// first-layer weight gradient: B = the tile's input rows [16 samples][16 columns, zero beyond Din] (xin)
-template <int PER>
+// first-layer weight gradient: B = the tile's input rows [16 samples][XW columns, zero beyond Din] (xin), XW / 16 column tiles
+template <int PER, int XW>
 __device__ __forceinline__ void dw_first(const float* __restrict__ dz, const float* __restrict__ xin, int t0, int lane,
-                                         f32x4_t (&acc)[PER]) {
+                                         f32x4_t (&acc)[PER][XW / 16]) {
+    constexpr int CT = XW / 16;
 #pragma unroll
-    for (int n = 0; n < PER; ++n) acc[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < PER; ++n)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) acc[n][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        const float bv = xin[(4 * s + (lane >> 4)) * 16 + (lane & 15)];
+        float bv[CT];
 #pragma unroll
-        for (int n = 0; n < PER; ++n) acc[n] = mfma16(chain_elem(dz, lane, t0 + n, s), bv, acc[n]);
+        for (int c = 0; c < CT; ++c) bv[c] = xin[(4 * s + (lane >> 4)) * XW + 16 * c + (lane & 15)];
+#pragma unroll
+        for (int n = 0; n < PER; ++n) {
+            const float av = chain_elem(dz, lane, t0 + n, s);
+#pragma unroll
+            for (int c = 0; c < CT; ++c) acc[n][c] = mfma16(av, bv[c], acc[n][c]);
+        }
     }
 }
 __device__ __forceinline__ void slab_put(float* __restrict__ p, f32x4_t v, bool accum) {
@@ -252,6 +331,49 @@ __device__ __forceinline__ void slab_blocks(float* __restrict__ seg, int t0, int
             for (int b = 0; b < NT; ++b) st4(p + (n * NT + b) * 256, acc[n][b] + ld4(p + (n * NT + b) * 256));
     }
 }
+// width 256: dw_blocks + slab_blocks in column slices of BC blocks (acc[PER][NT] alone would be 128 VGPRs); every block is the
+// same 4-k-step sum as in dw_blocks
+template <int NT, int PER, int BC>
+__device__ __forceinline__ void dw_slab_sliced(const float* __restrict__ dz, const float* __restrict__ h, float* __restrict__ seg, int t0,
+                                               int lane, bool accum) {
+    float* const p = seg + (t0 * NT * 64 + lane) * 4;
+#pragma unroll
+    for (int cb = 0; cb < NT; cb += BC) {
+        f32x4_t acc[PER][BC];
+#pragma unroll
+        for (int n = 0; n < PER; ++n)
+#pragma unroll
+            for (int b = 0; b < BC; ++b) acc[n][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            float av[PER], bv[BC];
+#pragma unroll
+            for (int n = 0; n < PER; ++n) av[n] = chain_elem(dz, lane, t0 + n, s);
+#pragma unroll
+            for (int b = 0; b < BC; ++b) bv[b] = chain_elem(h, lane, cb + b, s);
+#pragma unroll
+            for (int n = 0; n < PER; ++n)
+#pragma unroll
+                for (int b = 0; b < BC; ++b) acc[n][b] = mfma16(av[n], bv[b], acc[n][b]);
+        }
+#pragma unroll
+        for (int n = 0; n < PER; ++n)
+#pragma unroll
+            for (int b = 0; b < BC; ++b) slab_put(p + (n * NT + cb + b) * 256, acc[n][b], accum);
+    }
+}
+// weight gradient of an md x md layer into its slab segment: register-blocked (width <= 128, the round-4 code) or sliced (width 256)
+template <int NT, int PER, bool S>
+__device__ __forceinline__ void dw_slab(const float* __restrict__ dz, const float* __restrict__ h, float* __restrict__ seg, int t0, int lane,
+                                        bool accum) {
+    if constexpr (S) {
+        dw_slab_sliced<NT, PER, 8>(dz, h, seg, t0, lane, accum);
+    } else {
+        f32x4_t acc[PER][NT];
+        dw_blocks<NT, PER>(dz, h, t0, lane, acc);
+        slab_blocks<NT, PER>(seg, t0, lane, acc, accum);
+    }
+}
 // a vector gradient (bias, head weights) of this wave's features: v = per-sample terms, summed over the tile's samples
 template <int PER>
 __device__ __forceinline__ void vec_grad(float* __restrict__ seg, int t0, int lane, const f32x4_t (&v)[PER], bool accum) {
@@ -266,28 +388,34 @@ __device__ __forceinline__ void vec_grad(float* __restrict__ seg, int t0, int la
 // the moment a layer starts; from global memory each such read is an exposed L2 round trip on the workgroup's critical path (a dozen
 // per kernel).  They are copied into LDS once per workgroup, behind the minibatch gather: the flat tensors minus the big matrices,
 // in the same order (td3.hpp), so that a small-image offset is the flat offset minus the matrices in front of it.
+// Width 256 with the Stacking observations (KF = 8) leaves the first-layer weights in global memory: the four chain images take 72 KB
+// there and the three nets' first layers (~8 k floats each at D = 30) another 96 KB, over the 160 KB of a compute unit.  The small
+// image then starts at the first bias (W1 = 0, unused).
+__host__ __device__ constexpr bool td3_w1_global(int D, int md) { return md == 256 && td3_first_ksteps(D) == 8; }
 struct Td3SmallActor { int W1, b1, b2, b3, w4, b4, total; };
 struct Td3SmallCritic { int W1, b1, b2, q1w, q1b, q2w, q2b, total; };
 __host__ __device__ inline Td3SmallActor td3_small_actor(int D, int md) {
     const Td3ActorOff P = td3_actor_off(D, md);
-    const int mm = md * md;
-    return Td3SmallActor{P.W1, P.b1, P.b2 - mm, P.b3 - 2 * mm, P.w4 - 2 * mm, P.b4 - 2 * mm, P.total - 2 * mm};
+    const int mm = md * md, s = td3_w1_global(D, md) ? P.b1 : 0;
+    return Td3SmallActor{P.W1, P.b1 - s, P.b2 - mm - s, P.b3 - 2 * mm - s, P.w4 - 2 * mm - s, P.b4 - 2 * mm - s, P.total - 2 * mm - s};
 }
 __host__ __device__ inline Td3SmallCritic td3_small_critic(int D, int md) {
     const Td3CriticOff P = td3_critic_off(D, md);
-    const int mm = md * md;
-    return Td3SmallCritic{P.W1, P.b1, P.b2 - mm, P.q1w - mm, P.q1b - mm, P.q2w - mm, P.q2b - mm, P.total - mm};
+    const int mm = md * md, s = td3_w1_global(D, md) ? P.b1 : 0;
+    return Td3SmallCritic{P.W1, P.b1 - s, P.b2 - mm - s, P.q1w - mm - s, P.q1b - mm - s, P.q2w - mm - s, P.q2b - mm - s, P.total - mm - s};
 }
 
 struct Td3Lds {
     int buf[4], xin, red, small[3], total;
 };
 __host__ __device__ constexpr int td3_buf_floats(int NT) { return NT * kTP; }
+// the tile's input rows in LDS: [16 samples][XW columns], XW = 16 (KF = 2) or 32 (KF = 8)
+__host__ __device__ constexpr int td3_xin_width(int D) { return 16 * td3_first_tiles(D); }
 __host__ __device__ inline Td3Lds td3_lds(int NT, int D) {
     Td3Lds L{};
     int o = 0;
     for (int k = 0; k < 4; ++k) { L.buf[k] = o; o += td3_buf_floats(NT); }
-    L.xin = o; o += 16 * 16;
+    L.xin = o; o += 16 * td3_xin_width(D);
     L.red = o; o += 8 * kRedSlot;
     const int md = NT * 16, sa = td3_small_actor(D, md).total, sc = td3_small_critic(D, md).total;
     L.small[0] = o; o += sa;                 // the launch's actor (critic launch: the target actor)
@@ -306,6 +434,13 @@ __device__ __forceinline__ void small_store(float* __restrict__ dst, int n4, int
     if (tid < n4) st4(dst + 4 * tid, v);
 }
 
+// the generic staging of the Stacking / width-256 instantiations: floats [lo, hi) of a flat tensor to the small image (16-byte words,
+// every thread of the workgroup taking words tid, tid + NTH, ...)
+template <int NTH>
+__device__ __forceinline__ void small_copy(float* __restrict__ dst, const float* __restrict__ src, int lo, int hi, int tid) {
+    for (int u = tid; u < (hi - lo) / 4; u += NTH) st4(dst + 4 * u, ld4(src + lo + 4 * u));
+}
+
 // this lane's smoothing-noise draw for batch position pos
 __device__ __forceinline__ float td3_noise(const Td3Batch& b, long long trow, int pos) {
     if (b.noise) return b.noise[(size_t)trow * b.B + pos];
@@ -322,10 +457,15 @@ __device__ __forceinline__ float td3_noise(const Td3Batch& b, long long trow, in
 // DD: the state width as a compile-time constant (3: pH, 4: water tank Integrator), 0: read from the arguments.  With DD fixed every
 // offset of the parameter / slab / LDS layouts folds into an immediate; as run-time values they are ~100 live scalars that hipcc
 // spills through VGPR lanes (v_readlane / v_writelane) and re-derives with scalar arithmetic in every phase.
-template <int MD, int DD, int NW>
+template <int MD, int DD, int NW, int KF>
 __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
     constexpr int NT = MD / 16, PER = NT / NW;
     static_assert(PER >= 1 && PER * NW == NT, "the waves split a layer's output tiles evenly");
+    static_assert(DD == 0 || td3_first_ksteps(DD) == KF, "first-layer k-steps of the compiled-in state width");
+    constexpr bool S = MD == 256;                     // streamed md x md weights (Wts)
+    constexpr bool W1G = MD == 256 && KF == 8;        // first-layer weights read from global memory (td3_w1_global)
+    constexpr bool GEN = KF == 8 || MD == 256;        // small tensors staged by small_copy (the round-4 shapes: sv[] below)
+    constexpr int XW = KF == 2 ? 16 : 32, CT = XW / 16, XG = 4 * KF;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = DD ? DD : a.D, Dc = D + 1;
     const Td3Lds F = td3_lds(NT, D);
@@ -361,27 +501,32 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         const bool valid = pos < a.b.B;
         const int p = valid ? pos : a.b.B - 1;
         const long long row = a.b.idx[(size_t)trow * a.b.B + p], nrow = a.b.nxt[(size_t)trow * a.b.B + p];
-        f32x4_t wA[PER][NT], wB[PER][NT], in[NT];
-        load_w<NT, PER>(a.act + PA.W2, t0, lane, wA);   // the first md x md weights: in flight behind the gather's two round trips
+        Wts<NT, PER, S> wA, wB;
+        f32x4_t in[NT];
+        wload(wA, a.act + PA.W2, t0, lane);   // the first md x md weights: in flight behind the gather's two round trips
         // the nets' small tensors ride behind the index loads (first group only): seven 16-byte loads per thread, one round trip
         const bool stage = !accum;
         const int nA0 = (PA.W2 - PA.W1) / 4, nA1 = MD / 4, nA2 = (PA.total - PA.b3) / 4, nC0 = (PC.W2 - PC.W1) / 4, nC1 = (PC.total - PC.b2) / 4;
         f32x4_t sv[9];
-        if (stage) {
+        if (!GEN && stage) {
             sv[0] = small_load(a.act + PA.W1, nA0, tid); sv[1] = small_load(a.act + PA.b2, nA1, tid); sv[2] = small_load(a.act + PA.b3, nA2, tid);
             sv[3] = small_load(a.cri + PC.W1, nC0, tid); sv[4] = small_load(a.cri + PC.b2, nC1, tid);
             sv[5] = small_load(a.cri_target + PC.W1, nC0, tid); sv[6] = small_load(a.cri_target + PC.b2, nC1, tid);
             sv[7] = small_load(a.cri + PC.W1 + 1024, nC0 - 256, tid); sv[8] = small_load(a.cri_target + PC.W1 + 1024, nC0 - 256, tid);   // D = 7 only
         }
-        // first-layer B operands: input column q / 4 + q of sample j
+        // first-layer B operands: input column 4 k + q of sample j
         const float* srow = a.b.state + (size_t)row * D;
         const float* nsrow = a.b.state + (size_t)nrow * D;
-        const float s0 = q < D ? srow[q] : 0.f, s1 = 4 + q < D ? srow[4 + q] : 0.f;
-        const float n0 = q < D ? nsrow[q] : 0.f, n1 = 4 + q < D ? nsrow[4 + q] : 0.f;
+        float sx[KF], nx[KF];
+#pragma unroll
+        for (int k = 0; k < KF; ++k) {
+            sx[k] = 4 * k + q < D ? srow[4 * k + q] : 0.f;
+            nx[k] = 4 * k + q < D ? nsrow[4 * k + q] : 0.f;
+        }
         const float* orow = a.b.other + (size_t)row * 3;
         const float reward = orow[0], mask = orow[1], action = orow[2];
         const float eps = td3_noise(a.b, trow, p);
-        if (stage) {
+        if (!GEN && stage) {
             float* const w = lds + F.small[0];
             small_store(w + SA.W1, nA0, tid, sv[0]); small_store(w + SA.b2, nA1, tid, sv[1]); small_store(w + SA.b3, nA2, tid, sv[2]);
             float* const c = lds + F.small[1];
@@ -390,34 +535,50 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             small_store(t + SC.W1, nC0, tid, sv[5]); small_store(t + SC.b2, nC1, tid, sv[6]);
             small_store(c + SC.W1 + 1024, nC0 - 256, tid, sv[7]); small_store(t + SC.W1 + 1024, nC0 - 256, tid, sv[8]);
         }
+        if (GEN && stage) {
+            const int a0 = W1G ? PA.b1 : PA.W1, c0 = W1G ? PC.b1 : PC.W1;
+            small_copy<NW * 64>(lds + F.small[0], a.act, a0, PA.W2, tid);
+            small_copy<NW * 64>(lds + F.small[0] + SA.b2, a.act, PA.b2, PA.W3, tid);
+            small_copy<NW * 64>(lds + F.small[0] + SA.b3, a.act, PA.b3, PA.total, tid);
+            small_copy<NW * 64>(lds + F.small[1], a.cri, c0, PC.W2, tid);
+            small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
+            small_copy<NW * 64>(lds + F.small[2], a.cri_target, c0, PC.W2, tid);
+            small_copy<NW * 64>(lds + F.small[2] + SC.b2, a.cri_target, PC.b2, PC.total, tid);
+        }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
         TD3_MARK(1);   // gather + small tensors
         // the online critic's input [s, a, 0 ..]: column q / 4 + q of sample j (this lane's first-layer B operands)
-        const float xs0 = q < D ? s0 : (q == D ? action : 0.f), xs1 = 4 + q < D ? s1 : (4 + q == D ? action : 0.f);
-        if (wave == 0) {   // ... as rows [16 samples][16 columns] for its first-layer weight gradient, and for the actor launch
-            xin[j * 16 + q] = xs0; xin[j * 16 + 4 + q] = xs1; xin[j * 16 + 8 + q] = 0.f; xin[j * 16 + 12 + q] = 0.f;
-            if (valid) { a.xg[(size_t)pos * 8 + q] = xs0; a.xg[(size_t)pos * 8 + 4 + q] = xs1; }
+        float xs[KF];
+#pragma unroll
+        for (int k = 0; k < KF; ++k) xs[k] = 4 * k + q < D ? sx[k] : (4 * k + q == D ? action : 0.f);
+        if (wave == 0) {   // ... as rows [16 samples][XW columns] for its first-layer weight gradient, and for the actor launch
+#pragma unroll
+            for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? xs[k] : 0.f;
+            if (valid) {
+#pragma unroll
+                for (int k = 0; k < KF; ++k) a.xg[(size_t)pos * XG + 4 * k + q] = xs[k];
+            }
         }
 
         // ------------------------------------------------------------------ next_a = clamp(tanh(act_target(s')) + clamp(noise))
         {
             f32x4_t h[PER];
-            layer_first<PER>(at + SA.W1, at + SA.b1, D, t0, lane, n0, n1, h);
+            layer_first<PER, KF>(W1G ? a.act + PA.W1 : at + SA.W1, at + SA.b1, D, t0, lane, nx, h);
 #pragma unroll
             for (int n = 0; n < PER; ++n) chain_put(B0, lane, t0 + n, relu4(h[n]));
         }
-        load_w<NT, PER>(a.act + PA.W3, t0, lane, wB);
+        wload(wB, a.act + PA.W3, t0, lane);
         f32x4_t hb[PER];   // the next layer's accumulators, initialised with its bias in front of the barrier
         bias_get<PER>(at + SA.b2, t0, lane, hb);
         TD3_BARRIER();
         TD3_MARK(2);   // target actor layer 1
         chain_get<NT>(B0, lane, in);
         {
-            layer<NT, PER>(wA, in, hb);
+            wlayer(wA, in, hb);
 #pragma unroll
             for (int n = 0; n < PER; ++n) chain_put(B1, lane, t0 + n, relu4(hb[n]));
         }
-        load_w<NT, PER>(a.cri_target + PC.W2, t0, lane, wA);
+        wload(wA, a.cri_target + PC.W2, t0, lane);
         bias_get<PER>(at + SA.b3, t0, lane, hb);
         TD3_BARRIER();
         TD3_MARK(3);   // layer 2
@@ -425,7 +586,7 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         float next_a;
         {
             f32x4_t (&h)[PER] = hb;
-            layer<NT, PER>(wB, in, h);
+            wlayer(wB, in, h);
 #pragma unroll
             for (int n = 0; n < PER; ++n) h[n] = relu4(h[n]);
             red_put(red, 0, wave, lane, head_partial<PER>(at + SA.w4, t0, lane, h));
@@ -436,19 +597,20 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         }
         TD3_MARK(4);   // layer 3 + head: next_a
         // ------------------------------------------------------------------ q_label = r + mask * min(cri_target twin heads)(s', next_a)
-        load_w<NT, PER>(a.cri + PC.W2, t0, lane, wB);
+        wload(wB, a.cri + PC.W2, t0, lane);
         float label;
         {
-            const float x0 = q < D ? n0 : (q == D ? next_a : 0.f);
-            const float x1 = 4 + q < D ? n1 : (4 + q == D ? next_a : 0.f);
+            float xt[KF];
+#pragma unroll
+            for (int k = 0; k < KF; ++k) xt[k] = 4 * k + q < D ? nx[k] : (4 * k + q == D ? next_a : 0.f);
             f32x4_t h[PER];
-            layer_first<PER>(ct + SC.W1, ct + SC.b1, Dc, t0, lane, x0, x1, h);
+            layer_first<PER, KF>(W1G ? a.cri_target + PC.W1 : ct + SC.W1, ct + SC.b1, Dc, t0, lane, xt, h);
 #pragma unroll
             for (int n = 0; n < PER; ++n) chain_put(B0, lane, t0 + n, relu4(h[n]));
             bias_get<PER>(ct + SC.b2, t0, lane, h);
             TD3_BARRIER();
             chain_get<NT>(B0, lane, in);
-            layer<NT, PER>(wA, in, h);
+            wlayer(wA, in, h);
 #pragma unroll
             for (int n = 0; n < PER; ++n) h[n] = relu4(h[n]);
             red_put(red, 1, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, h));
@@ -461,15 +623,15 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         // ------------------------------------------------------------------ online twin critic on (s, a): forward
         f32x4_t h1[PER], h2[PER];
         {
-            layer_first<PER>(cr + SC.W1, cr + SC.b1, Dc, t0, lane, xs0, xs1, h1);
+            layer_first<PER, KF>(W1G ? a.cri + PC.W1 : cr + SC.W1, cr + SC.b1, Dc, t0, lane, xs, h1);
 #pragma unroll
             for (int n = 0; n < PER; ++n) { h1[n] = relu4(h1[n]); chain_put(B1, lane, t0 + n, h1[n]); }
         }
-        load_wt<NT, PER>(a.cri + PC.W2, t0, lane, wA);   // for dH1 = W2^T dZ2
+        wload_t(wA, a.cri + PC.W2, t0, lane);   // for dH1 = W2^T dZ2
         bias_get<PER>(cr + SC.b2, t0, lane, h2);
         TD3_BARRIER();
         chain_get<NT>(B1, lane, in);
-        layer<NT, PER>(wB, in, h2);
+        wlayer(wB, in, h2);
 #pragma unroll
         for (int n = 0; n < PER; ++n) h2[n] = relu4(h2[n]);
         red_put(red, 3, wave, lane, head_partial<PER>(cr + SC.q1w, t0, lane, h2));
@@ -513,18 +675,14 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         }
         TD3_BARRIER();   // dZ2 published
         TD3_MARK(7);   // loss, head gradients, dZ2
-        {   // net_sa.2 weight gradient
-            f32x4_t acc[PER][NT];
-            dw_blocks<NT, PER>(B2, B1, t0, lane, acc);
-            slab_blocks<NT, PER>(sl + SL.seg[2].slab_off, t0, lane, acc, accum);
-        }
+        dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[2].slab_off, t0, lane, accum);   // net_sa.2 weight gradient
         TD3_NO_HOIST();
         TD3_MARK(8);   // dW2
         chain_get<NT>(B2, lane, in);
         {
             f32x4_t d1[PER];
             zero4<PER>(d1);
-            layer<NT, PER>(wA, in, d1);
+            wlayer(wA, in, d1);
 #pragma unroll
             for (int n = 0; n < PER; ++n) { d1[n] = gate4(d1[n], h1[n]); chain_put(B0, lane, t0 + n, d1[n]); }
             vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d1, accum);   // net_sa.0 bias
@@ -532,11 +690,13 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         TD3_BARRIER();   // dZ1 published
         TD3_MARK(9);   // dH1, dZ1
         {
-            f32x4_t acc[PER];
-            dw_first<PER>(B0, xin, t0, lane, acc);
+            f32x4_t acc[PER][CT];
+            dw_first<PER, XW>(B0, xin, t0, lane, acc);
             float* seg = sl + SL.seg[0].slab_off;
 #pragma unroll
-            for (int n = 0; n < PER; ++n) slab_put(seg + ((t0 + n) * 64 + lane) * 4, acc[n], accum);
+            for (int n = 0; n < PER; ++n)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
         }
     }
     TD3_MARK(10);   // dW1
@@ -549,10 +709,15 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
 
 // ======================================================================================================== actor gradients
 // obj_actor = -mean(cri_target.q1(s, tanh(act(s))))  (agent.py:323-324), differentiated down to the actor's parameters
-template <int MD, int DD, int NW>
+template <int MD, int DD, int NW, int KF>
 __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
     constexpr int NT = MD / 16, PER = NT / NW;
     static_assert(PER >= 1 && PER * NW == NT, "the waves split a layer's output tiles evenly");
+    static_assert(DD == 0 || td3_first_ksteps(DD) == KF, "first-layer k-steps of the compiled-in state width");
+    constexpr bool S = MD == 256;                     // streamed md x md weights (Wts)
+    constexpr bool W1G = MD == 256 && KF == 8;        // first-layer weights read from global memory (td3_w1_global)
+    constexpr bool GEN = KF == 8 || MD == 256;        // small tensors staged by small_copy (the round-4 shapes: sv[] below)
+    constexpr int XW = KF == 2 ? 16 : 32, CT = XW / 16, XG = 4 * KF;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = DD ? DD : a.D, Dc = D + 1;
     const Td3Lds F = td3_lds(NT, D);
@@ -570,6 +735,7 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
     const Td3SmallCritic SC = td3_small_critic(D, MD);
     const float* const ac = lds + F.small[0];   // online actor, small tensors
     const float* const ct = lds + F.small[1];   // target critic
+    const float* const ctW1 = W1G ? a.cri + PC.W1 : ct + SC.W1;   // its first layer
     const Td3SlabLayout SL = td3_actor_slab(D, MD);
     const float invB = 1.0f / (float)a.b.B;
     float* const sl = a.slab + (size_t)blockIdx.x * a.stride;
@@ -586,48 +752,60 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         const int pos = group * kTd3Tile + j;
         const bool valid = pos < a.b.B;
         const int p = valid ? pos : a.b.B - 1;
-        f32x4_t wA[PER][NT], wB[PER][NT], in[NT];
-        load_w<NT, PER>(a.act + PA.W2, t0, lane, wA);
+        Wts<NT, PER, S> wA, wB;
+        f32x4_t in[NT];
+        wload(wA, a.act + PA.W2, t0, lane);
         // the minibatch's state rows as the critic launch of this step gathered them (one round trip instead of index -> row)
-        const float s0 = q < D ? a.xg[(size_t)p * 8 + q] : 0.f, s1 = 4 + q < D ? a.xg[(size_t)p * 8 + 4 + q] : 0.f;
+        float sx[KF];
+#pragma unroll
+        for (int k = 0; k < KF; ++k) sx[k] = 4 * k + q < D ? a.xg[(size_t)p * XG + 4 * k + q] : 0.f;
         const bool stage = !accum;   // the small tensors ride along (first group only)
         const int nA0 = (PA.W2 - PA.W1) / 4, nA1 = MD / 4, nA2 = (PA.total - PA.b3) / 4, nC0 = (PC.W2 - PC.W1) / 4, nC1 = (PC.total - PC.b2) / 4;
         f32x4_t sv[6];
-        if (stage) {
+        if (!GEN && stage) {
             sv[0] = small_load(a.act + PA.W1, nA0, tid); sv[1] = small_load(a.act + PA.b2, nA1, tid); sv[2] = small_load(a.act + PA.b3, nA2, tid);
             sv[3] = small_load(a.cri + PC.W1, nC0, tid); sv[4] = small_load(a.cri + PC.b2, nC1, tid);
             sv[5] = small_load(a.cri + PC.W1 + 1024, nC0 - 256, tid);   // D = 7 only
         }
-        if (stage) {
+        if (!GEN && stage) {
             float* const w = lds + F.small[0];
             small_store(w + SA.W1, nA0, tid, sv[0]); small_store(w + SA.b2, nA1, tid, sv[1]); small_store(w + SA.b3, nA2, tid, sv[2]);
             float* const c = lds + F.small[1];
             small_store(c + SC.W1, nC0, tid, sv[3]); small_store(c + SC.b2, nC1, tid, sv[4]);
             small_store(c + SC.W1 + 1024, nC0 - 256, tid, sv[5]);
         }
+        if (GEN && stage) {
+            const int a0 = W1G ? PA.b1 : PA.W1, c0 = W1G ? PC.b1 : PC.W1;
+            small_copy<NW * 64>(lds + F.small[0], a.act, a0, PA.W2, tid);
+            small_copy<NW * 64>(lds + F.small[0] + SA.b2, a.act, PA.b2, PA.W3, tid);
+            small_copy<NW * 64>(lds + F.small[0] + SA.b3, a.act, PA.b3, PA.total, tid);
+            small_copy<NW * 64>(lds + F.small[1], a.cri, c0, PC.W2, tid);
+            small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
+        }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
         TD3_MARK(1);
-        if (wave == 0) {   // the actor's input rows [16 samples][16 columns, zero beyond D] for its first-layer weight gradient
-            xin[j * 16 + q] = s0; xin[j * 16 + 4 + q] = s1; xin[j * 16 + 8 + q] = 0.f; xin[j * 16 + 12 + q] = 0.f;
+        if (wave == 0) {   // the actor's input rows [16 samples][XW columns, zero beyond D] for its first-layer weight gradient
+#pragma unroll
+            for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? sx[k] : 0.f;
         }
         f32x4_t a1[PER], a2[PER], a3[PER], c1[PER], c2[PER];
 
         // ------------------------------------------------------------------ action = tanh(act(s))
-        layer_first<PER>(ac + SA.W1, ac + SA.b1, D, t0, lane, s0, s1, a1);
+        layer_first<PER, KF>(W1G ? a.act + PA.W1 : ac + SA.W1, ac + SA.b1, D, t0, lane, sx, a1);
 #pragma unroll
         for (int n = 0; n < PER; ++n) { a1[n] = relu4(a1[n]); chain_put(B0, lane, t0 + n, a1[n]); }
-        load_w<NT, PER>(a.act + PA.W3, t0, lane, wB);
+        wload(wB, a.act + PA.W3, t0, lane);
         bias_get<PER>(ac + SA.b2, t0, lane, a2);   // a layer's accumulators start as its bias, read in front of the barrier
         TD3_BARRIER();
         chain_get<NT>(B0, lane, in);
-        layer<NT, PER>(wA, in, a2);
+        wlayer(wA, in, a2);
 #pragma unroll
         for (int n = 0; n < PER; ++n) { a2[n] = relu4(a2[n]); chain_put(B1, lane, t0 + n, a2[n]); }
-        load_w<NT, PER>(a.cri + PC.W2, t0, lane, wA);
+        wload(wA, a.cri + PC.W2, t0, lane);
         bias_get<PER>(ac + SA.b3, t0, lane, a3);
         TD3_BARRIER();
         chain_get<NT>(B1, lane, in);
-        layer<NT, PER>(wB, in, a3);
+        wlayer(wB, in, a3);
 #pragma unroll
         for (int n = 0; n < PER; ++n) a3[n] = relu4(a3[n]);
         red_put(red, 0, wave, lane, head_partial<PER>(ac + SA.w4, t0, lane, a3));
@@ -636,17 +814,18 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         TD3_MARK(2);   // actor forward
         // ------------------------------------------------------------------ q1 = cri_target.q1(s, action)
         {
-            const float x0 = q < D ? s0 : (q == D ? act : 0.f);
-            const float x1 = 4 + q < D ? s1 : (4 + q == D ? act : 0.f);
-            layer_first<PER>(ct + SC.W1, ct + SC.b1, Dc, t0, lane, x0, x1, c1);
+            float xt[KF];
+#pragma unroll
+            for (int k = 0; k < KF; ++k) xt[k] = 4 * k + q < D ? sx[k] : (4 * k + q == D ? act : 0.f);
+            layer_first<PER, KF>(ctW1, ct + SC.b1, Dc, t0, lane, xt, c1);
 #pragma unroll
             for (int n = 0; n < PER; ++n) { c1[n] = relu4(c1[n]); chain_put(B2, lane, t0 + n, c1[n]); }
         }
-        load_wt<NT, PER>(a.cri + PC.W2, t0, lane, wB);   // dC1 = W2^T dZc2
+        wload_t(wB, a.cri + PC.W2, t0, lane);   // dC1 = W2^T dZc2
         bias_get<PER>(ct + SC.b2, t0, lane, c2);
         TD3_BARRIER();
         chain_get<NT>(B2, lane, in);
-        layer<NT, PER>(wA, in, c2);
+        wlayer(wA, in, c2);
 #pragma unroll
         for (int n = 0; n < PER; ++n) c2[n] = relu4(c2[n]);
         red_put(red, 1, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, c2));   // (the value itself only feeds the logged objective)
@@ -657,7 +836,7 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
             const f32x4_t wq = ld4(ct + SC.q1w + 16 * (t0 + n) + 4 * q);
             chain_put(B3, lane, t0 + n, gate4(wq * g, c2[n]));
         }
-        load_wt<NT, PER>(a.act + PA.W3, t0, lane, wA);   // dA2 = W3^T dZ3
+        wload_t(wA, a.act + PA.W3, t0, lane);   // dA2 = W3^T dZ3
         TD3_BARRIER();
         TD3_MARK(3);   // target critic forward, dZc2
         if (valid && wave == 0 && q == 0) q_acc += red_get<NW>(red, 1, lane) + ct[SC.q1b];
@@ -666,13 +845,13 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         {
             f32x4_t d[PER];
             zero4<PER>(d);
-            layer<NT, PER>(wB, in, d);
+            wlayer(wB, in, d);
             float pa = 0.f;   // d obj / d action = sum_f W1[f][D] dZc1[f]
 #pragma unroll
             for (int n = 0; n < PER; ++n) {
                 d[n] = gate4(d[n], c1[n]);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) pa = fmaf(d[n][r], ct[SC.W1 + (16 * (t0 + n) + 4 * q + r) * Dc + D], pa);
+                for (int r = 0; r < 4; ++r) pa = fmaf(d[n][r], ctW1[(16 * (t0 + n) + 4 * q + r) * Dc + D], pa);
             }
             pa += __shfl_xor(pa, 16);
             pa += __shfl_xor(pa, 32);
@@ -701,37 +880,29 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
                 }
             }
         }
-        load_wt<NT, PER>(a.act + PA.W2, t0, lane, wB);   // dA1 = W2^T dZ2
+        wload_t(wB, a.act + PA.W2, t0, lane);   // dA1 = W2^T dZ2
         TD3_BARRIER();   // dZ3 published
         TD3_MARK(5);
-        {
-            f32x4_t acc[PER][NT];
-            dw_blocks<NT, PER>(B2, B1, t0, lane, acc);   // net.4: dZ3^T A2
-            slab_blocks<NT, PER>(sl + SL.seg[4].slab_off, t0, lane, acc, accum);
-        }
+        dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[4].slab_off, t0, lane, accum);   // net.4: dZ3^T A2
         TD3_NO_HOIST();
         chain_get<NT>(B2, lane, in);
         {
             f32x4_t d[PER];
             zero4<PER>(d);
-            layer<NT, PER>(wA, in, d);
+            wlayer(wA, in, d);
 #pragma unroll
             for (int n = 0; n < PER; ++n) { d[n] = gate4(d[n], a2[n]); chain_put(B3, lane, t0 + n, d[n]); }
             vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, d, accum);    // net.2 bias
         }
         TD3_BARRIER();   // dZ2 published
         TD3_MARK(6);   // dW3, dA2
-        {
-            f32x4_t acc[PER][NT];
-            dw_blocks<NT, PER>(B3, B0, t0, lane, acc);   // net.2: dZ2^T A1
-            slab_blocks<NT, PER>(sl + SL.seg[2].slab_off, t0, lane, acc, accum);
-        }
+        dw_slab<NT, PER, S>(B3, B0, sl + SL.seg[2].slab_off, t0, lane, accum);   // net.2: dZ2^T A1
         TD3_NO_HOIST();
         chain_get<NT>(B3, lane, in);
         {
             f32x4_t d[PER];
             zero4<PER>(d);
-            layer<NT, PER>(wB, in, d);
+            wlayer(wB, in, d);
 #pragma unroll
             for (int n = 0; n < PER; ++n) { d[n] = gate4(d[n], a1[n]); chain_put(B1, lane, t0 + n, d[n]); }
             vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d, accum);    // net.0 bias
@@ -739,11 +910,13 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         TD3_BARRIER();   // dZ1 published
         TD3_MARK(7);   // dW2, dA1
         {
-            f32x4_t acc[PER];
-            dw_first<PER>(B1, xin, t0, lane, acc);
+            f32x4_t acc[PER][CT];
+            dw_first<PER, XW>(B1, xin, t0, lane, acc);
             float* seg = sl + SL.seg[0].slab_off;
 #pragma unroll
-            for (int n = 0; n < PER; ++n) slab_put(seg + ((t0 + n) * 64 + lane) * 4, acc[n], accum);
+            for (int n = 0; n < PER; ++n)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
         }
     }
     TD3_MARK(8);   // dW1
@@ -899,43 +1072,53 @@ int td3_grid(int B) {
 }
 int64_t td3_workspace_floats(int D, int md, int B) {
     const int64_t g = td3_grid(B);
-    return g * (td3_actor_slab(D, md).stride + td3_critic_slab(D, md).stride) + (int64_t)2 * B * 8;   // slabs + the gathered rows [2][B][8] (by row parity)
+    // slabs + the gathered rows [2][B][td3_xg_stride(D)] (by row parity)
+    return g * (td3_actor_slab(D, md).stride + td3_critic_slab(D, md).stride) + (int64_t)2 * B * td3_xg_stride(D);
 }
-bool td3_supported(int D, int A, int md) { return A == 1 && D >= 1 && D <= kTd3MaxD && (md == 64 || md == 128); }
+bool td3_supported(int D, int A, int md) { return A == 1 && D >= 1 && D <= kTd3MaxD && (md == 64 || md == 128 || md == 256); }
 
 // Waves per workgroup of the gradient kernels at width 128: 4 = one wave per SIMD owning two of a layer's eight output tiles,
 // 8 = two waves per SIMD owning one tile each (the non-MFMA instructions of one wave issue behind the other's MFMAs).
-// Width 64 has four output tiles: four waves.  PIME_TD3_WAVES=4|8 is the A/B knob.
+// Width 64 has four output tiles: four waves; width 256 sixteen: eight waves owning two each.  PIME_TD3_WAVES=4|8 is the A/B knob
+// of the round-4 shapes (width 128, D <= 7).
 static int td3_waves(int md) {
     static const int w = [] {
         const char* e = std::getenv("PIME_TD3_WAVES");
         const int v = e ? std::atoi(e) : kTd3DefaultWaves;
         return v == 8 ? 8 : 4;
     }();
-    return md == 128 ? w : 4;
+    return md == 256 ? 8 : md == 128 ? w : 4;
 }
-template <int MD, int DD, int NW>
+template <int MD, int DD, int NW, int KF>
 static int launch_grad_w(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
     const size_t lds_bytes = sizeof(float) * (size_t)td3_lds(MD / 16, a.D).total;
-    if (critic) hipLaunchKernelGGL((td3_critic_kernel<MD, DD, NW>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
-    else hipLaunchKernelGGL((td3_actor_kernel<MD, DD, NW>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
+    if (critic) hipLaunchKernelGGL((td3_critic_kernel<MD, DD, NW, KF>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
+    else hipLaunchKernelGGL((td3_actor_kernel<MD, DD, NW, KF>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
-template <int MD, int DD>
+template <int MD, int DD, int KF>
 static int launch_grad_d(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
-    if constexpr (MD == 128) {
-        if (td3_waves(MD) == 8) return launch_grad_w<MD, DD, 8>(critic, a, grid, s);
+    if constexpr (MD == 256 || (MD == 128 && KF == 8)) {
+        return launch_grad_w<MD, DD, 8, KF>(critic, a, grid, s);
+    } else if constexpr (MD == 128) {
+        if (td3_waves(MD) == 8) return launch_grad_w<MD, DD, 8, KF>(critic, a, grid, s);
+        return launch_grad_w<MD, DD, 4, KF>(critic, a, grid, s);
+    } else {
+        return launch_grad_w<MD, DD, 4, KF>(critic, a, grid, s);
     }
-    return launch_grad_w<MD, DD, 4>(critic, a, grid, s);
 }
 template <int MD>
 static int launch_grad(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
-    if (a.D == 3) return launch_grad_d<MD, 3>(critic, a, grid, s);   // pH observation
-    if (a.D == 4) return launch_grad_d<MD, 4>(critic, a, grid, s);   // water-tank Integrator observation
-    return launch_grad_d<MD, 0>(critic, a, grid, s);
+    if (a.D == 3) return launch_grad_d<MD, 3, 2>(critic, a, grid, s);     // pH observation
+    if (a.D == 4) return launch_grad_d<MD, 4, 2>(critic, a, grid, s);     // water-tank Integrator observation
+    if (a.D == 12) return launch_grad_d<MD, 12, 8>(critic, a, grid, s);   // water-tank Stacking4
+    if (a.D == 30) return launch_grad_d<MD, 30, 8>(critic, a, grid, s);   // water-tank Stacking10
+    if (td3_first_ksteps(a.D) == 2) return launch_grad_d<MD, 0, 2>(critic, a, grid, s);
+    return launch_grad_d<MD, 0, 8>(critic, a, grid, s);
 }
 int launch_td3_grad(bool critic, int md, const Td3GradArgs& a, int grid, hipStream_t s) {
+    if (md == 256) return launch_grad<256>(critic, a, grid, s);
     if (md == 128) return launch_grad<128>(critic, a, grid, s);
     if (md == 64) return launch_grad<64>(critic, a, grid, s);
     set_error("no fused TD3 instantiation for width %d", md);
