@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 19
+#define PIME_ABI_VERSION 20
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -438,12 +438,9 @@ int pime_td3_param_offsets(int32_t which, int32_t D, int32_t md, int32_t* offset
 int64_t pime_td3_workspace_floats(int32_t D, int32_t md, int32_t B);
 /* soft_mode: 0 no soft target update, 1 soft update, 2 soft update when row % update_freq == 0 (the reference's delayed update).
  * phases: bit 0 = critic gradients, bit 1 = critic apply (slab reduction, Adam, soft update), bit 2 = actor gradients, bit 3 = actor
- *         apply; 15 = the whole step on one stream.  The four launches may also be issued on TWO streams, the data dependencies
- *         being: actor gradients(row) read the state rows the critic gradients(row) gathered (kept per row parity in the workspace)
- *         and, on a soft row, the critic target the critic apply(row) wrote; critic gradients(row + 1) read the critic the critic
- *         apply(row) wrote and, behind a soft row, the actor target the actor apply(row) wrote.  So on rows without a soft update
- *         the critic apply may run beside the actor gradients, and the actor apply beside the next row's critic gradients
- *         (AgentTD3._update_fused does that: parallel branches of the update's HIP graph).
+ *         apply; 15 = the whole step.  The launches of consecutive calls sharing a workspace run in stream order: the actor gradients
+ *         of a row read the state rows that the critic gradients of the same row gathered into the workspace, and the critic
+ *         gradients of the next row overwrite them.
  *         Data-parallel callers split the two apply launches around their all-reduce (mean) of the net's `grad` tensor: 16 = critic slab
  *         reduction ONLY (grad = this rank's gradient, loss words), 32 = critic Adam (+ soft update) FROM `grad` (no slabs read); 64 / 128
  *         the same for the actor.  One optimizer step on G ranks: phases 1|16, all-reduce critic grad, phases 32|4|64, all-reduce actor

@@ -1024,11 +1024,10 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
     PIME_REQUIRE(actor->D == critic->D, "actor and critic state_dim differ");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DwArgs dw{};
-    static const bool force_split = std::getenv("PIME_PPO_SPLIT") != nullptr;  // A/B knob: the net + dW kernel pipeline
     // Which kernel serves which net (index 0 = critic, 1 = actor):
     //   F16   the streamed 16-tile family (mlp16.hip): width 256, and 64 / 128 on observations too wide for FUSED; slabs
     //   FUSED the LDS-resident kernel (ppo_fused.hip): 64 / 128 while its LDS map fits; slabs
-    //   SPLIT the net + dW pipeline (ppo_train.hip, float atomics): a modular actor on a wide observation, or PIME_PPO_SPLIT
+    //   SPLIT the net + dW pipeline (ppo_train.hip, float atomics): a modular actor on a wide observation
     // Slab nets are finished by ppo_grad_reduce_kernel (which also derives the critic scale); a split critic by critic_scale_kernel.
     enum { F16, FUSED, SPLIT };
     const pime_ppo_net* nets[2] = {critic, actor};
@@ -1036,7 +1035,7 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
     for (int k = 0; k < 2; ++k) {
         const pime_ppo_net* n = nets[k];
         if (family16_grad(n->kind, n->md, n->D, n->Di)) mode[k] = F16;
-        else mode[k] = (force_split || !fused_fits(n->kind, n->D, n->Di, n->md)) ? SPLIT : FUSED;
+        else mode[k] = fused_fits(n->kind, n->D, n->Di, n->md) ? FUSED : SPLIT;
     }
     const bool any_split = mode[0] == SPLIT || mode[1] == SPLIT, any_slab = mode[0] != SPLIT || mode[1] != SPLIT;
     PIME_REQUIRE(!(b->dp_moments && mode[0] == SPLIT), "pime_ppo_minibatch_grad: dp_moments needs the critic on a slab kernel (it takes the split pipeline here)");
@@ -1052,12 +1051,6 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
                           {{const_cast<float*>(critic->img_fwd), const_cast<float*>(critic->img_bwd)},
                            {const_cast<float*>(actor->img_fwd), const_cast<float*>(actor->img_bwd)}}};
     }
-    static const bool tracing = std::getenv("PIME_FUSED_TRACE") != nullptr;  // tuning aid: phase marks of one workgroup
-    static long long* trace_dev = nullptr;
-    if (tracing && !trace_dev) {
-        PIME_HIP_TRY(hipMalloc(&trace_dev, (2 * 64 + 2 * 1024) * sizeof(long long)));   // marks of one workgroup + [net][workgroup][start, end]
-    }
-    if (tracing) PIME_HIP_TRY(hipMemsetAsync(trace_dev, 0, (2 * 64 + 2 * 1024) * sizeof(long long), s));
     if (mode[0] == SPLIT) PIME_HIP_TRY(hipMemsetAsync(moments, 0, 2 * sizeof(double), s));  // atomics accumulate into it
     if (b->flags & PIME_PPO_OVERWRITE_GRADS) {   // the atomics of the split pipeline need zeroed targets
         for (int k = 0; k < 2; ++k) {
@@ -1071,10 +1064,8 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
         }
     }
     PpoArgs slab_args[2];
-    // both nets on the LDS-resident fused kernel and of one width: ONE launch serves them (ppo_fused_dual_kernel); PIME_PPO_DUAL=0
-    // keeps one launch per net (A/B, and the per-net phase trace)
-    static const bool dual_off = std::getenv("PIME_PPO_DUAL") != nullptr && std::atoi(std::getenv("PIME_PPO_DUAL")) == 0;
-    const bool dual = mode[0] == FUSED && mode[1] == FUSED && critic->md == actor->md && !dual_off && !tracing;
+    // both nets on the LDS-resident fused kernel and of one width: ONE launch serves them (ppo_fused_dual_kernel)
+    const bool dual = mode[0] == FUSED && mode[1] == FUSED && critic->md == actor->md;
     for (int k = 0; k < 2; ++k) {
         const pime_ppo_net* n = nets[k];
         PpoArgs a{};
@@ -1088,12 +1079,8 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
         a.xg = a.dout + ntiles * 32;
         a.loss_sums = loss_sums; a.g_std = n->g_a_std_log;
         a.stagger = 3;  // measured best of 0..4 on MI355X (532 -> 522 us per minibatch gradient)
-        if (const char* e = std::getenv("PIME_STAGGER")) a.stagger = std::atoi(e);  // tuning knob
         const int np = n->kind == PIME_MLP_MODULAR_ACTOR ? 12 : 8;
         for (int i = 0; i < np; ++i) a.grad[i] = n->grads[i];
-        a.trace = (tracing && mode[k] != SPLIT) ? trace_dev + 64 * k : nullptr;
-        a.trace_wg = tracing ? std::atoi(std::getenv("PIME_FUSED_TRACE")) : 0;
-        a.trace_span = a.trace ? trace_dev + 128 + 1024 * k : nullptr;
         int psize[12];
         if (mode[k] == F16) {
             a.slab = n->workspace;
@@ -1116,39 +1103,7 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
     }
     if (any_split) {
         dw.tiles_per_wg = 16;
-        if (const char* e = std::getenv("PIME_DW_DEBUG")) dw.debug_skip = std::atoi(e);  // timing ablations only
         if (int rc = launch_dw(dw, b->B, s)) return rc;
-    }
-    if (tracing && any_slab) {
-        static long long t[128 + 2048];
-        PIME_HIP_TRY(hipStreamSynchronize(s));
-        PIME_HIP_TRY(hipMemcpy(t, trace_dev, sizeof(t), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 2; ++k) {
-            std::fprintf(stderr, "[pime trace] %s:", k ? "actor " : "critic");
-            for (int i = 1; i < 32; ++i)
-                if (t[64 * k + i]) std::fprintf(stderr, " m%d=%.1f", i, (double)(t[64 * k + i] - t[64 * k]) * 0.01);
-            for (int i = 32; i < 40; ++i)
-                if (t[64 * k + i]) std::fprintf(stderr, " c%d=%lld", i - 32, t[64 * k + i]);
-            for (int i = 40; i < 56; ++i)   // sub-marks of one job (16-tile family: the passes of the first sliced weight gradient)
-                if (t[64 * k + i]) std::fprintf(stderr, " p%d=%.1f", i - 40, (double)(t[64 * k + i] - t[64 * k]) * 0.01);
-            std::fprintf(stderr, "\n");
-            // every workgroup's start / end (100 MHz wall clock): launch skew, the slowest workgroup, the whole span
-            const long long* sp = t + 128 + 1024 * k;
-            long long s0 = 0, s1 = 0, e0 = 0, e1 = 0, dmin = 0, dmax = 0;
-            int n = 0;
-            for (int w = 0; w < 512; ++w) {
-                if (!sp[2 * w] || !sp[2 * w + 1]) continue;
-                const long long st = sp[2 * w], en = sp[2 * w + 1], d = en - st;
-                if (!n) { s0 = s1 = st; e0 = e1 = en; dmin = dmax = d; }
-                s0 = st < s0 ? st : s0; s1 = st > s1 ? st : s1; e0 = en < e0 ? en : e0; e1 = en > e1 ? en : e1;
-                dmin = d < dmin ? d : dmin; dmax = d > dmax ? d : dmax;
-                ++n;
-            }
-            if (n)
-                std::fprintf(stderr, "[pime trace] %s: %d workgroups: starts spread %.1f us, per-workgroup time %.1f .. %.1f us, "
-                             "first start -> last end %.1f us\n", k ? "actor " : "critic", n, (s1 - s0) * 0.01, dmin * 0.01, dmax * 0.01,
-                             (e1 - s0) * 0.01);
-        }
     }
     if (any_slab) {
         const int nslabs[2] = {mode[0] == F16 ? grid16(critic->kind, b->B, critic->md, critic->D, critic->Di) : fused_grid(b->B),
@@ -1239,9 +1194,8 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
     const Td3SlabLayout LA = td3_actor_slab(D, md), LC = td3_critic_slab(D, md);
     float* const slab_c = workspace;
     float* const slab_a = workspace + (size_t)grid * LC.stride;
-    // [2][B][td3_xg_stride(D)] gathered rows, by row parity: written by the critic launch of a row, read by its actor launch -- which may still run
-    // while the critic launch of the NEXT row (other parity) gathers (the caller's two-stream schedule, see include/pime_hip.h)
-    float* const xg = slab_a + (size_t)grid * LA.stride + (size_t)(b->row & 1) * b->B * td3_xg_stride(D);
+    // [B][td3_xg_stride(D)] gathered rows: written by the critic launch of a row, read by its actor launch
+    float* const xg = slab_a + (size_t)grid * LA.stride;
     Td3Batch tb{b->state, b->other, b->idx, b->nxt, b->noise, (long long)b->row, b->epoch, b->B, b->noise_seed, b->noise_epoch, b->policy_noise, b->noise_clip};
     auto apply = [&](const pime_td3_net* n, const Td3SlabLayout& L, const float* slab, int slot, int mode) {
         Td3ApplyArgs a{};
@@ -1252,12 +1206,8 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
         a.loss = loss; a.loss_slot = slot; a.inv_B = 1.0f / (float)b->B;
         return launch_td3_apply(a, s);
     };
-    static const bool tracing = std::getenv("PIME_TD3_TRACE") != nullptr;   // tuning aid: phase marks of workgroup 0 (synchronises)
-    static long long* trace_dev = nullptr;
-    if (tracing && !trace_dev) PIME_HIP_TRY(hipMalloc(&trace_dev, 64 * sizeof(long long)));
-    if (tracing) PIME_HIP_TRY(hipMemsetAsync(trace_dev, 0, 64 * sizeof(long long), s));
     if (phases & 1) {
-        Td3GradArgs g{tb, D, actor->target, critic->param, critic->target, slab_c, xg, LC.stride, ngroups, tracing ? trace_dev : nullptr};
+        Td3GradArgs g{tb, D, actor->target, critic->param, critic->target, slab_c, xg, LC.stride, ngroups};
         if (int rc = launch_td3_grad(true, md, g, grid, s)) return rc;
     }
     if (phases & (2 | 16))
@@ -1265,25 +1215,13 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
     if (phases & 32)
         if (int rc = apply(critic, LC, slab_c, 1, 2)) return rc;
     if (phases & 4) {
-        Td3GradArgs g{tb, D, actor->param, critic->target, nullptr, slab_a, xg, LA.stride, ngroups, tracing ? trace_dev + 32 : nullptr};
+        Td3GradArgs g{tb, D, actor->param, critic->target, nullptr, slab_a, xg, LA.stride, ngroups};
         if (int rc = launch_td3_grad(false, md, g, grid, s)) return rc;
     }
     if (phases & (8 | 64))
         if (int rc = apply(actor, LA, slab_a, 0, (phases & 64) ? 1 : 0)) return rc;
     if (phases & 128)
         if (int rc = apply(actor, LA, slab_a, 0, 2)) return rc;
-    if (tracing) {
-        long long t[64];
-        PIME_HIP_TRY(hipStreamSynchronize(s));
-        PIME_HIP_TRY(hipMemcpy(t, trace_dev, sizeof(t), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 2; ++k) {
-            std::fprintf(stderr, "[pime td3 trace] %s:", k ? "actor " : "critic");
-            for (int i = 1; i < 30; ++i)
-                if (t[32 * k + i]) std::fprintf(stderr, " m%d=%.2f", i, (double)(t[32 * k + i] - t[32 * k]) * 0.01);
-            if (t[32 * k + 30]) std::fprintf(stderr, " shader_cycles=%lld", t[32 * k + 30]);   // s_memtime ticks first mark -> last mark
-            std::fprintf(stderr, "\n");
-        }
-    }
     return PIME_OK;
 }
 

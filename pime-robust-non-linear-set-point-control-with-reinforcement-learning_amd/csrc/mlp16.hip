@@ -1155,7 +1155,7 @@ __global__ __launch_bounds__(k16Threads, T <= 8 ? 2 : 1) void mlp16_forward_kern
 }
 
 // ---- PPO minibatch gradients of one net ------------------------------------------------------------------------------
-// PIME_FUSED_TRACE=<workgroup>: wall-clock marks (100 MHz) of that workgroup's first two groups -- a tuning aid
+// Wall-clock marks (100 MHz) of workgroup trace_wg's first two groups.  Nothing sets PpoArgs::trace any more (see ppo_train.hpp)
 #define PIME16_MARK(i)                                                                                          \
     do {                                                                                                        \
         if (a.trace && blockIdx.x == a.trace_wg && threadIdx.x == 0 && mark0 + (i) < 32) a.trace[mark0 + (i)] = wall_clock64(); \

@@ -29,11 +29,9 @@
 // Every workgroup stores its partial gradient into its own slab (no atomics: memory-side float atomics cost 0.5 TB/s
 // here); ppo_grad_reduce_kernel sums the slabs in slab order, so gradients are reproducible bit for bit, applies Adam to the
 // element it has just reduced and writes the new value into the packed images (pime_ppo_minibatch_step, pime_ppo_image_map).
-// PIME_FUSED_TRACE=<workgroup> prints wall-clock phase marks of that workgroup (tuning aid, not a production path).
 #include "ppo_device.hpp"
 #include "ppo_train.hpp"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace pime {
@@ -234,7 +232,7 @@ template <int AT, int BT, class BSrc, class Plan = DwPlan<AT, BT>>
 __device__ __forceinline__ void dw_rounds(float* __restrict__ X, int lane, int wave, const f32x16 (&az)[AT],
                                           const BSrc& bsrc, f32x16 (&acc)[Plan::PER], float& bsum,
                                           float* __restrict__ stage_dst, const float* __restrict__ stage_src,
-                                          int stage_n4, long long* tr = nullptr) {
+                                          int stage_n4) {
     constexpr int PER = Plan::PER, NKS = 16;
     constexpr int BUF = tsize(AT) + bsize(BT);
     constexpr int NP = BT * 16 / kFusedWaves;                               // B elements this wave publishes per round
@@ -257,15 +255,6 @@ __device__ __forceinline__ void dw_rounds(float* __restrict__ X, int lane, int w
         for (int i = 0; i < NP; ++i) p[(8 * ((pr0 + i) >> 2) + ((pr0 + i) & 3)) * kBPitch] = pv[i];
     };
 
-    unsigned long long tsum[5] = {0, 0, 0, 0, 0}, tprev = 0;
-    const bool stamping = tr != nullptr && wave == 0;
-#define PIME_STAMP(k)                                                                           \
-    if (stamping) {                                                                             \
-        unsigned long long tnow;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tnow)::"memory");            \
-        tsum[k] += tnow - tprev;                                                                \
-        tprev = tnow;                                                                           \
-    }
     PIME_LDS_BARRIER();  // X free
     b_fetch(0, pv);
     if (wave == 0) put_tile<AT>(X, lane, az);
@@ -274,8 +263,6 @@ __device__ __forceinline__ void dw_rounds(float* __restrict__ X, int lane, int w
 #pragma unroll 1
     for (int t = 0; t < kFusedWaves; ++t) {
         PIME_LDS_BARRIER();  // buffer t&1 published; buffer (t+1)&1 no longer read
-        if (tr && tid == 0) tr[t] = wall_clock64();
-        PIME_STAMP(4);   // barrier wait (the first one also absorbs the time before the loop)
         const float* cur = X + (t & 1) * BUF;
         float* nxt = X + ((t + 1) & 1) * BUF;
         float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -283,7 +270,6 @@ __device__ __forceinline__ void dw_rounds(float* __restrict__ X, int lane, int w
         // B elements for round t+2: global loads (or a few LDS reads), issued now, landed behind this round's MFMAs
         if (t + 2 < kFusedWaves) b_fetch(t + 2, pv2);
         if (wave == t + 1) put_tile<AT>(nxt, lane, az);
-        PIME_STAMP(0);   // fetch (+ A publish on the owner)
         PIME_NO_HOIST();
         if (pl.active) {
             const float* Ap = cur + h * tpitch(AT) + pl.ao * 32 + li;                  // k-step s: samples 2s + h
@@ -298,7 +284,6 @@ __device__ __forceinline__ void dw_rounds(float* __restrict__ X, int lane, int w
                     const float4 b4 = *reinterpret_cast<const float4*>(Bp + n * 32 * kBPitch + 4 * q);
                     bv[n][4 * q] = b4.x; bv[n][4 * q + 1] = b4.y; bv[n][4 * q + 2] = b4.z; bv[n][4 * q + 3] = b4.w;
                 }
-            PIME_STAMP(1);   // operand reads back
 #pragma unroll
             for (int s = 0; s < NKS; ++s) {
 #pragma unroll
@@ -309,25 +294,14 @@ __device__ __forceinline__ void dw_rounds(float* __restrict__ X, int lane, int w
 #pragma unroll
                 for (int s = 0; s < NKS; s += 2) bs2 += f32x2_t{av[s], av[s + 1]};
             }
-            if (stamping) {
-                float sink;
-                asm volatile("v_mov_b32 %0, %1" : "=v"(sink) : "v"(acc[PER - 1][0]));   // waits for the last MFMA
-            }
-            PIME_STAMP(2);   // MFMAs
         }
         PIME_NO_HOIST();
         if (t + 1 < kFusedWaves) b_publish(nxt);
 #pragma unroll
         for (int i = 0; i < NP; ++i) pv[i] = pv2[i];
         if (tid < per4) dst4[t * per4 + tid] = sv;
-        PIME_STAMP(3);   // B publish, staging write
     }
-#undef PIME_STAMP
     bsum = bs2.x + bs2.y;
-    if (tr && tid == 0) {
-        tr[8] = wall_clock64();
-        for (int k = 0; k < 5; ++k) tr[16 + k] = (long long)tsum[k];
-    }
 }
 
 // Element offset of accumulator register 0 of a wave's first output block (D[i = a feature][j = b feature]: column on
@@ -562,17 +536,9 @@ __device__ __forceinline__ void half_sums16(const float (&p)[16], float (&out)[2
     }
 }
 
-// TRACE = false compiles the marks out (the dual kernel: the trace pointers and the traced workgroup's index are live scalars of the
-// whole body otherwise)
-#define PIME_MARK(i)                                                             \
-    do {                                                                         \
-        if constexpr (TRACE)                                                     \
-            if (a.trace && bid == a.trace_wg && threadIdx.x == 0) a.trace[i] = wall_clock64(); \
-    } while (0)
-
 // bid / nb: this workgroup's index among the nb workgroups that work on THIS net (ppo_fused_kernel: the grid; ppo_fused_dual_kernel:
 // the net's share of a grid that serves both nets)
-template <int T, int KIND, bool TRACE>
+template <int T, int KIND>
 __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restrict__ lds, const int bid, const int nb) {
     constexpr bool MODULAR = KIND == MLP_MODULAR_ACTOR;
     constexpr bool CRITIC = KIND == MLP_CRITIC;
@@ -593,9 +559,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
     float* const hacc = lds + F.hacc;   // head weight gradient of the workgroup
     const int Do = a.D - a.Di;
 
-    PIME_MARK(0);
-    if constexpr (TRACE)
-        if (a.trace_span && threadIdx.x == 0 && bid < 512) a.trace_span[2 * bid] = wall_clock64();
     const float asl = CRITIC ? 0.f : a.a_std_log[0];
     for (int e = tid; e < kFusedWaves * md; e += kFusedThreads) hacc[e] = 0.f;
     // small segments live in LDS for the whole kernel.  All their loads are issued before the first LDS write: one
@@ -653,19 +616,10 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
         const int pos = tile * 32 + li;
         const bool valid = pos < a.B;
         const int64_t* const idx = a.indices + (a.index_row ? (size_t)a.index_row[0] * a.B : 0);
-#ifdef PIME_PPO_ABLATE_GATHER   // timing ablation only: the minibatch is rows 0 .. B-1 (no index load in front of the row loads; wrong results)
-        const long long row = valid ? pos : a.B - 1;
-#else
         const long long row = idx[valid ? pos : a.B - 1];
-#endif
         const float* xrow = a.state + (size_t)row * a.D;
-#ifdef PIME_PPO_ABLATE_STASH   // timing ablation only: every workgroup stashes into the first group's tiles (L2-resident, wrong results)
-        float* st = a.stash + (size_t)wave * T * 1024;
-        const float* st0 = a.stash;
-#else
         float* st = a.stash + (size_t)tile * T * 1024;
         const float* st0 = a.stash + (size_t)group * kFusedWaves * T * 1024;  // the group's first tile
-#endif
         // Stash regions 1 (and 2): the FIRST-layer activations (round 3).  Rounds 1-2 recomputed them from the states wherever the
         // backward needed them -- as B operand of the second layer's weight-gradient rounds and for act'(H1) -- which is ~1 000
         // vector instructions per wave for the critic and ~2 300 (640 of them transcendental pairs) for the modular actor; with
@@ -715,7 +669,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
             }
         }
         PIME_LDS_BARRIER();   // the states are in LDS (the images are still in flight)
-        PIME_MARK(1);
         const float* xl = xs + (wave * 32 + li) * a.D;   // this lane's state row
 
         // ---------------------------------------------------------------------------------- forward + loss gradient
@@ -769,7 +722,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
             PIME_NO_HOIST();
             y = layer_head<T>(lds + F.headw, lds[F.headb], lane, hl);
         }
-        PIME_MARK(2);
         float dout = 0.f;
         float s0 = 0.f, s1 = 0.f, gstd = 0.f;
         double m1 = 0.0, m2 = 0.0;
@@ -852,13 +804,11 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
         // stash stores of H2, which may stay outstanding
         if constexpr (DX_FIRST) wait_dma_then_barrier<kStashOps>();
         else __syncthreads();                                  // forward images dead, stash visible to the whole workgroup
-        PIME_MARK(3);
         float* const sl = a.slab + (size_t)bid * a.slab_stride;   // this workgroup's partial gradients
         const bool accum = group != bid;                      // a later sample group of the same workgroup
         if constexpr (MODULAR) {
             f32x16(&dn0)[T] = hl;                                                                   // dZn0
             f32x16 dcat[T];
-            PIME_MARK(4);
             {
                 f32x16 acc[DwPlan<T, T>::PER];
                 float bsum;
@@ -868,7 +818,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                 dw_store_full<T, T>(lane, wave, acc, bsum, sl + a.poff[8], sl + a.poff[9], accum);   // net.0
             }
             PIME_LDS_BARRIER();
-            PIME_MARK(5);
             PIME_NO_HOIST();
             layer_mfma<T, T, 2, false>(wbuf, nullptr, lane, dn0, dcat);
             {
@@ -876,14 +825,13 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                 stash_get<T>(st, lane, cat);
                 times_act_grad<T, 1>(dcat, cat);                                                    // [dZo2 | dZi2]
             }
-            PIME_MARK(6);
             {   // other_net.2 and integrator_net.2: one set of rounds over the W+X region (W is dead until the next dX)
                 f32x16 acc[CatPlan<T>::PER];
                 float bsum;
                 PIME_NO_HOIST();
                 dw_rounds<T, 2 * T, CatStashB<T>, CatPlan<T>>(
                     wbuf, lane, wave, dcat, CatStashB<T>{st1_0, st2_0, T * 1024},
-                    acc, bsum, nullptr, nullptr, 0, (TRACE && a.trace && bid == a.trace_wg) ? a.trace + 16 : nullptr);
+                    acc, bsum, nullptr, nullptr, 0);
                 const CatPlan<T> pl(wave);
                 if (pl.active) {
                     const int br = pl.ao >= H ? 1 : 0;
@@ -895,10 +843,8 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                 }
             }
             PIME_LDS_BARRIER();   // the rounds are done with the region
-            PIME_MARK(7);
             stage_image(wbuf, a.img_bwd + Lb.off[4], 2 * H * T * 256);   // other_net.2^T | integrator_net.2^T
             PIME_LDS_BARRIER();
-            PIME_MARK(8);
             if constexpr (T == 4) {
                 // One branch at a time (64 instead of 128 live dZ registers): dX with act'(h1) formed behind its MFMAs,
                 // then that branch's first-layer gradient.  The branch's transposed image (its half of W) is dead by
@@ -914,7 +860,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                         PIME_NO_HOIST();
                         layer_mfma_gate<H, T, 1, true>(img, lane, *reinterpret_cast<f32x16(*)[H]>(&dcat[br * H]), d1, v);   // dZ1
                     }
-                    PIME_MARK(9 + br);
                     float* gW = sl + a.poff[br ? 4 : 0], *gb = sl + a.poff[br ? 5 : 1];
                     if (a.D <= kFirstValuMaxD) {
                         first_grad_valu<T>(X, lane, wave, d1, xsp, a.D, col0, Din, gW, gb, accum);
@@ -925,7 +870,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                         dw_store<T, 1>(lane, wave, acc, bsum, gW, Din, md, Din, gb, accum);
                     }
                 }
-                PIME_MARK(11);
             } else
             {
                 f32x16 d1[2 * T];   // [dZo1 | dZi1]
@@ -937,7 +881,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                     stash_get<T>(st1, lane, hh);
                     times_act_grad<T, 1>(*reinterpret_cast<f32x16(*)[T]>(&d1[0]), hh);                  // dZo1
                 }
-                PIME_MARK(9);
                 PIME_NO_HOIST();
                 layer_mfma<H, T, 2, false>(wbuf + H * T * 1024, nullptr, lane, *reinterpret_cast<f32x16(*)[H]>(&dcat[H]),
                                            *reinterpret_cast<f32x16(*)[T]>(&d1[T]));
@@ -946,7 +889,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                     stash_get<T>(st2, lane, hh);
                     times_act_grad<T, 1>(*reinterpret_cast<f32x16(*)[T]>(&d1[T]), hh);                  // dZi1
                 }
-                PIME_MARK(10);
                 if (a.D <= kFirstValuMaxD) {   // other_net.0, integrator_net.0 on the vector ALUs
                     first_grad_valu<T>(X, lane, wave, *reinterpret_cast<f32x16(*)[T]>(&d1[0]), xsp, a.D, 0, Do,
                                        sl + a.poff[0], sl + a.poff[1], accum);
@@ -966,18 +908,15 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                         bias_store(bsum, sl + a.poff[br ? 5 : 1] + (pl.ao - br * T) * 32, lane, accum);
                     }
                 }
-                PIME_MARK(11);
             }
         } else {
             f32x16(&d)[T] = hl;                                                                     // dZ3
             f32x16 d2[T];
-            PIME_MARK(4);
             if constexpr (DX_FIRST) {
                 PIME_NO_HOIST();
                 layer_mfma<T, T, 2, false>(wbuf, nullptr, lane, d, d2);                              // dH2
                 times_act_grad<T, ACT>(d2, hk);                                                     // dZ2 (H2 from registers)
                 __syncthreads();   // wbuf read; the stash stores (issued a whole dX step ago) are visible to the workgroup
-                PIME_MARK(5);
             }
             {
                 f32x16 acc[DwPlan<T, T>::PER];
@@ -990,7 +929,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
             }
             if constexpr (!DX_FIRST) {
                 PIME_LDS_BARRIER();
-                PIME_MARK(5);
                 PIME_NO_HOIST();
                 layer_mfma<T, T, 2, false>(wbuf, nullptr, lane, d, d2);
                 {
@@ -999,18 +937,15 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                     times_act_grad<T, ACT>(d2, hh);                                                 // dZ2
                 }
             }
-            PIME_MARK(6);
             {
                 f32x16 acc[DwPlan<T, T>::PER];
                 float bsum;
                 PIME_NO_HOIST();
                 dw_rounds<T, T>(X, lane, wave, d2, StashB{st1_0, T * 1024}, acc, bsum,
-                                DX_FIRST ? nullptr : wbuf, DX_FIRST ? nullptr : a.img_bwd + Lb.off[3], DX_FIRST ? 0 : T * T * 256,
-                                (TRACE && a.trace && bid == a.trace_wg) ? a.trace + 16 : nullptr);
+                                DX_FIRST ? nullptr : wbuf, DX_FIRST ? nullptr : a.img_bwd + Lb.off[3], DX_FIRST ? 0 : T * T * 256);
                 dw_store_full<T, T>(lane, wave, acc, bsum, sl + a.poff[2], sl + a.poff[3], accum);      // net.2
             }
             PIME_LDS_BARRIER();
-            PIME_MARK(7);
             PIME_NO_HOIST();
             layer_mfma<T, T, 2, false>(wbuf, nullptr, lane, d2, d);
             {
@@ -1018,7 +953,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                 stash_get<T>(st1, lane, hh);                                                        // H1
                 times_act_grad<T, ACT>(d, hh);                                                      // dZ1
             }
-            PIME_MARK(8);
             if (a.D <= kFirstValuMaxD) {   // net.0 on the vector ALUs (W is dead: its LDS holds the partial sums)
                 first_grad_valu<T>(X, lane, wave, d, xsp, a.D, 0, a.D, sl + a.poff[0], sl + a.poff[1], accum);
             } else {
@@ -1030,9 +964,6 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
         }
     }
 
-    PIME_MARK(12);
-    if constexpr (TRACE)
-        if (a.trace_span && threadIdx.x == 0 && bid < 512) a.trace_span[2 * bid + 1] = wall_clock64();
     // ---- workgroup totals of the scalar sums, combined in a fixed order (the slabs make the gradients reproducible
     // bit for bit; only the loss sums, which are for logging, use atomics)
     __syncthreads();
@@ -1063,12 +994,7 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
 template <int T, int KIND>
 __global__ __launch_bounds__(kFusedThreads) void ppo_fused_kernel(PpoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    // tuning aid: shader-clock ticks (s_memtime) and 100 MHz ticks (s_memrealtime) of the traced workgroup -> the clock the SIMDs ran at
-    const bool timing = a.trace && (int)blockIdx.x == a.trace_wg && threadIdx.x == 0;
-    long long c0 = 0, w0 = 0;
-    if (timing) { c0 = (long long)__builtin_readcyclecounter(); w0 = wall_clock64(); }
-    ppo_fused_body<T, KIND, true>(a, lds, (int)blockIdx.x, (int)gridDim.x);
-    if (timing) { a.trace[38] = wall_clock64() - w0; a.trace[39] = (long long)__builtin_readcyclecounter() - c0; }
+    ppo_fused_body<T, KIND>(a, lds, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Both nets of an optimizer step in ONE launch: workgroups [0, na) run the actor's body, [na, na + nc) the critic's.  The two
@@ -1081,8 +1007,8 @@ template <int T, int AKIND>
 __global__ __launch_bounds__(kFusedThreads) void ppo_fused_dual_kernel(PpoArgs actor, PpoArgs critic, int na) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = (int)blockIdx.x;
-    if (b < na) ppo_fused_body<T, AKIND, false>(actor, lds, b, na);
-    else ppo_fused_body<T, MLP_CRITIC, false>(critic, lds, b - na, (int)gridDim.x - na);
+    if (b < na) ppo_fused_body<T, AKIND>(actor, lds, b, na);
+    else ppo_fused_body<T, MLP_CRITIC>(critic, lds, b - na, (int)gridDim.x - na);
 }
 
 // ==================================================================================================== slab reduction
@@ -1112,10 +1038,7 @@ struct ReduceArgs {
     float* dp_moments;   // not NULL (data parallel): the critic's gradient stays unscaled; [0..2] = sum r, sum r^2, B of this rank's minibatch
 };
 
-#ifndef PIME_REDUCE_BATCH
-#define PIME_REDUCE_BATCH 4
-#endif
-constexpr int kReduceBatch = PIME_REDUCE_BATCH;
+constexpr int kReduceBatch = 4;   // slab loads in flight per thread: swept 4..32, 17.5-17.8 us per launch whatever the depth
 __global__ __launch_bounds__(512) void ppo_grad_reduce_kernel(ReduceArgs a) {
     __shared__ float4 part[8][64];
     __shared__ float scale_sh;
@@ -1303,17 +1226,10 @@ int launch_repack(const PackArgs& critic, const PackArgs& actor, float* c_fwd, f
     return PIME_OK;
 }
 
-int fused_grid(int B) {
-    // PIME_FUSED_GRID=<n>: tuning aid -- fewer workgroups than 256-sample groups, so that a workgroup runs several groups back to
-    // back (the second one from a warm instruction cache); production: one workgroup per group up to 256
-    static const int cap = [] {
-        const char* e = std::getenv("PIME_FUSED_GRID");
-        const int v = e ? std::atoi(e) : 0;
-        return v > 0 && v < 256 ? v : 256;
-    }();
+int fused_grid(int B) {   // one workgroup per 256-sample group, at most 256
     const int ntiles = (B + 31) / 32;
-    int grid = (ntiles + kFusedWaves - 1) / kFusedWaves;
-    return grid > cap ? cap : grid;
+    const int grid = (ntiles + kFusedWaves - 1) / kFusedWaves;
+    return grid > 256 ? 256 : grid;
 }
 
 int launch_grad_reduce(const PpoArgs& critic, const PpoArgs& actor, int kind_c, int md_c, int kind_a, int md_a,

@@ -245,7 +245,7 @@ __device__ __forceinline__ void lds_put_frag4(float* tile, int tid, const float4
 }
 
 template <int AT, int BT>
-__device__ void dw_job(const DwJob& j, int tiles_per_wg, int dbg, float* lds) {
+__device__ void dw_job(const DwJob& j, int tiles_per_wg, float* lds) {
     constexpr int NQ = AT * BT;
     constexpr int PER_WAVE = (NQ + 3) / 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, li = lane & 31;
@@ -317,14 +317,14 @@ __device__ void dw_job(const DwJob& j, int tiles_per_wg, int dbg, float* lds) {
             const int m = tid & 31;
             const float* xm = xs + m * j.Din;
             if (j.b_kind == 2) {
-                for (int f = tid >> 5; f < 32; f += 8) Bm[f * kDwPitch + m] = (f < j.Din && !(dbg & 4)) ? xm[f] : 0.f;
+                for (int f = tid >> 5; f < 32; f += 8) Bm[f * kDwPitch + m] = f < j.Din ? xm[f] : 0.f;
             } else {
                 const int nf = 32 * BT;
                 for (int f = tid >> 5; f < nf; f += 8) {
                     float s = W1[nf * j.Din + f];
                     for (int c = 0; c < j.Din; ++c) s = fmaf(xm[c], W1[f * j.Din + c], s);
                     const float v = j.act == 0 ? (s > 0.f ? s : 0.f) : fast_tanh(s);
-                    Bm[(f >> 5) * kDwTile + (f & 31) * kDwPitch + m] = (dbg & 4) ? 0.f : v;
+                    Bm[(f >> 5) * kDwTile + (f & 31) * kDwPitch + m] = v;
                 }
             }
         }
@@ -341,7 +341,7 @@ __device__ void dw_job(const DwJob& j, int tiles_per_wg, int dbg, float* lds) {
         // MFMA, and the second half's reads before the first half's MFMAs, so the LDS latency hides behind matrix
         // work (the naive per-tile loop compiled to read -> lgkmcnt(0) -> 2 MFMAs, exposing it every 128 cycles).
         // kt = tq % BT is the same for every tile of a wave (4 % BT == 0), so B is read once per k-step.
-        if (wave < NQ && !(dbg & 2)) {
+        if (wave < NQ) {
             const int kt = wave % BT;
             const float* bp = Bm + kt * kDwTile + li * kDwPitch + h;
             float av[2][PER_WAVE][8], bv[2][8];
@@ -374,7 +374,7 @@ __device__ void dw_job(const DwJob& j, int tiles_per_wg, int dbg, float* lds) {
         if (tq < NQ) {
             const int ot = tq / BT, kt = tq % BT;
             const int col = kt * 32 + li;
-            if (col < j.out_cols && !(dbg & 1)) {
+            if (col < j.out_cols) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int rowi = ot * 32 + feat32(r, h);
@@ -391,12 +391,12 @@ __global__ __launch_bounds__(kDwThreads) void ppo_dw_kernel(DwArgs a) {
     const DwJob& j = a.job[blockIdx.y];
     const int key = j.a_tiles * 8 + j.b_tiles;
     switch (key) {
-        case 2 * 8 + 4: dw_job<2, 4>(j, a.tiles_per_wg, a.debug_skip, lds); break;
-        case 4 * 8 + 1: dw_job<4, 1>(j, a.tiles_per_wg, a.debug_skip, lds); break;
-        case 1 * 8 + 4: dw_job<1, 4>(j, a.tiles_per_wg, a.debug_skip, lds); break;
-        case 2 * 8 + 2: dw_job<2, 2>(j, a.tiles_per_wg, a.debug_skip, lds); break;
-        case 1 * 8 + 2: dw_job<1, 2>(j, a.tiles_per_wg, a.debug_skip, lds); break;
-        case 2 * 8 + 1: dw_job<2, 1>(j, a.tiles_per_wg, a.debug_skip, lds); break;
+        case 2 * 8 + 4: dw_job<2, 4>(j, a.tiles_per_wg, lds); break;
+        case 4 * 8 + 1: dw_job<4, 1>(j, a.tiles_per_wg, lds); break;
+        case 1 * 8 + 4: dw_job<1, 4>(j, a.tiles_per_wg, lds); break;
+        case 2 * 8 + 2: dw_job<2, 2>(j, a.tiles_per_wg, lds); break;
+        case 1 * 8 + 2: dw_job<1, 2>(j, a.tiles_per_wg, lds); break;
+        case 2 * 8 + 1: dw_job<2, 1>(j, a.tiles_per_wg, lds); break;
         default: break;
     }
 }

@@ -22,9 +22,12 @@ struct PpoArgs {
     float* loss_sums;  // [4]: sum(-surrogate), sum(entropy proxy), sum(smooth-l1), unused
     float* g_std;      // actor: gradient of a_std_log (accumulated)
     int stagger;       // start delay of waves 4-7 in units of s_sleep(127) (8128 cycles)
-    int trace_wg;      // workgroup whose marks are recorded
-    long long* trace_span;  // tuning aid: [workgroup][2] start / end wall clock of every workgroup
-    long long* trace;  // tuning aid (PIME_FUSED_TRACE): wall-clock marks of workgroup 0 / wave 0, NULL in production
+    // Read only by the phase marks left in ppo16_kernel (mlp16.hip); no caller sets them, so they are 0 / NULL.  Removing the marks
+    // changes that kernel's register allocation and spills, and the PIME_MLP16 / PIME_GRAD_BF16X3 tests then fault; until that is
+    // understood the kernel keeps its code as it is.
+    int trace_wg;
+    long long* trace_span;
+    long long* trace;
     float* grad[12];   // split pipeline: gradient tensors in nn.Linear (W, b) order, accumulated with atomics
     float* slab;       // fused kernel: per-workgroup partial gradients [gridDim.x][slab_stride] (slab_layout order)
     int slab_stride, poff[13];  // float offsets of the params inside a slab; poff[np] = scalar slot (g_std / moments)
@@ -103,7 +106,7 @@ constexpr int kMaxDwJobs = 16;
 
 struct DwArgs {
     DwJob job[kMaxDwJobs];
-    int njobs, tiles_per_wg, debug_skip;  // debug_skip: timing-only ablation bits (PIME_DW_DEBUG env), 0 in production
+    int njobs, tiles_per_wg;
 };
 
 }  // namespace pime

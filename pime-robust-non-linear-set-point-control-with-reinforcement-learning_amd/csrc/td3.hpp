@@ -97,9 +97,9 @@ struct Td3GradArgs {
     const float *act, *cri;    // critic launch: TARGET actor, ONLINE critic;  actor launch: ONLINE actor, TARGET critic
     const float* cri_target;   // critic launch only: the target critic
     float* slab;               // [grid][stride]
-    float* xg;                 // [B][td3_xg_stride(D)]: the minibatch's state rows (+ action), gathered by the critic launch, read back by the actor launch
+    float* xg;                 // [B][td3_xg_stride(D)]: the minibatch's state rows (+ action), gathered by a row's critic launch, read back
+                               // by the same row's actor launch (one copy: the next row's critic launch must not start before that)
     int stride, ngroups;
-    long long* trace;          // tuning aid (PIME_TD3_TRACE): wall-clock marks of workgroup 0 / thread 0, NULL in production
 };
 
 struct Td3ApplyArgs {

@@ -30,7 +30,6 @@
 // (Wts / wlayer: a register block of a layer would be 128 VGPRs), forms the md x md weight gradients in column slices, and at KF = 8
 // reads the first-layer weights from global memory (they do not fit beside the chain images in LDS).  The round-4 instantiations
 // (width 64 / 128, D <= 7) compile to the same arithmetic as before.
-#include <cstdlib>
 #include "td3.hpp"
 #include "pime_common.hpp"
 
@@ -39,17 +38,11 @@ namespace pime {
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kTd3Tile = 16;
-constexpr int kTd3DefaultWaves = 8;   // measured: 63.1 -> 60.4 us per optimizer step (profiles/r04_u_td3_waves_ab.txt)
 constexpr int kQP = 72, kTP = 4 * kQP;   // chain layout: floats between lane groups / tiles (72 = 16 samples x 4 + 8: the operand reads of the weight gradients hit 32 banks; pitches 68 .. 88 swept at the end of round 4: the launches take the same 20.0 / 21.7 us)
 constexpr uint32_t STREAM_TD3_SMOOTH = 3;
 
 #define TD3_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define TD3_NO_HOIST() asm volatile("" ::: "memory")
-// PIME_TD3_TRACE=1: 100 MHz wall-clock marks of workgroup 0 (tuning aid; the pointer is NULL in production)
-#define TD3_MARK(i)                                                                        \
-    do {                                                                                   \
-        if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[i] = wall_clock64();   \
-    } while (0)
 
 __device__ __forceinline__ f32x4_t mfma16(float a, float b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4_t ld4(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
@@ -102,13 +95,6 @@ __device__ __forceinline__ float chain_elem(const float* __restrict__ buf, int l
     return buf[t * kTP + (i >> 2) * kQP + (4 * s + q) * 4 + (i & 3)];
 }
 
-// Timing ablation only (-DPIME_TD3_ABLATE_W: every weight load of the md x md matrices folded into the tensor's first 4 KB -- wrong
-// results, the same instructions; what is left is the step without the L2 -> compute-unit weight stream)
-#ifdef PIME_TD3_ABLATE_W
-#define PIME_TD3_WOFF(x) ((x) & 1023)
-#else
-#define PIME_TD3_WOFF(x) (x)
-#endif
 // ---- weights: global -> registers --------------------------------------------------------------------------------------------------
 // forward: A operand of output tile t0 + n, k-step (kt, r) = W[16 (t0 + n) + i][16 kt + 4 q + r]: component r of one 16-byte load
 // (a wave-uniform base pointer + ONE 32-bit lane offset + compile-time offsets: with a 64-bit per-lane pointer hipcc spends two
@@ -119,7 +105,7 @@ __device__ __forceinline__ void load_w(const float* __restrict__ W, int t0, int 
 #pragma unroll
     for (int n = 0; n < PER; ++n)
 #pragma unroll
-        for (int kt = 0; kt < NT; ++kt) w[n][kt] = ld4(W + PIME_TD3_WOFF(o + n * 16 * (NT * 16) + 16 * kt));
+        for (int kt = 0; kt < NT; ++kt) w[n][kt] = ld4(W + o + n * 16 * (NT * 16) + 16 * kt);
 }
 // transposed (dX = W^T dZ): A operand of output (= input-feature) tile t0 + n, k-step (kt, r) = W[16 kt + 4 q + r][16 (t0 + n) + i]
 template <int NT, int PER>
@@ -130,7 +116,7 @@ __device__ __forceinline__ void load_wt(const float* __restrict__ W, int t0, int
 #pragma unroll
         for (int n = 0; n < PER; ++n)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) w[n][kt][r] = W[PIME_TD3_WOFF(o + (16 * kt + r) * (NT * 16) + 16 * n)];
+            for (int r = 0; r < 4; ++r) w[n][kt][r] = W[o + (16 * kt + r) * (NT * 16) + 16 * n];
 }
 
 // Width 256 (NT = 16, eight waves, PER = 2): a [PER][NT] register block of one layer's weights is 128 VGPRs, two of them (the next
@@ -488,8 +474,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
     const long long trow = a.b.row;
     float* const sl = a.slab + (size_t)blockIdx.x * a.stride;
     float loss_acc = 0.f;   // wave 0, lanes 0..15: this workgroup's loss terms
-    TD3_MARK(0);
-    const long long cyc0 = a.trace ? (long long)__builtin_readcyclecounter() : 0;   // shader clock (s_memtime) beside the 100 MHz marks
 
 #pragma unroll 1
     for (int group = blockIdx.x; group < a.ngroups; group += gridDim.x) {
@@ -546,7 +530,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             small_copy<NW * 64>(lds + F.small[2] + SC.b2, a.cri_target, PC.b2, PC.total, tid);
         }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
-        TD3_MARK(1);   // gather + small tensors
         // the online critic's input [s, a, 0 ..]: column q / 4 + q of sample j (this lane's first-layer B operands)
         float xs[KF];
 #pragma unroll
@@ -571,7 +554,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         f32x4_t hb[PER];   // the next layer's accumulators, initialised with its bias in front of the barrier
         bias_get<PER>(at + SA.b2, t0, lane, hb);
         TD3_BARRIER();
-        TD3_MARK(2);   // target actor layer 1
         chain_get<NT>(B0, lane, in);
         {
             wlayer(wA, in, hb);
@@ -581,7 +563,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         wload(wA, a.cri_target + PC.W2, t0, lane);
         bias_get<PER>(at + SA.b3, t0, lane, hb);
         TD3_BARRIER();
-        TD3_MARK(3);   // layer 2
         chain_get<NT>(B1, lane, in);
         float next_a;
         {
@@ -595,7 +576,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             const float nz = fminf(fmaxf(eps * a.b.policy_noise, -a.b.noise_clip), a.b.noise_clip);   // net.py:109
             next_a = fminf(fmaxf(tanhf(pre) + nz, -1.0f), 1.0f);
         }
-        TD3_MARK(4);   // layer 3 + head: next_a
         // ------------------------------------------------------------------ q_label = r + mask * min(cri_target twin heads)(s', next_a)
         wload(wB, a.cri + PC.W2, t0, lane);
         float label;
@@ -619,7 +599,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             const float tq1 = red_get<NW>(red, 1, lane) + ct[SC.q1b], tq2 = red_get<NW>(red, 2, lane) + ct[SC.q2b];
             label = reward + mask * fminf(tq1, tq2);
         }
-        TD3_MARK(5);   // target critic: label
         // ------------------------------------------------------------------ online twin critic on (s, a): forward
         f32x4_t h1[PER], h2[PER];
         {
@@ -637,7 +616,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         red_put(red, 3, wave, lane, head_partial<PER>(cr + SC.q1w, t0, lane, h2));
         red_put(red, 4, wave, lane, head_partial<PER>(cr + SC.q2w, t0, lane, h2));
         TD3_BARRIER();
-        TD3_MARK(6);   // online critic forward
         // ------------------------------------------------------------------ SmoothL1 x 2 (beta = 1, mean) and its gradient
         float g1 = 0.f, g2 = 0.f;
         {
@@ -674,10 +652,8 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             }
         }
         TD3_BARRIER();   // dZ2 published
-        TD3_MARK(7);   // loss, head gradients, dZ2
         dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[2].slab_off, t0, lane, accum);   // net_sa.2 weight gradient
         TD3_NO_HOIST();
-        TD3_MARK(8);   // dW2
         chain_get<NT>(B2, lane, in);
         {
             f32x4_t d1[PER];
@@ -688,7 +664,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d1, accum);   // net_sa.0 bias
         }
         TD3_BARRIER();   // dZ1 published
-        TD3_MARK(9);   // dH1, dZ1
         {
             f32x4_t acc[PER][CT];
             dw_first<PER, XW>(B0, xin, t0, lane, acc);
@@ -699,8 +674,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
                 for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
         }
     }
-    TD3_MARK(10);   // dW1
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[30] = (long long)__builtin_readcyclecounter() - cyc0;
     if (wave == 0) {
         const float t = row_sum16(loss_acc);
         if (tid == 0) st4(sl + SL.scalar_off, f32x4_t{t, 0.f, 0.f, 0.f});
@@ -740,8 +713,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
     const float invB = 1.0f / (float)a.b.B;
     float* const sl = a.slab + (size_t)blockIdx.x * a.stride;
     float q_acc = 0.f;
-    TD3_MARK(0);
-    const long long cyc0 = a.trace ? (long long)__builtin_readcyclecounter() : 0;
 
 #pragma unroll 1
     for (int group = blockIdx.x; group < a.ngroups; group += gridDim.x) {
@@ -783,7 +754,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
             small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
         }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
-        TD3_MARK(1);
         if (wave == 0) {   // the actor's input rows [16 samples][XW columns, zero beyond D] for its first-layer weight gradient
 #pragma unroll
             for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? sx[k] : 0.f;
@@ -811,7 +781,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         red_put(red, 0, wave, lane, head_partial<PER>(ac + SA.w4, t0, lane, a3));
         TD3_BARRIER();
         const float act = tanhf(red_get<NW>(red, 0, lane) + ac[SA.b4]);
-        TD3_MARK(2);   // actor forward
         // ------------------------------------------------------------------ q1 = cri_target.q1(s, action)
         {
             float xt[KF];
@@ -838,7 +807,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         }
         wload_t(wA, a.act + PA.W3, t0, lane);   // dA2 = W3^T dZ3
         TD3_BARRIER();
-        TD3_MARK(3);   // target critic forward, dZc2
         if (valid && wave == 0 && q == 0) q_acc += red_get<NW>(red, 1, lane) + ct[SC.q1b];
         chain_get<NT>(B3, lane, in);
         float dpre;
@@ -859,7 +827,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
             TD3_BARRIER();
             dpre = red_get<NW>(red, 2, lane) * (1.0f - act * act);   // tanh'
         }
-        TD3_MARK(4);   // critic backward to the action
         // ------------------------------------------------------------------ actor backward + weight gradients
         {
             f32x4_t v[PER], dz[PER];
@@ -882,7 +849,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         }
         wload_t(wB, a.act + PA.W2, t0, lane);   // dA1 = W2^T dZ2
         TD3_BARRIER();   // dZ3 published
-        TD3_MARK(5);
         dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[4].slab_off, t0, lane, accum);   // net.4: dZ3^T A2
         TD3_NO_HOIST();
         chain_get<NT>(B2, lane, in);
@@ -895,7 +861,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
             vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, d, accum);    // net.2 bias
         }
         TD3_BARRIER();   // dZ2 published
-        TD3_MARK(6);   // dW3, dA2
         dw_slab<NT, PER, S>(B3, B0, sl + SL.seg[2].slab_off, t0, lane, accum);   // net.2: dZ2^T A1
         TD3_NO_HOIST();
         chain_get<NT>(B3, lane, in);
@@ -908,7 +873,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
             vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d, accum);    // net.0 bias
         }
         TD3_BARRIER();   // dZ1 published
-        TD3_MARK(7);   // dW2, dA1
         {
             f32x4_t acc[PER][CT];
             dw_first<PER, XW>(B1, xin, t0, lane, acc);
@@ -919,8 +883,6 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
                 for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
         }
     }
-    TD3_MARK(8);   // dW1
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[30] = (long long)__builtin_readcyclecounter() - cyc0;
     if (wave == 0) {
         const float t = row_sum16(q_acc);
         if (tid == 0) st4(sl + SL.scalar_off, f32x4_t{t, 0.f, 0.f, 0.f});
@@ -937,15 +899,10 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
 // (bit-reproducible); the threads of group 0 then own four gradient elements each: they write them, apply torch.optim.Adam (defaults:
 // no weight decay, no amsgrad) to their parameters and, on a delayed step, target = tau * param + (1 - tau) * target (agent.py:116-124,
 // the reference's operand order).
-#ifndef PIME_APPLY_WORDS
-#define PIME_APPLY_WORDS 64   // swept at the end of round 4 (words x threads, us per launch): 16x256 9.6, 8x256 11.6, 32x256 8.7, 64x256 8.2, 128x256 10.6,
-                              // 32x512 8.6, 64x512 7.4, 128x512 9.1, 256x512 14.8, 64x1024 7.5, 32x1024 12.8 (profiles/r04_w_td3_apply_shape_sweep.txt)
-#endif
-#ifndef PIME_APPLY_THREADS
-#define PIME_APPLY_THREADS 512
-#endif
-constexpr int kApplyThreads = PIME_APPLY_THREADS;
-constexpr int kApplyWords = PIME_APPLY_WORDS, kApplyGroups = kApplyThreads / kApplyWords;
+// Words x threads swept at the end of round 4 (us per launch): 16x256 9.6, 8x256 11.6, 32x256 8.7, 64x256 8.2, 128x256 10.6,
+// 32x512 8.6, 64x512 7.4, 128x512 9.1, 256x512 14.8, 64x1024 7.5, 32x1024 12.8 (profiles/r04_w_td3_apply_shape_sweep.txt)
+constexpr int kApplyThreads = 512;
+constexpr int kApplyWords = 64, kApplyGroups = kApplyThreads / kApplyWords;
 constexpr int kApplyBatch = 256 / kApplyGroups > 32 ? 32 : 256 / kApplyGroups;   // slab loads a thread keeps in flight: one batch covers 256 slabs
 __global__ __launch_bounds__(kApplyThreads) void td3_apply_kernel(Td3ApplyArgs a) {
     __shared__ float4 part[kApplyGroups][kApplyWords];
@@ -1059,54 +1016,28 @@ __global__ __launch_bounds__(kApplyThreads) void td3_apply_kernel(Td3ApplyArgs a
 }
 
 // ======================================================================================================== host side
-int td3_grid(int B) {
-    // PIME_TD3_GRID=<n>: tuning aid -- fewer workgroups than sample tiles, so that a workgroup runs several groups back to back
-    // (the second one from a warm instruction cache); production: one group per workgroup up to kTd3MaxSlabs
-    static const int cap = [] {
-        const char* e = std::getenv("PIME_TD3_GRID");
-        const int v = e ? std::atoi(e) : 0;
-        return v > 0 && v < kTd3MaxSlabs ? v : kTd3MaxSlabs;
-    }();
+int td3_grid(int B) {   // one 16-sample group per workgroup, at most kTd3MaxSlabs
     const int ngroups = (B + kTd3Tile - 1) / kTd3Tile;
-    return ngroups < cap ? ngroups : cap;
+    return ngroups < kTd3MaxSlabs ? ngroups : kTd3MaxSlabs;
 }
 int64_t td3_workspace_floats(int D, int md, int B) {
     const int64_t g = td3_grid(B);
-    // slabs + the gathered rows [2][B][td3_xg_stride(D)] (by row parity)
-    return g * (td3_actor_slab(D, md).stride + td3_critic_slab(D, md).stride) + (int64_t)2 * B * td3_xg_stride(D);
+    // slabs + the gathered rows [B][td3_xg_stride(D)]
+    return g * (td3_actor_slab(D, md).stride + td3_critic_slab(D, md).stride) + (int64_t)B * td3_xg_stride(D);
 }
 bool td3_supported(int D, int A, int md) { return A == 1 && D >= 1 && D <= kTd3MaxD && (md == 64 || md == 128 || md == 256); }
 
-// Waves per workgroup of the gradient kernels at width 128: 4 = one wave per SIMD owning two of a layer's eight output tiles,
-// 8 = two waves per SIMD owning one tile each (the non-MFMA instructions of one wave issue behind the other's MFMAs).
-// Width 64 has four output tiles: four waves; width 256 sixteen: eight waves owning two each.  PIME_TD3_WAVES=4|8 is the A/B knob
-// of the round-4 shapes (width 128, D <= 7).
-static int td3_waves(int md) {
-    static const int w = [] {
-        const char* e = std::getenv("PIME_TD3_WAVES");
-        const int v = e ? std::atoi(e) : kTd3DefaultWaves;
-        return v == 8 ? 8 : 4;
-    }();
-    return md == 256 ? 8 : md == 128 ? w : 4;
-}
-template <int MD, int DD, int NW, int KF>
-static int launch_grad_w(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
+// Waves per workgroup of the gradient kernels.  Width 64 has four output tiles: four waves, one per SIMD.  Widths 128 and 256: eight
+// waves, two per SIMD, owning one / two of a layer's eight / sixteen output tiles (the non-MFMA instructions of one wave issue behind
+// the other's MFMAs); at width 128 that measured 60.4 us per optimizer step against 63.1 on four waves (profiles/r04_u_td3_waves_ab.txt).
+template <int MD, int DD, int KF>
+static int launch_grad_d(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
+    constexpr int NW = MD == 64 ? 4 : 8;
     const size_t lds_bytes = sizeof(float) * (size_t)td3_lds(MD / 16, a.D).total;
     if (critic) hipLaunchKernelGGL((td3_critic_kernel<MD, DD, NW, KF>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
     else hipLaunchKernelGGL((td3_actor_kernel<MD, DD, NW, KF>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
-}
-template <int MD, int DD, int KF>
-static int launch_grad_d(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
-    if constexpr (MD == 256 || (MD == 128 && KF == 8)) {
-        return launch_grad_w<MD, DD, 8, KF>(critic, a, grid, s);
-    } else if constexpr (MD == 128) {
-        if (td3_waves(MD) == 8) return launch_grad_w<MD, DD, 8, KF>(critic, a, grid, s);
-        return launch_grad_w<MD, DD, 4, KF>(critic, a, grid, s);
-    } else {
-        return launch_grad_w<MD, DD, 4, KF>(critic, a, grid, s);
-    }
 }
 template <int MD>
 static int launch_grad(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {

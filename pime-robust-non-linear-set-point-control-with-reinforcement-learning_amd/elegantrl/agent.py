@@ -135,7 +135,6 @@ class AgentPPO(AgentBase):
         self.noise_hook = None  # tests: callable(t, shape) -> exploration noise tensor (else torch.randn)
         self.use_fused_update = True
         self.use_hip_graphs = True
-        self.use_single_graph = True     # one graph per optimizer step when nothing has to happen between its launches
         self.use_graph_collective = True  # data parallel: capture the RCCL all-reduce INSIDE that one graph
         self.use_update_graph = True      # ... and, once that graph exists, all n_steps optimizer steps of an update as ONE graph
         self.use_fused_rollout = True
@@ -543,7 +542,7 @@ class AgentPPO(AgentBase):
         # an eager all-reduce in between cost 14 % on one rank before any communication).  If the capture fails (a torch / RCCL
         # build that refuses collectives under capture) the agent falls back to the two-graph sequence for good.
         in_graph_dp = self.dp is not None and self.use_graph_collective and getattr(self.dp, "graph_capturable", False)
-        one_graph = self.use_single_graph and (self.dp is None or in_graph_dp) and use_table and self.launch_timer is None
+        one_graph = (self.dp is None or in_graph_dp) and use_table and self.launch_timer is None
         if st.mode != (use_table, one_graph, fuse_adam, dp_union):   # the captured graphs bake in the index source and the step form
             st.mode, st.graph_a, st.graph_b, st.graph_full = (use_table, one_graph, fuse_adam, dp_union), None, None, None
             st.graph_update, st.graph_update_steps = None, None
@@ -706,21 +705,13 @@ class AgentTD3(AgentBase):
         self.update_freq = 2
         self.use_hip_graphs = True
         self.use_fused_rollout = True   # vectorised env: the whole explore call as ONE launch (csrc/rollout_offpolicy.hip)
-        # target Q of the critic objective through pime_mlp_forward (_target_packs).  OFF by default: at the TD3 batch of 4 096 rows a
-        # forward is 16 workgroups on three serial 256-MFMA chains (~25 us each), slower than rocBLAS's small GEMMs -- 165 vs 157 ms
-        # per bench step.  PIME_TD3_FUSED_TARGETS=1 switches it on (parity: tests/test_gpu_td3.py).
-        self.use_fused_targets = os.environ.get("PIME_TD3_FUSED_TARGETS", "0") == "1"
         self.use_fused_update = os.environ.get("PIME_TD3_FUSED", "1") == "1"   # the optimizer step on the hand-written kernels
-        # critic / actor chains as parallel graph branches (rows without a soft update): bit-identical, measured NEUTRAL (58.1 vs 58.4 M:
-        # each launch already fills the chip, overlapped launches only stretch each other -- DESIGN.md section 4c), so off by default
-        self.use_two_streams = os.environ.get("PIME_TD3_TWO_STREAMS", "0") == "1"
         self.draw_hook = None      # tests: callable(n_steps, batch) -> (idx, nxt, noise) tables of a whole update (injected draws)
         self.launch_timer = None   # bench.py: callable(name, fn) timing one update's launches with HIP events
         self._fused_td3 = None
         self._graphs = None
         self._obs = None
         self._packed_act = None
-        self._tpacks = None
 
     def init(self, net_dim, state_dim, action_dim, if_per=False):
         assert not if_per, "prioritised replay is not on the residual-control path"
@@ -740,12 +731,10 @@ class AgentTD3(AgentBase):
         self.act_optimizer = torch.optim.Adam(self.act.parameters(), lr=self.learning_rate, **kw)
         self._graphs = None
         self._packed_act = None
-        self._tpacks = None
         self._fused_td3 = None   # its Adam moments belong to the optimizers just replaced
 
     def weights_changed(self):
         super().weights_changed()
-        self._tpacks = None   # the target nets' packed images are stale (checkpoint load, rebuilt optimizer)
         self._graphs = None   # (the fused step reads the parameters where they live: nothing of it goes stale)
 
     def _fused_step(self, batch_size):
@@ -761,23 +750,6 @@ class AgentTD3(AgentBase):
                 return None
         f.ensure_batch(batch_size)
         return f
-
-    def _target_packs(self):
-        """(actor_target, q1 head, q2 head of cri_target) as packed images of the hand-written forward kernel, or None -> the torch
-        modules.  The no-grad half of the critic objective (agent.py:363-367: next_a = act_target.get_action(next_s),
-        next_q = min(cri_target.get_q1_q2(next_s, next_a))) is then three pime_mlp_forward launches on the f32 matrix cores (the twin
-        heads share the trunk through an identity layer: backend.packed_twin_heads) instead of ~15 rocBLAS / elementwise ones; the
-        images are re-packed right behind every soft update (_one_update), inside the same captured graph."""
-        if self._tpacks is None:
-            self._tpacks = False
-            ok = (self.use_fused_targets and self.device.type == "cuda" and hasattr(self.backend, "packed_twin_heads")
-                  and getattr(self.act_target, "action_dim", 1) == 1)
-            if ok:
-                a = self.backend.packed(self.act_target)
-                q = self.backend.packed_twin_heads(self.cri_target) if a is not None else None
-                if a is not None and q is not None:
-                    self._tpacks = (a, q[0], q[1])
-        return self._tpacks or None
 
     def _prior_term(self, states):
         """Prior-controller part of the env action (none for plain TD3)."""
@@ -877,16 +849,8 @@ class AgentTD3(AgentBase):
     def get_obj_critic_raw(self, buffer, batch_size):
         with torch.no_grad():
             reward, mask, action, state, next_s = buffer.sample_batch(batch_size)
-            tp = self._target_packs() if next_s.is_cuda else None
-            if tp is not None:   # the same arithmetic, the forwards on the hand-written kernel (net.py: Actor.get_action)
-                a = tp[0](next_s).tanh().unsqueeze(1)
-                noise = (torch.randn_like(a) * self.policy_noise).clamp(-0.5, 0.5)
-                next_a = (a + noise).clamp(-1.0, 1.0)
-                sa = torch.cat((next_s, next_a), dim=1)
-                next_q = torch.min(tp[1](sa), tp[2](sa)).unsqueeze(1)
-            else:
-                next_a = self.act_target.get_action(next_s, self.policy_noise)
-                next_q = torch.min(*self.cri_target.get_q1_q2(next_s, next_a))
+            next_a = self.act_target.get_action(next_s, self.policy_noise)
+            next_q = torch.min(*self.cri_target.get_q1_q2(next_s, next_a))
             q_label = reward + mask * next_q
         q1, q2 = self.cri.get_q1_q2(state, action)
         return self.criterion(q1, q_label) + self.criterion(q2, q_label), state
@@ -903,11 +867,8 @@ class AgentTD3(AgentBase):
         if self.dp is not None:
             self.dp.average_gradients([p for p in self.cri.parameters() if p.grad is not None])
         self.cri_optimizer.step()
-        tp = self._tpacks or None
         if soft:
             self.soft_update(self.cri_target, self.cri, self.soft_update_tau)
-            if tp is not None:
-                tp[1].repack(); tp[2].repack()
         obj_actor = -self.cri_target(state, self.act(state)).mean()
         self.act_optimizer.zero_grad(set_to_none=False)
         obj_actor.backward()
@@ -916,8 +877,6 @@ class AgentTD3(AgentBase):
         self.act_optimizer.step()
         if soft:
             self.soft_update(self.act_target, self.act, self.soft_update_tau)
-            if tp is not None:
-                tp[0].repack()
         return obj_actor.detach(), obj_critic.detach()
 
     def update_net(self, buffer, target_step, batch_size, repeat_times):
@@ -994,9 +953,6 @@ class AgentTD3(AgentBase):
         f.loss.zero_()
         f.begin_update()   # table row 0; the noise epoch advances (a captured graph draws fresh noise in every replay)
 
-        side = st.get("side")
-        if side is None and self.use_two_streams and self.dp is None:
-            side = st["side"] = torch.cuda.Stream(device=dev)
         # data parallel: the two all-reduces of every step are captured inside the update's graph where the communicator allows it
         # (RCCL: yes; gloo and a refused capture: eager launches, decided for all ranks together)
         in_graph_dp = (self.dp is not None and getattr(self, "use_graph_collective", True)
@@ -1008,12 +964,7 @@ class AgentTD3(AgentBase):
                    noise_seed=self._smooth_seed, row=k, phases=phases)
 
         def run():
-            """The critic chain (gradients, apply) on the current stream, the actor chain on a side stream.  Only rows with the
-            delayed soft update tie the two completely: the actor's gradients read the critic TARGET (written by the critic's apply
-            on soft rows only) and the state rows its critic launch gathered; the next row's critic gradients read the actor TARGET
-            (written by the actor's apply on soft rows only).  On the other rows the critic's apply runs beside the actor's
-            gradients and the actor's apply beside the next row's critic gradients -- inside the captured graph these are parallel
-            branches.  Same arithmetic, same bits as the one-stream order (tests/test_gpu_td3_fused.py)."""
+            """Every optimizer step's launches, in order, on the current stream."""
             if self.dp is not None:
                 # data parallel: a net's slab reduction leaves THIS rank's gradient, the ranks average it, Adam (+ the delayed soft
                 # update) is applied from the averaged tensor -- five launches and two all-reduces per step (ops.FusedTD3.step_dp); G
@@ -1025,29 +976,11 @@ class AgentTD3(AgentBase):
                     self.dp.all_reduce_mean(f.act_grad)
                     one(k, 128)
                 return
-            if side is None:
-                for k in range(n_steps):
-                    one(k, 15)
-                return
-            main = torch.cuda.current_stream(dev)
-            side.wait_stream(main)
             for k in range(n_steps):
-                soft = k % self.update_freq == 0
-                one(k, 1)                       # critic gradients (gathers the row's states)
-                if soft:
-                    one(k, 2)                   # critic apply writes the critic target: the actor's gradients must see it
-                    side.wait_stream(main)
-                else:
-                    side.wait_stream(main)      # the actor's gradients need the gathered rows only
-                    one(k, 2)
-                with torch.cuda.stream(side):
-                    one(k, 4)
-                    one(k, 8)
-                if soft or k == n_steps - 1:
-                    main.wait_stream(side)      # the next critic gradients read the actor target this row's actor apply wrote
+                one(k, 15)
 
         key = (buffer.buf_state.data_ptr(), buffer.buf_other.data_ptr(), noise is None, self.soft_update_tau, self.update_freq,
-               self.policy_noise, side is not None, self.dp is not None)
+               self.policy_noise, self.dp is not None)
         if can_graph and st["warm"] and (st["graph"] is None or st["key"] != key):
             refused = None
             try:

@@ -4,7 +4,6 @@ All operands are CUDA (ROCm) tensors; launches go to torch's current stream.  No
 a CPU tensor raises.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -180,12 +179,8 @@ class FusedPPOGrad:
     def image_map(self):
         """int32 [2 n]: where every element of the flat parameter tensor sits in its net's forward / transposed image
         (pime_ppo_image_map).  With it the fused optimizer step keeps the images current by itself (`images_follow_step`) and the
-        re-pack launch after every step goes away; None if the library cannot derive it (the caller then re-packs as before).
-        PIME_NO_IMAGE_MAP=1 turns it off (A/B)."""
+        re-pack launch after every step goes away; None if the library cannot derive it (the caller then re-packs as before)."""
         if self._image_map is None:
-            if os.environ.get("PIME_NO_IMAGE_MAP"):
-                self._image_map = False
-                return None
             if self._structs is None:
                 self._build_structs()
             actor, critic, _ = self._structs

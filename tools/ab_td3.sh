@@ -5,7 +5,6 @@ OUT=gpurun_out; mkdir -p $OUT
 timeout -k 10 400 python -m pytest tests/test_gpu_td3_fused.py tests/test_gpu_td3.py -q -x > $OUT/${TAG}_pytest.log 2>&1
 rc=$?; tail -3 $OUT/${TAG}_pytest.log
 if [ $rc -ne 0 ]; then tail -40 $OUT/${TAG}_pytest.log; exit 1; fi
-PIME_TD3_TRACE=1 timeout -k 10 120 python tools/td3_trace.py 2>&1 | grep "td3 trace" | tail -2
 rm -f $OUT/${TAG}.log
 for rep in 1 2 3; do
   for v in "$@"; do

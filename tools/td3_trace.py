@@ -1,5 +1,5 @@
-"""Phase marks of workgroup 0 of the two TD3 gradient kernels (PIME_TD3_TRACE=1 python tools/td3_trace.py [width] [batch]) and
-event-timed optimizer steps on a synthetic replay buffer (no env): the tuning loop of csrc/td3_fused.hip."""
+"""Event-timed fused TD3 optimizer steps on a synthetic replay buffer, no env (python tools/td3_trace.py [width] [batch]): the
+tuning loop of csrc/td3_fused.hip, and the workload tools/kstats.sh and tools/pmc_pipe.sh profile."""
 import os
 import sys
 
@@ -28,9 +28,6 @@ def run(n):
 
 
 run(3)
-torch.cuda.synchronize()
-if os.environ.get("PIME_TD3_TRACE"):
-    sys.exit(0)
 torch.cuda.synchronize()
 g = torch.cuda.CUDAGraph()
 with torch.cuda.graph(g):
