@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 20
+#define PIME_ABI_VERSION 21
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -197,6 +197,9 @@ int pime_gae_scan(const float* reward, const float* mask, const float* value, in
  *   kind PIME_MLP_PLAIN_ACTOR    replaces ActorResidualPPO / ActorPPO mean, net_residual.py:19-22,45-48
  *                                (same shape, Tanh); params[8] as above
  *   kind PIME_MLP_MODULAR_ACTOR  replaces ActorResidualIntegratorModularPPO mean, net_residual.py:153-160,172-176
+ *   kind PIME_MLP_SAC_ACTOR      replaces ActorSAC's net_state + net_a_avg / net_a_std, elegantrl/net.py:197-205 (width 64 / 128): params =
+ *                                ten tensors in module order (net_state.0/2/4, net_a_avg, net_a_std: W, b); ReLU, Hardswish, Hardswish
+ *                                body; the image carries both head rows; pime_mlp_forward returns the mean head BEFORE its tanh
  *                                params[12] = other_net.0 W,b ; other_net.2 W,b ; integrator_net.0 W,b ;
  *                                integrator_net.2 W,b ; net.0 W,b ; net.2 W,b ; Di = integrator_dim (trailing
  *                                columns of x)
@@ -206,7 +209,7 @@ int pime_gae_scan(const float* reward, const float* mask, const float* value, in
  * Integrator observation :11-18 -- on 16-sample tiles of v_mfma_f32_16x16x4_f32 with the weight images streamed through LDS in
  * k-slices, csrc/mlp16.hip; the modular actor's md -> md/2 tower layers are rectangular chain layers there).
  * out [dev] float32[M] is the scalar head (value, or pre-tanh action mean without noise and prior term). */
-enum pime_mlp_kind { PIME_MLP_CRITIC = 0, PIME_MLP_PLAIN_ACTOR = 1, PIME_MLP_MODULAR_ACTOR = 2 };
+enum pime_mlp_kind { PIME_MLP_CRITIC = 0, PIME_MLP_PLAIN_ACTOR = 1, PIME_MLP_MODULAR_ACTOR = 2, PIME_MLP_SAC_ACTOR = 3 };
 /* floats in the packed image (0 and an error message if the shape is unsupported) */
 int64_t pime_mlp_packed_floats(int32_t kind, int32_t D, int32_t Di, int32_t md);
 int pime_mlp_pack(int32_t kind, int32_t D, int32_t Di, int32_t md, const float* const* params, float* packed,
@@ -356,7 +359,8 @@ int pime_rollout_h(pime_env* env, int32_t kind, int32_t md, const float* packed_
  * n_steps steps of every lane under the DETERMINISTIC residual policy a_env = tanh(mean(s)) + s @ priorK -- no exploration noise,
  * no auto-reset, no per-step host round trip -- with the env state in registers.  Handles in PIME_STATE_MIXED or PIME_STATE_F64
  * mode (the latter reproduces the reference's float64 protocol records to 1e-11), pH or Integrator water tank, Philox draws.
- *   kind         PIME_MLP_PLAIN_ACTOR | PIME_MLP_MODULAR_ACTOR with packed_actor = its pime_mlp_pack image (width 64 / 128), or -1:
+ *   kind         PIME_MLP_PLAIN_ACTOR | PIME_MLP_MODULAR_ACTOR | PIME_MLP_SAC_ACTOR (ActorSAC.forward = tanh(net_a_avg), net.py:197-199)
+ *                with packed_actor = its pime_mlp_pack image (width 64 / 128), or -1:
  *                the prior controller alone (get_linear_action, ph.py:227-231), packed_actor ignored
  *   seg_len      0: plain episode.  > 0: every seg_len steps (from step 0) a protocol segment starts: set-point r =
  *                setpoints[segment], integrated error 0, step counter 0, plant state kept -- what the protocols' `env.reset();
@@ -390,6 +394,14 @@ int pime_rollout_offpolicy_supported(const pime_env* env, int32_t md);
 int pime_rollout_offpolicy(pime_env* env, int32_t md, const float* packed_actor, const double* priorK, float explore_noise,
                            float gamma, float reward_scale, int32_t n_steps, uint64_t noise_seed, uint32_t noise_epoch,
                            float* obs, float* ring_state, float* ring_other, int32_t slot0, int32_t slots, pime_stream stream);
+/* The same launch for AgentSAC -- replaces AgentBase.explore_env's body (elegantrl/agent.py:54-70) with AgentSAC.select_action
+ * (:425-431) and ActorSAC.get_action (net.py:201-205): a = tanh(avg + exp(clamp(log_std, -20, 2)) * eps), eps the SAME Philox
+ * stream-2 draw (counter (lane, noise_epoch, t)); the ring stores the squashed action.  packed_actor: pime_mlp_pack image of kind
+ * PIME_MLP_SAC_ACTOR, width 64 / 128; everything else as pime_rollout_offpolicy. */
+int pime_rollout_offpolicy_sac_supported(const pime_env* env, int32_t md);
+int pime_rollout_offpolicy_sac(pime_env* env, int32_t md, const float* packed_actor, const double* priorK, float gamma,
+                               float reward_scale, int32_t n_steps, uint64_t noise_seed, uint32_t noise_epoch, float* obs,
+                               float* ring_state, float* ring_other, int32_t slot0, int32_t slots, pime_stream stream);
 
 /* -- fused TD3 optimizer step ---------------------------------------------------------------------------------------
  * replaces, per iteration of AgentTD3.update_net's loop (elegantrl/agent.py:314-331): get_obj_critic_raw (:361-370 -- the gather of
@@ -450,6 +462,56 @@ int64_t pime_td3_workspace_floats(int32_t D, int32_t md, int32_t B);
 int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_td3_batch* batch,
                   float tau, int32_t update_freq, int32_t soft_mode, int32_t phases, float* workspace, float* loss,
                   pime_stream stream);
+
+/* -- fused SAC optimizer step ---------------------------------------------------------------------------------------
+ * replaces, per iteration of AgentSAC.update_net's loop (elegantrl/agent.py:442-468): get_obj_critic_raw (:519-527 -- the gather of
+ * buffer.sample_batch's rows (replay.py:344-351), act.get_action_logprob(next_s) on the ONLINE actor (net.py:207-239),
+ * min(cri_target.get_q1_q2) + next_logprob * alpha, q_label, cri.get_q1_q2, SmoothL1 x 2), obj_critic.backward(),
+ * cri_optimizer.step(), soft_update(cri_target) on every step (:116-124), act.get_action_logprob(state), obj_alpha and
+ * alpha_optimizer.step() (:452-458), alpha = exp(alpha_log) (:461), obj_actor = -(min(cri_target.get_q1_q2(state, a_pg)) +
+ * logprob * alpha).mean() (:463), obj_actor.backward(), act_optimizer.step(): FOUR launches (csrc/sac_fused.hip) -- critic gradients
+ * (which also leave the batch sum of the policy-gradient sample's logprob), slab reduction + Adam + soft update of the critic +
+ * the temperature's Adam step, actor gradients (through BOTH heads of the target critic, min per sample, with the new alpha), slab
+ * reduction + Adam of the actor.  "logprob" is the reference's NEGATIVE log-density, kept with its sign.
+ * Nets: ActorSAC (net.py:175-239, non-DenseNet: D -> md ReLU -> md Hardswish -> md Hardswish, heads net_a_avg / net_a_std) and
+ * CriticTwin (net.py:305-332), action_dim 1, 1 <= D <= 7, md 64 | 128.  Both are read where they live: ONE flat float32 tensor per net
+ * in nn.Module parameter order, each tensor on a multiple of 4 floats, padding words zero (the actor: pime_sac_param_offsets, ten
+ * tensors; the critic: pime_td3_param_offsets(1, ...)).  The nets are described by pime_td3_net; the actor's `target` is unused and
+ * may be NULL (SAC has no actor target). */
+typedef struct pime_sac_temperature {
+    float* alpha_log;     /* [dev] float32[1]: the trainable log-temperature (agent.py:408), stepped by the critic's apply launch */
+    float* exp_avg;       /* [dev] float32[1]: its Adam moments; zero at construction */
+    float* exp_avg_sq;
+    float lr, beta1, beta2, eps;   /* the step number is the nets': pime_td3_net.step[0] + row + 1 */
+    float target_entropy;          /* agent.py:403,407: 1.0 * log(action_dim) = 0 */
+} pime_sac_temperature;
+typedef struct pime_sac_batch {
+    const float* state;        /* [dev] float32[rows, D]: replay states */
+    const float* other;        /* [dev] float32[rows, 3]: reward * scale, mask, action */
+    const int64_t* idx;        /* [dev] int64[table_rows, B]: the sampled rows of every optimizer step of an update */
+    const int64_t* nxt;        /* [dev] int64[table_rows, B]: their successors */
+    const float* noise_next;   /* [dev] float32[table_rows, B]: the standard normal draws of the next-state sample (the first */
+    const float* noise_pg;     /*   torch.randn_like of an iteration) and of the policy-gradient sample (the second); or BOTH NULL: drawn
+                                *   in the kernels -- Philox4x32-10 keyed by noise_seed, counter (batch position, noise_epoch, table row,
+                                *   stream 4 / 5), Box-Muller cosine branch in float32 */
+    int64_t row;               /* the table row of THIS optimizer step: a launch argument, so that an update's steps sit in one graph */
+    const int64_t* epoch;      /* [dev] int64[1] or NULL: added to noise_epoch (bumped by the host once per update) */
+    int32_t B;
+    uint64_t noise_seed;
+    uint32_t noise_epoch;
+} pime_sac_batch;
+int pime_sac_supported(int32_t D, int32_t action_dim, int32_t md);
+/* the actor's flat size, and offsets [10]: float offset of every parameter tensor (W, b pairs in module order) */
+int64_t pime_sac_param_floats(int32_t D, int32_t md);
+int pime_sac_param_offsets(int32_t D, int32_t md, int32_t* offsets);
+int64_t pime_sac_workspace_floats(int32_t D, int32_t md, int32_t B);
+/* phases: bit 0 = critic gradients, bit 1 = critic apply (slab reduction, Adam, soft update with tau, temperature step), bit 2 = actor
+ *         gradients, bit 3 = actor apply; 15 = the whole step.  Launches of consecutive calls sharing a workspace run in stream order.
+ * loss [dev] float32[8] or NULL: [0] += obj_actor, [1] += obj_critic, [2] += obj_alpha, [3] += alpha of this step (zero them per
+ *         update), [4..7] = this step's values.
+ * workspace [dev] float32[pime_sac_workspace_floats].  Two calls on the same inputs give the same bits (fixed summation order). */
+int pime_sac_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_sac_temperature* temp,
+                  const pime_sac_batch* batch, float tau, int32_t phases, float* workspace, float* loss, pime_stream stream);
 
 /* replaces: self.optimizer.step() of the single Adam over both nets (elegantrl/agent.py:565-566,656-657; no weight
  * decay, no amsgrad) when every parameter lives in ONE flat tensor.  All [dev] float32[n]; step [dev] float32[2], zeroed

@@ -41,7 +41,8 @@ class HipBackend:
             _warn_once(("fwd", type(module).__name__), f"pime_amd: no fused forward kernel for {type(module).__name__} "
                        f"(action_dim {getattr(module, 'action_dim', '?')}): using the torch module on the GPU")
             return None
-        md = module.net[0].out_features if kind != "modular_actor" else module.other_net[0].out_features
+        first = {"modular_actor": "other_net", "sac_actor": "net_state"}.get(kind, "net")
+        md = getattr(module, first)[0].out_features
         if not ops.PackedMLP.supported(kind, module.state_dim, getattr(module, "integrator_dim", 0), md):
             _warn_once(("fwd", kind, md, module.state_dim),
                        f"pime_amd: no fused forward kernel for {kind} width {md} state_dim {module.state_dim} "
@@ -68,3 +69,13 @@ class HipBackend:
                        "1 <= state_dim <= 31, width 64 / 128 / 256, action_dim 1")
             return False
         return ops.FusedTD3(agent.act, agent.act_target, agent.cri, agent.cri_target, max_batch, agent.learning_rate)
+
+    def fused_sac(self, agent, max_batch):
+        """ops.FusedSAC for an SAC agent's three nets and temperature, or False when their shape has no fused optimizer step."""
+        if not ops.FusedSAC.supported(agent.act, agent.cri):
+            _warn_once(("sac", type(agent.act).__name__, getattr(agent.act, "state_dim", None)),
+                       f"pime_amd: no fused SAC step for ({type(agent.act).__name__}, {type(agent.cri).__name__}) at these shapes; "
+                       "update_net runs through torch autograd on the GPU (several times slower).  Supported: ActorSAC + CriticTwin, "
+                       "1 <= state_dim <= 7, width 64 / 128, action_dim 1")
+            return False
+        return ops.FusedSAC(agent.act, agent.cri, agent.cri_target, agent.alpha_log, max_batch, agent.learning_rate)

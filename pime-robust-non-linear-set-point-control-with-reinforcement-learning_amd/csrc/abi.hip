@@ -13,6 +13,7 @@
 #include "rollout_eval.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
+#include "sac.hpp"
 
 namespace pime {
 
@@ -125,6 +126,10 @@ int64_t td3_workspace_floats(int, int, int);
 bool td3_supported(int, int, int);
 int launch_td3_grad(bool, int, const Td3GradArgs&, int, hipStream_t);
 int launch_td3_apply(const Td3ApplyArgs&, hipStream_t);
+// sac_fused.hip
+bool sac_supported(int, int, int);
+int64_t sac_workspace_floats(int, int, int);
+int launch_sac_grad(bool, int, const SacGradArgs&, int, hipStream_t);
 
 }  // namespace pime
 
@@ -750,7 +755,7 @@ int pime_rollout_eval_supported(const pime_env* e, int32_t kind, int32_t md) {
         return (md == 256 && kind == PIME_MLP_PLAIN_ACTOR && e->cfg.state_mode == PIME_STATE_MIXED && (S == 1 || S == 4 || S == 10)) ? 2 : 0;
     }   // (2: returns and trace, no set-point schedule -- the protocols of utils/test.py are written for the Integrator observation)
     if (kind == -1) return 1;                                            // the prior controller alone
-    if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR) return 0;
+    if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR) return 0;
     if (md == 256) return e->cfg.state_mode == PIME_STATE_MIXED ? 1 : 0;   // the streamed kernel's evaluation mode (float32 state)
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
@@ -792,17 +797,20 @@ int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed
                                  trace, stream);
 }
 
-int pime_rollout_offpolicy_supported(const pime_env* e, int32_t md) {
+static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {
     if (e == nullptr || e->cfg.state_mode != PIME_STATE_MIXED) return 0;
     if (e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0) return 0;
-    return (md == 64 || md == 128) && !family16(PIME_MLP_CRITIC, md) ? 1 : 0;
+    return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
+int pime_rollout_offpolicy_supported(const pime_env* e, int32_t md) { return offpolicy_supported(e, PIME_MLP_CRITIC, md); }
+int pime_rollout_offpolicy_sac_supported(const pime_env* e, int32_t md) { return offpolicy_supported(e, PIME_MLP_SAC_ACTOR, md); }
 
-int pime_rollout_offpolicy(pime_env* e, int32_t md, const float* packed_actor, const double* priorK, float explore_noise,
-                           float gamma, float reward_scale, int32_t n_steps, uint64_t noise_seed, uint32_t noise_epoch,
-                           float* obs, float* ring_state, float* ring_other, int32_t slot0, int32_t slots, pime_stream stream) {
+static int rollout_offpolicy_common(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                                    float explore_noise, float gamma, float reward_scale, int32_t n_steps, uint64_t noise_seed,
+                                    uint32_t noise_epoch, float* obs, float* ring_state, float* ring_other, int32_t slot0, int32_t slots,
+                                    pime_stream stream) {
     PIME_REQUIRE(e != nullptr, "NULL env handle");
-    PIME_REQUIRE(pime_rollout_offpolicy_supported(e, md), "pime_rollout_offpolicy: not served for this handle / width %d", md);
+    PIME_REQUIRE(offpolicy_supported(e, kind, md), "pime_rollout_offpolicy: not served for this handle / width %d", md);
     PIME_REQUIRE(packed_actor && priorK && obs && ring_state && ring_other && n_steps >= 1 && slots >= 2 && slot0 >= 0 &&
                  slot0 < slots && n_steps <= slots, "pime_rollout_offpolicy: bad arguments");
     if (!e->was_reset) { set_error("pime_rollout_offpolicy before pime_env_reset"); return PIME_ERR_STATE; }
@@ -813,12 +821,27 @@ int pime_rollout_offpolicy(pime_env* e, int32_t md, const float* packed_actor, c
     a.env_offset = e->cfg.env_offset;
     if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 1; a.st = e->ph32; }
     else { a.wp = e->wt; a.wp.auto_reset = 1; a.wst = e->wt32; }
+    a.kind = kind;
     a.img = packed_actor;
     for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
     a.explore_noise = explore_noise; a.gamma = gamma; a.reward_scale = reward_scale;
     a.n_steps = n_steps; a.noise_seed = noise_seed; a.noise_epoch = noise_epoch;
     a.obs = obs; a.ring_state = ring_state; a.ring_other = ring_other; a.slot0 = slot0; a.slots = slots;
     return launch_rollout_offpolicy(md, a, static_cast<hipStream_t>(stream));
+}
+
+int pime_rollout_offpolicy(pime_env* e, int32_t md, const float* packed_actor, const double* priorK, float explore_noise,
+                           float gamma, float reward_scale, int32_t n_steps, uint64_t noise_seed, uint32_t noise_epoch,
+                           float* obs, float* ring_state, float* ring_other, int32_t slot0, int32_t slots, pime_stream stream) {
+    return rollout_offpolicy_common(e, PIME_MLP_CRITIC, md, packed_actor, priorK, explore_noise, gamma, reward_scale, n_steps, noise_seed,
+                                    noise_epoch, obs, ring_state, ring_other, slot0, slots, stream);
+}
+
+int pime_rollout_offpolicy_sac(pime_env* e, int32_t md, const float* packed_actor, const double* priorK, float gamma, float reward_scale,
+                               int32_t n_steps, uint64_t noise_seed, uint32_t noise_epoch, float* obs, float* ring_state,
+                               float* ring_other, int32_t slot0, int32_t slots, pime_stream stream) {
+    return rollout_offpolicy_common(e, PIME_MLP_SAC_ACTOR, md, packed_actor, priorK, 0.f, gamma, reward_scale, n_steps, noise_seed,
+                                    noise_epoch, obs, ring_state, ring_other, slot0, slots, stream);
 }
 
 int pime_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
@@ -1203,7 +1226,7 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
         a.param = n->param; a.target = n->target; a.grad = n->grad; a.exp_avg = n->exp_avg; a.exp_avg_sq = n->exp_avg_sq; a.step = n->step;
         a.lr = n->lr; a.b1 = n->beta1; a.b2 = n->beta2; a.eps = n->eps; a.tau = tau;
         a.row = (long long)b->row; a.soft = soft;
-        a.loss = loss; a.loss_slot = slot; a.inv_B = 1.0f / (float)b->B;
+        a.loss = loss; a.loss_slot = slot; a.inv_B = 1.0f / (float)b->B; a.loss_last = 2;
         return launch_td3_apply(a, s);
     };
     if (phases & 1) {
@@ -1222,6 +1245,89 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
         if (int rc = apply(actor, LA, slab_a, 0, (phases & 64) ? 1 : 0)) return rc;
     if (phases & 128)
         if (int rc = apply(actor, LA, slab_a, 0, 2)) return rc;
+    return PIME_OK;
+}
+
+// -- fused SAC optimizer step (csrc/sac_fused.hip) -----------------------------------------------------------------------
+#define PIME_SAC_SERVED "served: action_dim 1, 1 <= state_dim <= %d, width 64 | 128"
+int pime_sac_supported(int32_t D, int32_t action_dim, int32_t md) { return sac_supported(D, action_dim, md) ? 1 : 0; }
+
+int64_t pime_sac_param_floats(int32_t D, int32_t md) {
+    if (!sac_supported(D, 1, md)) {
+        set_error("pime_sac_param_floats: unsupported actor (state_dim %d, width %d; " PIME_SAC_SERVED ")", D, md, kSacMaxD);
+        return -1;
+    }
+    return sac_actor_off(D, md).total;
+}
+
+int pime_sac_param_offsets(int32_t D, int32_t md, int32_t* offsets) {
+    PIME_REQUIRE(offsets && sac_supported(D, 1, md), "pime_sac_param_offsets: bad arguments (state_dim %d, width %d; " PIME_SAC_SERVED ")", D, md,
+                 kSacMaxD);
+    const SacActorOff o = sac_actor_off(D, md);
+    const int v[10] = {o.W1, o.b1, o.W2, o.b2, o.W3, o.b3, o.wa, o.ba, o.ws, o.bs};
+    for (int i = 0; i < 10; ++i) offsets[i] = v[i];
+    return PIME_OK;
+}
+
+int64_t pime_sac_workspace_floats(int32_t D, int32_t md, int32_t B) {
+    if (!sac_supported(D, 1, md) || B < 1) {
+        set_error("pime_sac_workspace_floats: unsupported shape (state_dim %d, width %d, batch %d; " PIME_SAC_SERVED ")", D, md, B, kSacMaxD);
+        return -1;
+    }
+    return sac_workspace_floats(D, md, B);
+}
+
+static int check_sac_net(const pime_td3_net* n, const char* what, bool need_target) {
+    PIME_REQUIRE(n && n->param && (n->target || !need_target) && n->grad && n->exp_avg && n->exp_avg_sq && n->step,
+                 "pime_sac_step: NULL pointer in the %s's pime_td3_net", what);
+    PIME_REQUIRE(n->lr > 0.f && n->beta1 >= 0.f && n->beta1 < 1.f && n->beta2 >= 0.f && n->beta2 < 1.f && n->eps > 0.f,
+                 "pime_sac_step: bad Adam constants for the %s", what);
+    return PIME_OK;
+}
+
+int pime_sac_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_sac_temperature* temp,
+                  const pime_sac_batch* b, float tau, int32_t phases, float* workspace, float* loss, pime_stream stream) {
+    PIME_REQUIRE(sac_supported(D, 1, md), "pime_sac_step: no kernel for state_dim %d width %d (" PIME_SAC_SERVED ")", D, md, kSacMaxD);
+    if (int rc = check_sac_net(actor, "actor", false)) return rc;
+    if (int rc = check_sac_net(critic, "critic", true)) return rc;
+    PIME_REQUIRE(temp && temp->alpha_log && temp->exp_avg && temp->exp_avg_sq, "pime_sac_step: NULL pointer in pime_sac_temperature");
+    PIME_REQUIRE(temp->lr > 0.f && temp->beta1 >= 0.f && temp->beta1 < 1.f && temp->beta2 >= 0.f && temp->beta2 < 1.f && temp->eps > 0.f,
+                 "pime_sac_step: bad Adam constants for the temperature");
+    PIME_REQUIRE(b && b->state && b->other && b->idx && b->nxt && b->B >= 1, "pime_sac_step: bad pime_sac_batch (NULL pointer or B < 1)");
+    PIME_REQUIRE((b->noise_next == nullptr) == (b->noise_pg == nullptr), "pime_sac_step: give both noise tables or neither");
+    PIME_REQUIRE(workspace != nullptr, "pime_sac_step: NULL workspace");
+    PIME_REQUIRE(b->row >= 0, "pime_sac_step: table row %lld", (long long)b->row);
+    PIME_REQUIRE(phases >= 1 && phases <= 15, "pime_sac_step: phases %d", phases);
+    PIME_REQUIRE(tau >= 0.f && tau <= 1.f, "pime_sac_step: tau %g", (double)tau);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = td3_grid(b->B), ngroups = (b->B + 15) / 16;
+    const Td3SlabLayout LA = sac_actor_slab(D, md), LC = td3_critic_slab(D, md);
+    float* const slab_c = workspace;
+    float* const slab_a = workspace + (size_t)grid * LC.stride;
+    float* const xg = slab_a + (size_t)grid * LA.stride;   // [B][8] gathered rows: written by the critic launch of a row, read by its actor launch
+    const SacBatch sb{b->state, b->other, b->idx, b->nxt, b->noise_next, b->noise_pg, (long long)b->row, b->epoch, b->B, b->noise_seed, b->noise_epoch};
+    auto apply = [&](const pime_td3_net* n, const Td3SlabLayout& L, const float* slab, int slot, bool is_critic) {
+        Td3ApplyArgs a{};
+        a.L = L; a.slab = slab; a.nslabs = grid; a.mode = 0;
+        a.param = n->param; a.target = n->target; a.grad = n->grad; a.exp_avg = n->exp_avg; a.exp_avg_sq = n->exp_avg_sq; a.step = n->step;
+        a.lr = n->lr; a.b1 = n->beta1; a.b2 = n->beta2; a.eps = n->eps; a.tau = tau;
+        a.row = (long long)b->row; a.soft = is_critic ? 1 : 0;   // the target critic follows on EVERY step; there is no actor target
+        a.loss = loss; a.loss_slot = slot; a.inv_B = 1.0f / (float)b->B; a.loss_last = 4;
+        if (is_critic) a.temp = {temp->alpha_log, temp->exp_avg, temp->exp_avg_sq, temp->lr, temp->beta1, temp->beta2, temp->eps, temp->target_entropy};
+        return launch_td3_apply(a, s);
+    };
+    if (phases & 1) {
+        SacGradArgs g{sb, D, actor->param, critic->param, critic->target, temp->alpha_log, slab_c, xg, LC.stride, ngroups};
+        if (int rc = launch_sac_grad(true, md, g, grid, s)) return rc;
+    }
+    if (phases & 2)
+        if (int rc = apply(critic, LC, slab_c, 1, true)) return rc;
+    if (phases & 4) {
+        SacGradArgs g{sb, D, actor->param, critic->target, nullptr, temp->alpha_log, slab_a, xg, LA.stride, ngroups};
+        if (int rc = launch_sac_grad(false, md, g, grid, s)) return rc;
+    }
+    if (phases & 8)
+        if (int rc = apply(actor, LA, slab_a, 0, false)) return rc;
     return PIME_OK;
 }
 

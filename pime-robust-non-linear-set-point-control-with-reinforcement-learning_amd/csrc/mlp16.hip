@@ -1918,6 +1918,7 @@ static bool forced16() {
     return forced;
 }
 bool family16(int kind, int md) {
+    if (kind == MLP_SAC_ACTOR) return false;            // ActorSAC: the LDS-resident images only (width 64 / 128)
     if (kind == MLP_MODULAR_ACTOR) return md == 256;   // the modular actor here only at the width the LDS-resident kernels cannot hold
     if (md == 256) return true;
     return forced16() && (md == 64 || md == 128);

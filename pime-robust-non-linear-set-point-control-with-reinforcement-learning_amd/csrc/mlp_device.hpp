@@ -8,7 +8,11 @@ namespace pime {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-enum { MLP_CRITIC = 0, MLP_PLAIN_ACTOR = 1, MLP_MODULAR_ACTOR = 2 };
+enum { MLP_CRITIC = 0, MLP_PLAIN_ACTOR = 1, MLP_MODULAR_ACTOR = 2, MLP_SAC_ACTOR = 3 };
+
+// activations of the two md x md layers' outputs in the four-layer kinds (the first layer's is A1 as well):
+//   CriticAdv / TD3 Actor: ReLU, ReLU;  ActorPPO: Tanh, Tanh;  ActorSAC (net.py:186-188): ReLU, then Hardswish, Hardswish
+template <int KIND> struct MlpActs { static constexpr int A1 = KIND == MLP_PLAIN_ACTOR ? 1 : 0, A2 = KIND == MLP_PLAIN_ACTOR ? 1 : (KIND == MLP_SAC_ACTOR ? 3 : 0); };
 
 // feature index inside a 32-wide tile held by accumulator register s of lane-half h (C/D map of 32x32 MFMA)
 __host__ __device__ __forceinline__ constexpr int feat32(int s, int h) { return (s & 3) + 8 * (s >> 2) + 4 * h; }
@@ -52,8 +56,12 @@ __host__ __device__ inline MlpLayout mlp_layout(int kind, int D, int Di, int md)
         seg(2, T * 32);
         seg(3, T * 16 * 64 * T);       // net.4
         seg(4, T * 32);
-        seg(5, T * 32);                // net.6 weights (HEAD)
+        seg(5, T * 32);                // net.6 weights (HEAD; ActorSAC: net_a_avg)
         seg(6, 4);                     // net.6 bias
+        if (kind == MLP_SAC_ACTOR) {   // the second head row: net_a_std (net.py:192)
+            seg(7, T * 32);
+            seg(8, 4);
+        }
     }
     L.total = o;
     return L;
@@ -122,6 +130,10 @@ __device__ inline void pack_forward_image(const PackArgs& a, float* __restrict__
         pack_vec(out + L.off[4], a.p[5], T, tid, nthr);
         pack_vec(out + L.off[5], a.p[6], T, tid, nthr);
         if (tid == 0) out[L.off[6]] = a.p[7][0];
+        if (a.kind == MLP_SAC_ACTOR) {
+            pack_vec(out + L.off[7], a.p[8], T, tid, nthr);
+            if (tid == 0) out[L.off[8]] = a.p[9][0];
+        }
     }
 }
 
@@ -176,6 +188,7 @@ template <int ACT>
 __device__ __forceinline__ float activate(float v) {
     if constexpr (ACT == 0) return v > 0.f ? v : 0.f;  // nn.ReLU
     else if constexpr (ACT == 1) return fast_tanh(v);   // nn.Tanh
+    else if constexpr (ACT == 3) return v * __builtin_amdgcn_fmed3f(v + 3.0f, 0.f, 6.0f) * (1.0f / 6.0f);   // nn.Hardswish
     else return v;                                      // identity (backward chains)
 }
 

@@ -65,13 +65,13 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_forward_kernel(const float* _
             PIME_NO_HOIST();
             y = layer_head<T>(lds + L.off[8], lds[L.off[9]], lane, n0);
         } else {
-            constexpr int ACT = KIND == MLP_CRITIC ? 0 : 1;
+            constexpr int A1 = MlpActs<KIND>::A1, A2 = MlpActs<KIND>::A2;   // (ActorSAC: the mean head, before its tanh)
             f32x16 a0[T], a1[T];
             layer_first<T, 2>(lds + L.off[0], xrow, D, h, a0);
             PIME_NO_HOIST();
-            layer_mfma_in<T, T, 2, ACT>(lds + L.off[1], lds + L.off[2], lane, a0, a1);
+            layer_mfma_in<T, T, 2, A1>(lds + L.off[1], lds + L.off[2], lane, a0, a1);
             PIME_NO_HOIST();
-            layer_mfma_in<T, T, ACT, ACT>(lds + L.off[3], lds + L.off[4], lane, a1, a0);
+            layer_mfma_in<T, T, A2, A2>(lds + L.off[3], lds + L.off[4], lane, a1, a0);
             PIME_NO_HOIST();
             y = layer_head<T>(lds + L.off[5], lds[L.off[6]], lane, a0);
         }
@@ -90,12 +90,14 @@ int64_t mlp_packed_floats(int kind, int D, int Di, int md) {
 }
 
 int mlp_check(int kind, int D, int Di, int md) {
-    PIME_REQUIRE(kind >= MLP_CRITIC && kind <= MLP_MODULAR_ACTOR, "mlp kind %d unknown", kind);
+    PIME_REQUIRE(kind >= MLP_CRITIC && kind <= MLP_SAC_ACTOR, "mlp kind %d unknown", kind);
     PIME_REQUIRE(D >= 1 && D <= kMaxObsDim, "state_dim %d out of range [1,%d]", D, kMaxObsDim);
     if (kind == MLP_MODULAR_ACTOR) {
         PIME_REQUIRE(Di >= 1 && Di < D, "integrator_dim %d must be in [1, state_dim)", Di);
         // 64 / 128: LDS-resident (this file, ppo_fused.hip); 256: the streamed 16x16x4 family (mlp16.hip: mlp16m_forward_kernel, ppo16m_kernel)
         PIME_REQUIRE(md == 64 || md == 128 || md == 256, "fused modular-actor kernels support width 64, 128 or 256, got %d", md);
+    } else if (kind == MLP_SAC_ACTOR) {
+        PIME_REQUIRE(md == 64 || md == 128, "the fused ActorSAC forward supports width 64 or 128, got %d", md);
     } else {
         // 64 / 128: the LDS-resident 32x32x2 family (this file, ppo_fused.hip); 256: the streamed 16x16x4 family (mlp16.hip)
         PIME_REQUIRE(md == 64 || md == 128 || md == 256, "fused MLP kernels support width 64, 128 or 256, got %d", md);
@@ -106,7 +108,7 @@ int mlp_check(int kind, int D, int Di, int md) {
 int launch_mlp_pack(int kind, int D, int Di, int md, const float* const* params, float* packed, hipStream_t s) {
     if (int rc = mlp_check(kind, D, Di, md)) return rc;
     PackArgs a{};
-    const int np = kind == MLP_MODULAR_ACTOR ? 12 : 8;
+    const int np = kind == MLP_MODULAR_ACTOR ? 12 : (kind == MLP_SAC_ACTOR ? 10 : 8);
     for (int i = 0; i < np; ++i) {
         PIME_REQUIRE(params[i] != nullptr, "mlp params[%d] is NULL", i);
         a.p[i] = params[i];
@@ -148,6 +150,7 @@ int launch_mlp_forward(int kind, const float* x, int M, int D, int Di, int md, c
     PIME_FWD(2, MLP_CRITIC) PIME_FWD(4, MLP_CRITIC)
     PIME_FWD(2, MLP_PLAIN_ACTOR) PIME_FWD(4, MLP_PLAIN_ACTOR)
     PIME_FWD(2, MLP_MODULAR_ACTOR) PIME_FWD(4, MLP_MODULAR_ACTOR)
+    PIME_FWD(2, MLP_SAC_ACTOR) PIME_FWD(4, MLP_SAC_ACTOR)
 #undef PIME_FWD
     set_error("no fused MLP instantiation for kind %d width %d", kind, md);
     return PIME_ERR_ARG;

@@ -138,6 +138,7 @@ int launch_rollout_eval(int kind, int md, const EvalArgs<S>& a, hipStream_t s) {
     PIME_EV(0, -1, 0) PIME_EV(0, -1, 1)
     PIME_EV(4, MLP_MODULAR_ACTOR, 0) PIME_EV(2, MLP_MODULAR_ACTOR, 0) PIME_EV(4, MLP_PLAIN_ACTOR, 0) PIME_EV(2, MLP_PLAIN_ACTOR, 0)
     PIME_EV(4, MLP_MODULAR_ACTOR, 1) PIME_EV(2, MLP_MODULAR_ACTOR, 1) PIME_EV(4, MLP_PLAIN_ACTOR, 1) PIME_EV(2, MLP_PLAIN_ACTOR, 1)
+    PIME_EV(4, MLP_SAC_ACTOR, 0) PIME_EV(2, MLP_SAC_ACTOR, 0) PIME_EV(4, MLP_SAC_ACTOR, 1) PIME_EV(2, MLP_SAC_ACTOR, 1)   // tanh(net_a_avg): ActorSAC.forward
 #undef PIME_EV
     set_error("no fused evaluation instantiation for env %d kind %d width %d", a.env, kind, md);
     return PIME_ERR_ARG;

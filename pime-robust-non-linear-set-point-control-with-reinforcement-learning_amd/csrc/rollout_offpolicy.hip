@@ -10,6 +10,8 @@
 // round 2 (42 ms per 200 lock-steps of 4 096 lanes, profiles/r03d_td3_kstats.txt).
 // Policy forward = rollout_policy.hpp with the TD3 Actor's activations (three ReLU layers: CriticAdv's image kind); env arithmetic
 // = env_device.hpp; exploration noise = the rollout kernel's Philox stream 2.
+// KIND = MLP_SAC_ACTOR: AgentSAC's exploration (agent.py:425-431 with net.py:201-205) -- the stochastic actor's two heads from the
+// same forward, a = tanh(avg + exp(clamp(log_std, -20, 2)) * eps) with eps the same stream-2 draw; everything else is shared.
 #include <cstdlib>
 #include "env_device.hpp"
 #include "rollout_offpolicy.hpp"
@@ -21,11 +23,11 @@ constexpr uint32_t STREAM_EXPLORE_OFFPOLICY = 2;   // = rollout.hip's STREAM_EXP
 constexpr int kOffThreads = 256;   // four waves of 16 lanes: one per SIMD (16-lane tiles, rollout_policy.hpp: policy_forward16)
 
 // QUAD (launches of <= 4 096 lanes): one 16-lane tile per workgroup, split over its four waves (rollout_policy.hpp: policy_forward16q)
-template <int T, int ENV, bool QUAD>
+template <int T, int ENV, bool QUAD, int KIND>
 __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolicyArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int D = ENV == 0 ? 3 : 4;
-    const MlpLayout L = mlp_layout(MLP_CRITIC, D, 0, T * 32);
+    const MlpLayout L = mlp_layout(KIND, D, 0, T * 32);
     stage_image(lds, a.img, L.total / 4);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -46,13 +48,15 @@ __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolic
     int slot = a.slot0;
     for (int t = 0; t < a.n_steps; ++t) {
         PIME_NO_HOIST();
-        float mean;
-        if constexpr (QUAD) mean = policy_forward16q<T, MLP_CRITIC, D, 0>(lds, lds + L.total, L, obs, lane, wave);
-        else mean = policy_forward16<T, MLP_CRITIC, D, 0>(lds, L, obs, lane);
+        float mean, raw = 0.f;
+        if constexpr (QUAD) mean = policy_forward16q<T, KIND, D, 0>(lds, lds + L.total, L, obs, lane, wave, &raw);
+        else mean = policy_forward16<T, KIND, D, 0>(lds, L, obs, lane, &raw);
         double ua, ub;
         philox_pair(a.noise_seed, gid, a.noise_epoch, (uint32_t)t, STREAM_EXPLORE_OFFPOLICY, ua, ub);
         const float eps = (float)(sqrt(-2.0 * log(1.0 - ua)) * cos(6.283185307179586476925286766559 * ub));
-        const float act = clip(tanhf(mean) + eps * a.explore_noise, -1.0f, 1.0f);   // agent.py:303-305
+        float act;
+        if constexpr (KIND == MLP_SAC_ACTOR) act = tanhf(mean + expf(clip(raw, -20.0f, 2.0f)) * eps);   // net.py:201-205
+        else act = clip(tanhf(mean) + eps * a.explore_noise, -1.0f, 1.0f);                              // agent.py:303-305
         double a_env = (double)act;
 #pragma unroll
         for (int j = 0; j < D; ++j) a_env += (double)obs[j] * a.K.k[j];
@@ -91,29 +95,36 @@ __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolic
 
 int mlp_check(int kind, int D, int Di, int md);
 
-template <int T, int ENV, bool QUAD>
+template <int T, int ENV, bool QUAD, int KIND>
 static int launch_off_q(const OffPolicyArgs& a, hipStream_t s) {
-    const size_t lds_bytes = ((size_t)mlp_layout(MLP_CRITIC, ENV == 0 ? 3 : 4, 0, T * 32).total + (QUAD ? quad_xchg_floats<T>() : 0)) * sizeof(float);
+    const size_t lds_bytes = ((size_t)mlp_layout(KIND, ENV == 0 ? 3 : 4, 0, T * 32).total + (QUAD ? quad_xchg_floats<T>() : 0)) * sizeof(float);
     static LdsLimit lds_limit;  // per instantiation
-    PIME_RAISE_LDS(lds_limit, (rollout_offpolicy_kernel<T, ENV, QUAD>), 160 * 1024);
+    PIME_RAISE_LDS(lds_limit, (rollout_offpolicy_kernel<T, ENV, QUAD, KIND>), 160 * 1024);
     const int per_wg = QUAD ? 16 : kOffThreads / 64 * 16;
-    hipLaunchKernelGGL((rollout_offpolicy_kernel<T, ENV, QUAD>), dim3((a.n + per_wg - 1) / per_wg), dim3(kOffThreads), lds_bytes, s, a);
+    hipLaunchKernelGGL((rollout_offpolicy_kernel<T, ENV, QUAD, KIND>), dim3((a.n + per_wg - 1) / per_wg), dim3(kOffThreads), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
-template <int T, int ENV>
+template <int T, int ENV, int KIND>
 static int launch_off_t(const OffPolicyArgs& a, hipStream_t s) {
     bool quad = a.n <= 4096;   // at most one tile per compute unit: split it over the workgroup's waves (csrc/rollout.hip: tiling)
     if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
-    return quad ? launch_off_q<T, ENV, true>(a, s) : launch_off_q<T, ENV, false>(a, s);
+    return quad ? launch_off_q<T, ENV, true, KIND>(a, s) : launch_off_q<T, ENV, false, KIND>(a, s);
 }
 
 int launch_rollout_offpolicy(int md, const OffPolicyArgs& a, hipStream_t s) {
-    if (int rc = mlp_check(MLP_CRITIC, a.env == 0 ? 3 : 4, 0, md)) return rc;
-    if (md == 128 && a.env == 0) return launch_off_t<4, 0>(a, s);
-    if (md == 128 && a.env == 1) return launch_off_t<4, 1>(a, s);
-    if (md == 64 && a.env == 0) return launch_off_t<2, 0>(a, s);
-    if (md == 64 && a.env == 1) return launch_off_t<2, 1>(a, s);
+    if (int rc = mlp_check(a.kind, a.env == 0 ? 3 : 4, 0, md)) return rc;
+    if (a.kind == MLP_SAC_ACTOR) {
+        if (md == 128 && a.env == 0) return launch_off_t<4, 0, MLP_SAC_ACTOR>(a, s);
+        if (md == 128 && a.env == 1) return launch_off_t<4, 1, MLP_SAC_ACTOR>(a, s);
+        if (md == 64 && a.env == 0) return launch_off_t<2, 0, MLP_SAC_ACTOR>(a, s);
+        if (md == 64 && a.env == 1) return launch_off_t<2, 1, MLP_SAC_ACTOR>(a, s);
+    } else if (a.kind == MLP_CRITIC) {
+        if (md == 128 && a.env == 0) return launch_off_t<4, 0, MLP_CRITIC>(a, s);
+        if (md == 128 && a.env == 1) return launch_off_t<4, 1, MLP_CRITIC>(a, s);
+        if (md == 64 && a.env == 0) return launch_off_t<2, 0, MLP_CRITIC>(a, s);
+        if (md == 64 && a.env == 1) return launch_off_t<2, 1, MLP_CRITIC>(a, s);
+    }
     set_error("no fused off-policy rollout instantiation for env %d width %d", a.env, md);
     return PIME_ERR_ARG;
 }

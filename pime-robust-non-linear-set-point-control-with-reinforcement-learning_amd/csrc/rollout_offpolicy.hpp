@@ -11,7 +11,8 @@ struct OffPolicyArgs {
     PhPtrs<float> st;
     WtParams wp;
     WtPtrs<float> wst;
-    const float* img;        // packed deterministic actor: pime_mlp_pack image of kind PIME_MLP_CRITIC (same shape and ReLUs)
+    int kind;                // MLP_CRITIC: the TD3 Actor (deterministic + clipped noise); MLP_SAC_ACTOR: ActorSAC (re-parameterised sample)
+    const float* img;        // packed actor: pime_mlp_pack image of that kind
     PriorK K;                // prior-controller gain of the residual composition; zeros for plain TD3
     float explore_noise, gamma, reward_scale;
     int n_steps;

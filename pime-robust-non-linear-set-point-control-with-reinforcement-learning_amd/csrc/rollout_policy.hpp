@@ -62,13 +62,13 @@ __device__ __forceinline__ float policy_forward(const float* __restrict__ lds, c
         PIME_NO_HOIST();
         return layer_head<T>(lds + L.off[8], lds[L.off[9]], lane, n0);
     } else {   // plain actor (Tanh) or the TD3 Actor, whose shape and ReLUs are CriticAdv's (net.py:96-110 / :274-277): KIND MLP_CRITIC
-        constexpr int ACT = KIND == MLP_CRITIC ? 0 : 1;
+        constexpr int A1 = MlpActs<KIND>::A1, A2 = MlpActs<KIND>::A2;
         f32x16 a0[T], a1[T];
         layer_first_regs<T, 2, D>(lds + L.off[0], obs, h, a0);
         PIME_NO_HOIST();
-        layer_mfma_in<T, T, 2, ACT>(lds + L.off[1], lds + L.off[2], lane, a0, a1);
+        layer_mfma_in<T, T, 2, A1>(lds + L.off[1], lds + L.off[2], lane, a0, a1);
         PIME_NO_HOIST();
-        layer_mfma_in<T, T, ACT, ACT>(lds + L.off[3], lds + L.off[4], lane, a1, a0);
+        layer_mfma_in<T, T, A2, A2>(lds + L.off[3], lds + L.off[4], lane, a1, a0);
         PIME_NO_HOIST();
         return layer_head<T>(lds + L.off[5], lds[L.off[6]], lane, a0);
     }
@@ -157,7 +157,8 @@ __device__ __forceinline__ float head16_on32(const float* __restrict__ w, float 
 
 // a_avg for this lane's sample (lane & 15; the four lane groups carry the same 16 samples)
 template <int T, int KIND, int D, int Di>
-__device__ __forceinline__ float policy_forward16(const float* __restrict__ lds, const MlpLayout& L, const float (&obs)[D], int lane) {
+__device__ __forceinline__ float policy_forward16(const float* __restrict__ lds, const MlpLayout& L, const float (&obs)[D], int lane,
+                                                  float* second = nullptr) {   // ActorSAC: the log-std head's output
     constexpr int Do = D - Di, H = T / 2 > 0 ? T / 2 : 1;
     static_assert(T >= 2 && T % 2 == 0, "whole 32-feature tiles in both towers");
     const int g = lane >> 4;
@@ -182,14 +183,17 @@ __device__ __forceinline__ float policy_forward16(const float* __restrict__ lds,
         PIME_NO_HOIST();
         return head16_on32<T>(lds + L.off[8], lds[L.off[9]], lane, n0);
     } else {
-        constexpr int ACT = KIND == MLP_CRITIC ? 0 : 1;
+        constexpr int A1 = MlpActs<KIND>::A1, A2 = MlpActs<KIND>::A2;
         f32x4_t a0[T * 2], a1[T * 2];
-        first16_on32<T, ACT, D>(lds + L.off[0], obs, g, a0);
+        first16_on32<T, A1, D>(lds + L.off[0], obs, g, a0);
         PIME_NO_HOIST();
-        layer16_on32<T, T, ACT>(lds + L.off[1], lds + L.off[2], lane, a0, a1);
+        layer16_on32<T, T, A2>(lds + L.off[1], lds + L.off[2], lane, a0, a1);
         PIME_NO_HOIST();
-        layer16_on32<T, T, ACT>(lds + L.off[3], lds + L.off[4], lane, a1, a0);
+        layer16_on32<T, T, A2>(lds + L.off[3], lds + L.off[4], lane, a1, a0);
         PIME_NO_HOIST();
+        if constexpr (KIND == MLP_SAC_ACTOR) {   // net_a_std, for the callers that sample (evaluation takes the mean alone)
+            if (second) *second = head16_on32<T>(lds + L.off[7], lds[L.off[8]], lane, a0);
+        }
         return head16_on32<T>(lds + L.off[5], lds[L.off[6]], lane, a0);
     }
 }
@@ -247,7 +251,7 @@ __device__ __forceinline__ void xchg_write(float* __restrict__ buf, int lane, in
 // a_avg for this lane's sample; every wave of the workgroup returns the same value.  xbuf: quad_xchg_floats<T>() floats of LDS.
 template <int T, int KIND, int D, int Di>
 __device__ __forceinline__ float policy_forward16q(const float* __restrict__ lds, float* __restrict__ xbuf, const MlpLayout& L,
-                                                   const float (&obs)[D], int lane, int wave) {
+                                                   const float (&obs)[D], int lane, int wave, float* second = nullptr) {
     constexpr int Do = D - Di, H = T / 2 > 0 ? T / 2 : 1, NT = T * 2;   // NT tiles of 16 features per full-width activation
     static_assert(T == 4 || T == 2, "widths 128 and 64");
     constexpr int PER = NT / kQuadWaves;                                 // output tiles per wave of a full-width layer: 2 (1 at width 64)
@@ -291,25 +295,28 @@ __device__ __forceinline__ float policy_forward16q(const float* __restrict__ lds
         PIME_NO_HOIST();
         return head16_on32<T>(lds + L.off[8], lds[L.off[9]], lane, act);
     } else {
-        constexpr int ACT = KIND == MLP_CRITIC ? 0 : 1;
+        constexpr int A1 = MlpActs<KIND>::A1, A2 = MlpActs<KIND>::A2;
         f32x4_t o[PER];
         {
             f32x4_t a0[NT];
-            first16_on32<T, ACT, D>(lds + L.off[0], obs, g, a0);
+            first16_on32<T, A1, D>(lds + L.off[0], obs, g, a0);
             PIME_NO_HOIST();
-            layer16_on32_part<T, T, PER, ACT>(lds + L.off[1], lds + L.off[2], lane, wave * PER, a0, o);
+            layer16_on32_part<T, T, PER, A2>(lds + L.off[1], lds + L.off[2], lane, wave * PER, a0, o);
         }
 #pragma unroll
         for (int n = 0; n < PER; ++n) xchg_write(buf0, lane, wave * PER + n, o[n]);
         PIME_XCHG_BARRIER();
         xchg_read<NT>(buf0, lane, act);
         PIME_NO_HOIST();
-        layer16_on32_part<T, T, PER, ACT>(lds + L.off[3], lds + L.off[4], lane, wave * PER, act, o);
+        layer16_on32_part<T, T, PER, A2>(lds + L.off[3], lds + L.off[4], lane, wave * PER, act, o);
 #pragma unroll
         for (int n = 0; n < PER; ++n) xchg_write(buf1, lane, wave * PER + n, o[n]);
         PIME_XCHG_BARRIER();
         xchg_read<NT>(buf1, lane, act);
         PIME_NO_HOIST();
+        if constexpr (KIND == MLP_SAC_ACTOR) {   // net_a_std
+            if (second) *second = head16_on32<T>(lds + L.off[7], lds[L.off[8]], lane, act);
+        }
         return head16_on32<T>(lds + L.off[5], lds[L.off[6]], lane, act);
     }
 }

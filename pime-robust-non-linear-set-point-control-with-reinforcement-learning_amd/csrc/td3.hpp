@@ -51,7 +51,7 @@ struct Td3Seg {
     int n;                 // tb == 0: valid floats (the rest of the last word is padding)
 };
 struct Td3SlabLayout {
-    Td3Seg seg[8];
+    Td3Seg seg[10];        // (the SAC actor has ten tensors: sac.hpp)
     int nseg, scalar_off, stride;
 };
 __host__ __device__ inline Td3SlabLayout td3_actor_slab(int D, int md) {
@@ -113,9 +113,18 @@ struct Td3ApplyArgs {
     int soft;                  // 1: soft target update in this launch (delayed steps: row % update_freq == 0, agent.py:320-321,330-331)
     int mode;                  // 0: slab reduction + Adam (+ soft update); data-parallel callers split it around their all-reduce of `grad`:
                                // 1: slab reduction only (grad = the sum, loss words), 2: Adam (+ soft update) from `grad`, no slabs read
-    float* loss;               // [4]: [slot] += value of this step, [2 + slot] = value of this step
+    float* loss;               // [2 loss_last]: [slot] += value of this step, [loss_last + slot] = value of this step
     int loss_slot;             // 0: actor objective = -(q sum) / B, 1: critic objective = (loss sum) / B
     float inv_B;
+    int loss_last;             // 2 (TD3: two objectives), 4 (SAC: obj_actor, obj_critic, obj_alpha, alpha)
+    // SAC's critic apply only (alpha_log != NULL): the Adam step of the temperature rides on the scalar word's finisher.  Word [1] of
+    // the slabs' scalar slots sums the "logprob" of the policy-gradient sample over the batch (sac_critic_kernel):
+    //   grad = sum / B - target_entropy, obj_alpha = alpha_log * grad (agent.py:454), torch.optim.Adam on the one element with the
+    //   step number of this launch; loss[2] / loss[3] take obj_alpha and alpha = exp(alpha_log) AFTER the step (agent.py:461-462)
+    struct Temp {
+        float *alpha_log, *exp_avg, *exp_avg_sq;   // [dev] float32[1] each
+        float lr, b1, b2, eps, target_entropy;
+    } temp;
 };
 
 }  // namespace pime

@@ -1,5 +1,6 @@
 """Base agents: AgentBase, AgentPPO (on-policy, the residual agents' parent) and AgentTD3
-(interface of /root/reference/elegantrl/agent.py: AgentBase :15-124, AgentTD3 :276-394, AgentPPO :543-712).
+(interface of /root/reference/elegantrl/agent.py: AgentBase :15-124, AgentTD3 :276-394, AgentPPO :543-712; AgentSAC :397-478
+is in agent_sac.py and importable from here).
 
 What differs from the reference, by design:
   * `explore_env` understands vectorised envs (`env.num_envs`): all N lanes advance in lock-step, the policy
@@ -1036,3 +1037,11 @@ class AgentTD3(AgentBase):
             self.use_hip_graphs = False
             torch.cuda.synchronize(self.device)
             return {}
+
+
+def __getattr__(name):
+    """`AgentSAC` lives in agent_sac.py (which imports this module's AgentBase); the name resolves here as in the reference."""
+    if name == "AgentSAC":
+        from .agent_sac import AgentSAC
+        return AgentSAC
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

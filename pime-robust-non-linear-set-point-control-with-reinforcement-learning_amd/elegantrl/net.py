@@ -1,5 +1,5 @@
 """Base actor / critic MLPs (interface of /root/reference/elegantrl/net.py for the classes the residual path
-reaches: Actor :96-110, ActorPPO :113-172, CriticAdv :256-302, CriticTwin :305-332, layer_norm :617-619).
+reaches: Actor :96-110, ActorPPO :113-172, ActorSAC :175-239, CriticAdv :256-302, CriticTwin :305-332, layer_norm :617-619).
 
 state_dict key layout is the reference's (`net.0.weight`, `net.2.bias`, ..., `a_std_log`), so checkpoints written
 by either side load in the other (agent.py:86-114).  Only the vector-state (int state_dim) variants exist here:
@@ -98,6 +98,51 @@ class ActorPPO(nn.Module, GaussianHead):
 
     def frozen_transfer(self):
         _freeze_all_but_last(self.net)
+
+
+class ActorSAC(nn.Module):
+    """Stochastic policy of SAC (net.py:175-239, the non-DenseNet branch): D -> md ReLU -> md Hardswish -> md Hardswish, a mean
+    head and a log-std head; the action is the tanh of a re-parameterised normal sample.  `get_action_logprob` returns the
+    reference's "logprob", which is the NEGATIVE log-density of the squashed action (the agent adds `logprob * alpha`)."""
+    packed_kind = "sac_actor"
+
+    def __init__(self, mid_dim, state_dim, action_dim, if_use_dn=False):
+        super().__init__()
+        if if_use_dn or not isinstance(state_dim, int):
+            raise NotImplementedError("DenseNet / pixel branches are outside the control-env path")
+        self.state_dim, self.action_dim = state_dim, action_dim
+        self.net_state = nn.Sequential(nn.Linear(state_dim, mid_dim), nn.ReLU(),
+                                       nn.Linear(mid_dim, mid_dim), nn.Hardswish(),
+                                       nn.Linear(mid_dim, mid_dim), nn.Hardswish())
+        self.net_a_avg = nn.Linear(mid_dim, action_dim)   # the mean of the pre-tanh action
+        self.net_a_std = nn.Linear(mid_dim, action_dim)   # its log-std
+        self.sqrt_2pi_log = LOG_SQRT_2PI
+        layer_norm(self.net_a_avg, std=0.01)
+
+    def forward(self, state):
+        return self.net_a_avg(self.net_state(state)).tanh()
+
+    def get_action(self, state, noise=None):
+        t_tmp = self.net_state(state)
+        a_avg = self.net_a_avg(t_tmp)
+        a_std = self.net_a_std(t_tmp).clamp(-20, 2).exp()
+        if noise is None:
+            return torch.normal(a_avg, a_std).tanh()
+        return (a_avg + a_std * noise).tanh()
+
+    def get_action_logprob(self, state, noise=None):
+        t_tmp = self.net_state(state)
+        a_avg = self.net_a_avg(t_tmp)
+        a_std_log = self.net_a_std(t_tmp).clamp(-20, 2)
+        a_std = a_std_log.exp()
+        if noise is None:
+            noise = torch.randn_like(a_avg, requires_grad=True)
+        action = a_avg + a_std * noise
+        a_tan = action.tanh()
+        delta = ((a_avg - action) / a_std).pow(2).__mul__(0.5)
+        logprob = a_std_log + self.sqrt_2pi_log + delta
+        logprob = logprob + (-a_tan.pow(2) + 1.000001).log()
+        return a_tan, logprob.sum(1, keepdim=True)
 
 
 class CriticAdv(nn.Module):

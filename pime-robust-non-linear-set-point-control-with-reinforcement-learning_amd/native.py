@@ -16,12 +16,12 @@ LIB_PATH = _override or os.path.join(PACKAGE_DIR, "libpime_hip.so")
 CSRC = os.path.join(PACKAGE_DIR, "csrc")
 
 OK = 0
-ABI_VERSION = 20
+ABI_VERSION = 21
 ENV_PH, ENV_WT = 0, 1
 STATE_F64, STATE_MIXED, STATE_MIXED16 = 0, 1, 2
 REWARD = {"distance": 0, "square_distance": 1, "sparse": 2}
 F32, F64 = 0, 1
-MLP_CRITIC, MLP_PLAIN_ACTOR, MLP_MODULAR_ACTOR = 0, 1, 2
+MLP_CRITIC, MLP_PLAIN_ACTOR, MLP_MODULAR_ACTOR, MLP_SAC_ACTOR = 0, 1, 2, 3
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -69,6 +69,17 @@ class Td3Batch(C.Structure):
     _fields_ = [("state", C.c_void_p), ("other", C.c_void_p), ("idx", C.c_void_p), ("nxt", C.c_void_p), ("noise", C.c_void_p),
                 ("row", C.c_int64), ("epoch", C.c_void_p), ("B", C.c_int32), ("noise_seed", C.c_uint64), ("noise_epoch", C.c_uint32),
                 ("policy_noise", C.c_float), ("noise_clip", C.c_float)]
+
+
+class SacTemperature(C.Structure):
+    _fields_ = [("alpha_log", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("target_entropy", C.c_float)]
+
+
+class SacBatch(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("other", C.c_void_p), ("idx", C.c_void_p), ("nxt", C.c_void_p), ("noise_next", C.c_void_p),
+                ("noise_pg", C.c_void_p), ("row", C.c_int64), ("epoch", C.c_void_p), ("B", C.c_int32), ("noise_seed", C.c_uint64),
+                ("noise_epoch", C.c_uint32)]
 
 
 class EnvCfg(C.Structure):
@@ -135,6 +146,9 @@ _SIGNATURES = {
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy": (C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,
                                          _vp, _i32, _i32, _vp]),
+    "pime_rollout_offpolicy_sac_supported": (C.c_int, [_vp, _i32]),
+    "pime_rollout_offpolicy_sac": (C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _i32,
+                                             _i32, _vp]),
     "pime_oneshot_create": (_vp, [_i32, _i32, C.c_int64, _i32]),
     "pime_oneshot_export": (C.c_int, [_vp, _vp]),
     "pime_oneshot_connect": (C.c_int, [_vp, _vp]),
@@ -154,6 +168,11 @@ _SIGNATURES = {
     "pime_td3_param_offsets": (C.c_int, [_i32, _i32, _i32, _vp]),
     "pime_td3_workspace_floats": (C.c_int64, [_i32, _i32, _i32]),
     "pime_td3_step": (C.c_int, [_i32, _i32, _vp, _vp, _vp, C.c_float, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pime_sac_supported": (C.c_int, [_i32, _i32, _i32]),
+    "pime_sac_param_floats": (C.c_int64, [_i32, _i32]),
+    "pime_sac_param_offsets": (C.c_int, [_i32, _i32, _vp]),
+    "pime_sac_workspace_floats": (C.c_int64, [_i32, _i32, _i32]),
+    "pime_sac_step": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, C.c_float, _i32, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -9,11 +9,13 @@ import torch
 
 from . import native
 
-_KINDS = {"critic": native.MLP_CRITIC, "plain_actor": native.MLP_PLAIN_ACTOR, "modular_actor": native.MLP_MODULAR_ACTOR}
+_KINDS = {"critic": native.MLP_CRITIC, "plain_actor": native.MLP_PLAIN_ACTOR, "modular_actor": native.MLP_MODULAR_ACTOR,
+          "sac_actor": native.MLP_SAC_ACTOR}
 _PARAM_ORDER = {
     "critic": ["net.0", "net.2", "net.4", "net.6"],
     "plain_actor": ["net.0", "net.2", "net.4", "net.6"],
     "modular_actor": ["other_net.0", "other_net.2", "integrator_net.0", "integrator_net.2", "net.0", "net.2"],
+    "sac_actor": ["net_state.0", "net_state.2", "net_state.4", "net_a_avg", "net_a_std"],   # __call__: the mean head before its tanh
 }
 
 
@@ -522,4 +524,137 @@ class FusedTD3:
                                                     native.ptr(self.workspace), native.ptr(self.loss), _stream(buf_state)),
                          "pime_td3_step")
         if advance and phases & (8 | 128):
+            self.row += 1
+
+
+_SAC_ACTOR_PARAMS = ["net_state.0.weight", "net_state.0.bias", "net_state.2.weight", "net_state.2.bias", "net_state.4.weight",
+                     "net_state.4.bias", "net_a_avg.weight", "net_a_avg.bias", "net_a_std.weight", "net_a_std.bias"]
+
+
+class FusedSAC:
+    """One SAC optimizer step -- critic objective with the entropy term, its gradients, Adam, soft update, the temperature's
+    objective and Adam step, actor objective through the target critic's twin heads, its gradients, Adam
+    (elegantrl/agent.py:442-468 of the reference) -- as four HIP launches (csrc/sac_fused.hip, `pime_sac_step`).
+
+    The three nets (actor, critic, critic target) are re-homed into ONE flat float32 tensor each, as FusedTD3 does
+    (`pime_sac_param_offsets` for the actor, `pime_td3_param_offsets` for the critics): every nn.Parameter becomes a view into its
+    net's flat tensor and every online parameter's .grad a view into the flat gradient the step writes.  The temperature is the
+    agent's own one-element `alpha_log` tensor, stepped on the device."""
+
+    def __init__(self, act, cri, cri_target, alpha_log, max_batch, lr, lr_alpha=None, betas=(0.9, 0.999), eps=1e-8):
+        dev = next(cri.parameters()).device
+        _need_cuda(next(cri.parameters()), alpha_log)
+        L = native.lib()
+        self.device = dev
+        self.D, self.md = int(act.state_dim), int(act.net_state[0].out_features)
+        if not self.supported(act, cri):
+            raise native.PimeError(f"fused SAC step unsupported for state_dim {self.D} width {self.md}: {native.last_error()}")
+        self.max_batch = int(max_batch)
+        self.nets = (act, cri, cri_target)
+        self.alpha_log = alpha_log
+        self.lr, self.lr_alpha, self.betas, self.eps = float(lr), float(lr if lr_alpha is None else lr_alpha), betas, float(eps)
+        f32 = dict(dtype=torch.float32, device=dev)
+
+        def rehome(module, names, n, offs):
+            flat = torch.zeros(n, **f32)
+            sd = dict(module.named_parameters())
+            with torch.no_grad():
+                for name, off in zip(names, offs):
+                    p = sd[name]
+                    assert p.dtype == torch.float32
+                    flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
+                    p.data = flat[off:off + p.numel()].view_as(p)
+            return flat, list(offs)
+
+        a_offs, c_offs = (C.c_int32 * 10)(), (C.c_int32 * 8)()
+        native.check(L.pime_sac_param_offsets(self.D, self.md, a_offs), "pime_sac_param_offsets")
+        native.check(L.pime_td3_param_offsets(1, self.D, self.md, c_offs), "pime_td3_param_offsets")
+        n_a, n_c = L.pime_sac_param_floats(self.D, self.md), L.pime_td3_param_floats(1, self.D, self.md)
+        self.act_flat, self.act_off = rehome(act, _SAC_ACTOR_PARAMS, n_a, a_offs)
+        self.cri_flat, self.cri_off = rehome(cri, _TD3_CRITIC_PARAMS, n_c, c_offs)
+        self.cri_t_flat, _ = rehome(cri_target, _TD3_CRITIC_PARAMS, n_c, c_offs)
+        self.act_grad, self.cri_grad = torch.zeros_like(self.act_flat), torch.zeros_like(self.cri_flat)
+        for module, names, offs, g in ((act, _SAC_ACTOR_PARAMS, self.act_off, self.act_grad),
+                                      (cri, _TD3_CRITIC_PARAMS, self.cri_off, self.cri_grad)):
+            sd = dict(module.named_parameters())
+            for name, off in zip(names, offs):
+                p = sd[name]
+                p.grad = g[off:off + p.numel()].view_as(p)
+        self.state = {k: torch.zeros_like(t) for k, t in (("act_m", self.act_flat), ("act_v", self.act_flat),
+                                                          ("cri_m", self.cri_flat), ("cri_v", self.cri_flat))}
+        self.state["alpha_m"], self.state["alpha_v"] = torch.zeros(1, **f32), torch.zeros(1, **f32)
+        self.steps_done = torch.zeros(1, **f32)   # optimizer steps applied before table row 0 of the running update (all three step together)
+        self.workspace = None
+        self.ensure_batch(self.max_batch)
+        self.loss = torch.zeros(8, **f32)          # sums of obj_actor, obj_critic, obj_alpha, alpha over the update; [4..7] the last step's
+        self.epoch = torch.zeros(1, dtype=torch.int64, device=dev)    # added to the noise epoch: bumped once per update
+        self.row = 0                                                   # table row of the next step (host side: a launch argument)
+        s = self.state
+        self._actor = native.Td3Net(param=self.act_flat.data_ptr(), target=None, grad=self.act_grad.data_ptr(),
+                                    exp_avg=s["act_m"].data_ptr(), exp_avg_sq=s["act_v"].data_ptr(), step=self.steps_done.data_ptr(),
+                                    lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
+        self._critic = native.Td3Net(param=self.cri_flat.data_ptr(), target=self.cri_t_flat.data_ptr(), grad=self.cri_grad.data_ptr(),
+                                     exp_avg=s["cri_m"].data_ptr(), exp_avg_sq=s["cri_v"].data_ptr(), step=self.steps_done.data_ptr(),
+                                     lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
+
+    def begin_update(self):
+        """Table row 0 again: the steps of the previous update move into the optimizers' step base, the noise epoch advances."""
+        if self.row:
+            self.steps_done += float(self.row)
+        self.row = 0
+        self.epoch += 1
+
+    def ensure_batch(self, batch):
+        """Workspace (one partial-gradient slab per workgroup) for minibatches of up to `batch` rows; the optimizer state stays."""
+        if self.workspace is None or batch > self.max_batch:
+            self.max_batch = max(int(batch), self.max_batch)
+            n_ws = native.lib().pime_sac_workspace_floats(self.D, self.md, self.max_batch)
+            if n_ws <= 0:
+                raise native.PimeError(f"fused SAC step: {native.last_error()}")
+            self.workspace = torch.empty(n_ws, dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def supported(act, cri):
+        try:
+            if type(act).__name__ != "ActorSAC" or type(cri).__name__ != "CriticTwin":
+                return False
+            md = act.net_state[0].out_features
+            if cri.net_sa[0].out_features != md or cri.net_sa[0].in_features != act.state_dim + 1 or len(act.net_state) != 6:
+                return False
+            return bool(native.lib().pime_sac_supported(int(act.state_dim), int(getattr(act, "action_dim", 1)), int(md))) \
+                and next(cri.parameters()).is_cuda
+        except Exception:
+            return False
+
+    def wraps(self, agent):
+        return (agent.act, agent.cri, agent.cri_target) == self.nets and agent.alpha_log is self.alpha_log and \
+            agent.act.net_state[0].weight.data_ptr() == self.act_flat.data_ptr()
+
+    def step(self, buf_state, buf_other, idx, nxt, noise_next, noise_pg, tau, target_entropy, noise_seed=0, noise_epoch=0, phases=15,
+             row=None):
+        """One optimizer step on table row `row` (default: self.row, which then advances) of idx / nxt (int64 [rows, B]) and the two
+        noise tables (float32 [rows, B], or both None: Philox in the kernels).  phases: bit 0 critic gradients, 1 critic apply +
+        temperature step, 2 actor gradients, 3 actor apply (include/pime_hip.h)."""
+        _need_cuda(buf_state, buf_other, idx, nxt)
+        B = idx.shape[-1]
+        advance = row is None
+        row = self.row if advance else int(row)
+        assert idx.dim() == 2 and 0 <= row < idx.shape[0], (row, idx.shape)
+        assert B <= self.max_batch and idx.dtype == nxt.dtype == torch.int64 and idx.is_contiguous() and nxt.is_contiguous()
+        assert buf_state.dtype == buf_other.dtype == torch.float32 and buf_state.is_contiguous() and buf_other.is_contiguous()
+        assert buf_state.shape[1] == self.D and buf_other.shape[1] == 3
+        for n in (noise_next, noise_pg):
+            assert n is None or (n.dtype == torch.float32 and n.is_contiguous() and n.shape == idx.shape)
+        temp = native.SacTemperature(alpha_log=self.alpha_log.data_ptr(), exp_avg=self.state["alpha_m"].data_ptr(),
+                                     exp_avg_sq=self.state["alpha_v"].data_ptr(), lr=self.lr_alpha, beta1=self.betas[0],
+                                     beta2=self.betas[1], eps=self.eps, target_entropy=float(target_entropy))
+        batch = native.SacBatch(state=buf_state.data_ptr(), other=buf_other.data_ptr(), idx=idx.data_ptr(), nxt=nxt.data_ptr(),
+                                noise_next=noise_next.data_ptr() if noise_next is not None else None,
+                                noise_pg=noise_pg.data_ptr() if noise_pg is not None else None, row=row, epoch=self.epoch.data_ptr(),
+                                B=B, noise_seed=int(noise_seed), noise_epoch=int(noise_epoch))
+        with torch.cuda.device(self.device):
+            native.check(native.lib().pime_sac_step(self.D, self.md, C.byref(self._actor), C.byref(self._critic), C.byref(temp),
+                                                    C.byref(batch), C.c_float(tau), int(phases), native.ptr(self.workspace),
+                                                    native.ptr(self.loss), _stream(buf_state)), "pime_sac_step")
+        if advance and phases & 8:
             self.row += 1

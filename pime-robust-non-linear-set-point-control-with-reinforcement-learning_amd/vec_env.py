@@ -362,8 +362,11 @@ class VecControlEnv:
 
     def offpolicy_rollout_supported(self, packed_actor):
         """Does the fused off-policy exploration kernel serve this env with this packed deterministic actor?"""
-        return (self.cfg.state_mode == native.STATE_MIXED and not self.draws.injects and packed_actor.kind == "critic"
-                and packed_actor.D == self.obs_dim and bool(self._lib.pime_rollout_offpolicy_supported(self._h, int(packed_actor.md))))
+        if self.cfg.state_mode != native.STATE_MIXED or self.draws.injects or packed_actor.D != self.obs_dim:
+            return False
+        if packed_actor.kind == "sac_actor":   # ActorSAC: the re-parameterised sample instead of mean + clipped noise
+            return bool(self._lib.pime_rollout_offpolicy_sac_supported(self._h, int(packed_actor.md)))
+        return packed_actor.kind == "critic" and bool(self._lib.pime_rollout_offpolicy_supported(self._h, int(packed_actor.md)))
 
     def rollout_offpolicy(self, packed_actor, priorK, explore_noise, gamma, reward_scale, n_steps, noise_seed, noise_epoch, obs,
                           ring_state, ring_other, slot0):
@@ -376,10 +379,16 @@ class VecControlEnv:
         assert ring_state.shape == (slots, self.num_envs, self.obs_dim) and ring_other.shape == (slots, self.num_envs, 3)
         k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
         assert k.size == self.obs_dim and self._was_reset
-        native.check(self._lib.pime_rollout_offpolicy(
-            self._h, int(packed_actor.md), native.ptr(packed_actor.packed), native.ptr(k), C.c_float(explore_noise), C.c_float(gamma),
-            C.c_float(reward_scale), int(n_steps), C.c_uint64(noise_seed), C.c_uint32(noise_epoch), native.ptr(obs),
-            native.ptr(ring_state), native.ptr(ring_other), int(slot0), int(slots), self._stream()), "pime_rollout_offpolicy")
+        if packed_actor.kind == "sac_actor":   # (explore_noise unused: the actor's own log-std head scales the draw)
+            native.check(self._lib.pime_rollout_offpolicy_sac(
+                self._h, int(packed_actor.md), native.ptr(packed_actor.packed), native.ptr(k), C.c_float(gamma), C.c_float(reward_scale),
+                int(n_steps), C.c_uint64(noise_seed), C.c_uint32(noise_epoch), native.ptr(obs), native.ptr(ring_state),
+                native.ptr(ring_other), int(slot0), int(slots), self._stream()), "pime_rollout_offpolicy_sac")
+        else:
+            native.check(self._lib.pime_rollout_offpolicy(
+                self._h, int(packed_actor.md), native.ptr(packed_actor.packed), native.ptr(k), C.c_float(explore_noise), C.c_float(gamma),
+                C.c_float(reward_scale), int(n_steps), C.c_uint64(noise_seed), C.c_uint32(noise_epoch), native.ptr(obs),
+                native.ptr(ring_state), native.ptr(ring_other), int(slot0), int(slots), self._stream()), "pime_rollout_offpolicy")
         if self._t_lanes is None:     # host mirror of the step counters: auto-reset wraps them at max_step
             self._t_all = (self._t_all + n_steps) % self.max_step
         else:
@@ -394,9 +403,10 @@ class VecControlEnv:
         if packed_actor is None:
             level = self._lib.pime_rollout_eval_supported(self._h, -1, 0)
         else:
-            if packed_actor.kind not in ("modular_actor", "plain_actor") or packed_actor.D != self.obs_dim:
+            if packed_actor.kind not in ("modular_actor", "plain_actor", "sac_actor") or packed_actor.D != self.obs_dim:
                 return False
-            kind = native.MLP_MODULAR_ACTOR if packed_actor.kind == "modular_actor" else native.MLP_PLAIN_ACTOR
+            kind = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR,
+                    "sac_actor": native.MLP_SAC_ACTOR}[packed_actor.kind]
             level = self._lib.pime_rollout_eval_supported(self._h, kind, int(packed_actor.md))
         return level == 1 or (level == 2 and not schedule)
 
@@ -414,7 +424,8 @@ class VecControlEnv:
         if packed_actor is None:
             kind, md, img = -1, 0, None
         else:
-            kind = native.MLP_MODULAR_ACTOR if packed_actor.kind == "modular_actor" else native.MLP_PLAIN_ACTOR
+            kind = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR,
+                    "sac_actor": native.MLP_SAC_ACTOR}[packed_actor.kind]
             md, img = int(packed_actor.md), packed_actor.packed
         native.check(self._lib.pime_rollout_eval(self._h, kind, md, native.ptr(img), native.ptr(k), int(n_steps), int(seg_len),
                                                  native.ptr(sp) if sp.size else None, int(sp.size), native.ptr(ret),
