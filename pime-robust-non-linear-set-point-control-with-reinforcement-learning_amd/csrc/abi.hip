@@ -120,16 +120,7 @@ int launch_critic_scale(int, int, float* const*, const double*, int, float*, flo
 int launch_adam(float*, float*, float*, float*, long long, float, float, float, float, float*, const int32_t*, float* const (*)[2],
                 const float*, long long, int, hipStream_t);
 int launch_rollout(int, int, const RolloutArgs&, hipStream_t);
-// td3_fused.hip
-int td3_grid(int);
-int64_t td3_workspace_floats(int, int, int);
-bool td3_supported(int, int, int);
-int launch_td3_grad(bool, int, const Td3GradArgs&, int, hipStream_t);
-int launch_td3_apply(const Td3ApplyArgs&, hipStream_t);
-// sac_fused.hip
-bool sac_supported(int, int, int);
-int64_t sac_workspace_floats(int, int, int);
-int launch_sac_grad(bool, int, const SacGradArgs&, int, hipStream_t);
+// (td3_fused.hip, sac_fused.hip: declared in td3.hpp / sac.hpp)
 
 }  // namespace pime
 
@@ -1193,18 +1184,20 @@ int64_t pime_td3_workspace_floats(int32_t D, int32_t md, int32_t B) {
     return td3_workspace_floats(D, md, B);
 }
 
-static int check_td3_net(const pime_td3_net* n, const char* what) {
-    PIME_REQUIRE(n && n->param && n->target && n->grad && n->exp_avg && n->exp_avg_sq && n->step, "pime_td3_step: NULL pointer in the %s's pime_td3_net", what);
+// a net of pime_td3_step / pime_sac_step (`fn`): every pointer set (the target only where the step has one), sane Adam constants
+static int check_offpolicy_net(const char* fn, const pime_td3_net* n, const char* what, bool need_target) {
+    PIME_REQUIRE(n && n->param && (n->target || !need_target) && n->grad && n->exp_avg && n->exp_avg_sq && n->step,
+                 "%s: NULL pointer in the %s's pime_td3_net", fn, what);
     PIME_REQUIRE(n->lr > 0.f && n->beta1 >= 0.f && n->beta1 < 1.f && n->beta2 >= 0.f && n->beta2 < 1.f && n->eps > 0.f,
-                 "pime_td3_step: bad Adam constants for the %s", what);
+                 "%s: bad Adam constants for the %s", fn, what);
     return PIME_OK;
 }
 
 int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_td3_batch* b, float tau,
                   int32_t update_freq, int32_t soft_mode, int32_t phases, float* workspace, float* loss, pime_stream stream) {
     PIME_REQUIRE(td3_supported(D, 1, md), "pime_td3_step: no kernel for state_dim %d width %d (1 <= D <= %d, width 64 | 128 | 256)", D, md, kTd3MaxD);
-    if (int rc = check_td3_net(actor, "actor")) return rc;
-    if (int rc = check_td3_net(critic, "critic")) return rc;
+    if (int rc = check_offpolicy_net("pime_td3_step", actor, "actor", true)) return rc;
+    if (int rc = check_offpolicy_net("pime_td3_step", critic, "critic", true)) return rc;
     PIME_REQUIRE(b && b->state && b->other && b->idx && b->nxt && b->B >= 1, "pime_td3_step: bad pime_td3_batch");
     PIME_REQUIRE(workspace != nullptr, "pime_td3_step: NULL workspace");
     PIME_REQUIRE(soft_mode >= 0 && soft_mode <= 2 && (soft_mode != 2 || update_freq >= 1), "pime_td3_step: soft_mode %d / update_freq %d", soft_mode, update_freq);
@@ -1277,19 +1270,11 @@ int64_t pime_sac_workspace_floats(int32_t D, int32_t md, int32_t B) {
     return sac_workspace_floats(D, md, B);
 }
 
-static int check_sac_net(const pime_td3_net* n, const char* what, bool need_target) {
-    PIME_REQUIRE(n && n->param && (n->target || !need_target) && n->grad && n->exp_avg && n->exp_avg_sq && n->step,
-                 "pime_sac_step: NULL pointer in the %s's pime_td3_net", what);
-    PIME_REQUIRE(n->lr > 0.f && n->beta1 >= 0.f && n->beta1 < 1.f && n->beta2 >= 0.f && n->beta2 < 1.f && n->eps > 0.f,
-                 "pime_sac_step: bad Adam constants for the %s", what);
-    return PIME_OK;
-}
-
 int pime_sac_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_sac_temperature* temp,
                   const pime_sac_batch* b, float tau, int32_t phases, float* workspace, float* loss, pime_stream stream) {
     PIME_REQUIRE(sac_supported(D, 1, md), "pime_sac_step: no kernel for state_dim %d width %d (" PIME_SAC_SERVED ")", D, md, kSacMaxD);
-    if (int rc = check_sac_net(actor, "actor", false)) return rc;
-    if (int rc = check_sac_net(critic, "critic", true)) return rc;
+    if (int rc = check_offpolicy_net("pime_sac_step", actor, "actor", false)) return rc;
+    if (int rc = check_offpolicy_net("pime_sac_step", critic, "critic", true)) return rc;
     PIME_REQUIRE(temp && temp->alpha_log && temp->exp_avg && temp->exp_avg_sq, "pime_sac_step: NULL pointer in pime_sac_temperature");
     PIME_REQUIRE(temp->lr > 0.f && temp->beta1 >= 0.f && temp->beta1 < 1.f && temp->beta2 >= 0.f && temp->beta2 < 1.f && temp->eps > 0.f,
                  "pime_sac_step: bad Adam constants for the temperature");

@@ -59,4 +59,9 @@ struct SacGradArgs {
     int stride, ngroups;
 };
 
+// sac_fused.hip, host side
+bool sac_supported(int D, int action_dim, int md);
+int64_t sac_workspace_floats(int D, int md, int B);     // both nets' slabs + the gathered rows
+int launch_sac_grad(bool critic, int md, const SacGradArgs& a, int grid, hipStream_t s);
+
 }  // namespace pime

@@ -511,7 +511,6 @@ __global__ __launch_bounds__(NW * 64, 1) void sac_actor_kernel(SacGradArgs a) {
 }
 
 // ======================================================================================================== host side
-int td3_grid(int);
 bool sac_supported(int D, int A, int md) { return A == 1 && D >= 1 && D <= kSacMaxD && (md == 64 || md == 128); }
 int64_t sac_workspace_floats(int D, int md, int B) {
     const int64_t g = td3_grid(B);

@@ -1,5 +1,6 @@
 // Launch-argument blocks and parameter / slab layouts of the fused TD3 optimizer step (td3_fused.hip), shared with abi.hip.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace pime {
@@ -126,5 +127,12 @@ struct Td3ApplyArgs {
         float lr, b1, b2, eps, target_entropy;
     } temp;
 };
+
+// td3_fused.hip, host side
+int td3_grid(int B);                                    // workgroups (= slabs) of a gradient launch on a minibatch of B rows
+int64_t td3_workspace_floats(int D, int md, int B);     // both nets' slabs + the gathered rows
+bool td3_supported(int D, int action_dim, int md);
+int launch_td3_grad(bool critic, int md, const Td3GradArgs& a, int grid, hipStream_t s);
+int launch_td3_apply(const Td3ApplyArgs& a, hipStream_t s);
 
 }  // namespace pime

@@ -1,6 +1,8 @@
-"""Base agents: AgentBase, AgentPPO (on-policy, the residual agents' parent) and AgentTD3
-(interface of /root/reference/elegantrl/agent.py: AgentBase :15-124, AgentTD3 :276-394, AgentPPO :543-712; AgentSAC :397-478
-is in agent_sac.py and importable from here).
+"""Base agents: AgentBase, AgentPPO (on-policy, the residual agents' parent), AgentOffPolicy and AgentTD3
+(interface of the reference's elegantrl/agent.py: AgentBase :15-124, AgentTD3 :276-394, AgentPPO :543-712; AgentSAC :397-478
+is in agent_sac.py and importable from here).  AgentOffPolicy is not in the reference: it is the host path that AgentTD3 and
+AgentSAC share -- vectorised exploration into a VecReplayBuffer and `update_net` on a fused optimizer step (index tables, one
+HIP graph per update) -- so that each agent keeps only its own arithmetic.
 
 What differs from the reference, by design:
   * `explore_env` understands vectorised envs (`env.num_envs`): all N lanes advance in lock-step, the policy
@@ -686,123 +688,77 @@ class AgentPPO(AgentBase):
         return r_sum.reshape(-1), self._normalise_advantage(adv.reshape(-1))
 
 
-# ================================================================================================= TD3
-class AgentTD3(AgentBase):
-    """Twin-delayed DDPG (agent.py:276-394): twin critics, target policy smoothing, delayed soft target updates.
+# ================================================================================================= off-policy
+class AgentOffPolicy(AgentBase):
+    """The host path AgentTD3 and AgentSAC share: exploration of a vectorised env into a `VecReplayBuffer` (one fused launch per
+    call, or lock-step by lock-step), and `update_net` on a fused optimizer step (ops.FusedTD3 / ops.FusedSAC): the tables of a
+    whole update drawn at once, the update captured as ONE HIP graph from the second call on, one host read at the end.
 
-    One-instance env + flat ring buffer: the reference's loop, op for op (pinned against the reference's weights by
-    tests/test_td3_golden_cpu.py).  Vectorised env (`env.num_envs`) + `VecReplayBuffer`: all lanes step in lock-step through
-    the HIP env kernel, transitions stay in HBM, and `update_net` runs target_step / num_envs * repeat_times optimizer steps
-    (the reference's "one gradient step per env step" counted per LOCK-STEP, not per lane).  On the GPU an optimizer step is
-    four hand-written launches (`pime_td3_step`, csrc/td3_fused.hip: critic gradients, slab reduction + Adam + delayed soft
-    update, actor gradients through the target critic, the same for the actor), a whole update_net one HIP graph; shapes the
-    kernels do not serve (state_dim > 7, widths other than 64 / 128, data parallel) and CPU tensors run the same arithmetic as
-    PyTorch modules (`_one_update`)."""
+    An agent names its fused step (`_fused_name`: the backend's factory and, with a leading underscore, the cache attribute) and
+    supplies `_explore_actions`, `_rollout_sigma`, `_rollout_priorK` and the `f.step` closure of its `_update_fused`."""
+    _fused_name = None   # "fused_td3" / "fused_sac"
 
     def __init__(self, backend=None, device=None):
         super().__init__(backend, device)
-        self.explore_noise = 0.1
-        self.policy_noise = 0.2
-        self.update_freq = 2
         self.use_hip_graphs = True
-        self.use_fused_rollout = True   # vectorised env: the whole explore call as ONE launch (csrc/rollout_offpolicy.hip)
-        self.use_fused_update = os.environ.get("PIME_TD3_FUSED", "1") == "1"   # the optimizer step on the hand-written kernels
-        self.draw_hook = None      # tests: callable(n_steps, batch) -> (idx, nxt, noise) tables of a whole update (injected draws)
+        self.use_graph_collective = True   # data parallel: capture the all-reduces inside the update's graph
+        self.use_fused_rollout = True      # vectorised env: a whole explore call / evaluation episode as ONE launch
+        self.draw_hook = None      # tests: callable(n_steps, batch) -> (idx, nxt, noise table(s)) of a whole update (injected draws)
         self.launch_timer = None   # bench.py: callable(name, fn) timing one update's launches with HIP events
-        self._fused_td3 = None
-        self._graphs = None
+        setattr(self, "_" + self._fused_name, None)   # None: not built yet; False: no fused step for these nets
         self._obs = None
         self._packed_act = None
 
-    def init(self, net_dim, state_dim, action_dim, if_per=False):
-        assert not if_per, "prioritised replay is not on the residual-control path"
-        self._pick_device()
-        from copy import deepcopy
-        self.cri = CriticTwin(net_dim, state_dim, action_dim).to(self.device)
-        self.cri_target = deepcopy(self.cri)
-        self.act = Actor(net_dim, state_dim, action_dim).to(self.device)
-        self.act_target = deepcopy(self.act)
-        self._make_optimizers()
-        self.criterion = torch.nn.SmoothL1Loss()
-        self.get_obj_critic = self.get_obj_critic_raw
-
-    def _make_optimizers(self):
-        kw = dict(fused=True, capturable=True) if self.device.type == "cuda" else {}
-        self.cri_optimizer = torch.optim.Adam(self.cri.parameters(), lr=self.learning_rate, **kw)
-        self.act_optimizer = torch.optim.Adam(self.act.parameters(), lr=self.learning_rate, **kw)
-        self._graphs = None
-        self._packed_act = None
-        self._fused_td3 = None   # its Adam moments belong to the optimizers just replaced
-
-    def weights_changed(self):
-        super().weights_changed()
-        self._graphs = None   # (the fused step reads the parameters where they live: nothing of it goes stale)
-
     def _fused_step(self, batch_size):
-        """ops.FusedTD3 serving the current nets, or None -> the PyTorch modules (_one_update)."""
-        if not self.use_fused_update or self.device.type != "cuda" or not hasattr(self.backend, "fused_td3"):
+        """The fused optimizer step (ops.FusedTD3 / ops.FusedSAC) serving the current nets, or None -> the PyTorch modules
+        (_one_update)."""
+        if not self.use_fused_update or self.device.type != "cuda" or not hasattr(self.backend, self._fused_name):
             return None
-        f = self._fused_td3
+        f = getattr(self, "_" + self._fused_name)
         if f is False:
             return None
         if f is None or not f.wraps(self):
-            f = self._fused_td3 = self.backend.fused_td3(self, batch_size)
+            f = getattr(self.backend, self._fused_name)(self, batch_size)
+            setattr(self, "_" + self._fused_name, f)
             if f is False:
                 return None
         f.ensure_batch(batch_size)
         return f
 
-    def _prior_term(self, states):
-        """Prior-controller part of the env action (none for plain TD3)."""
-        return None
-
+    # ---- exploration -------------------------------------------------------------------------------------
     def _rollout_priorK(self):
-        """float64 prior gain of the fused exploration kernel's composition a_env = a + s @ priorK (zeros: plain TD3)."""
+        """float64 prior gain of the fused exploration kernel's composition a_env = a + s @ priorK (zeros: no prior controller)."""
         return np.zeros(self.act.state_dim)
 
-    def _fused_explore(self, env):
-        """Packed deterministic actor for the fused exploration kernel, or None -> lock-step by lock-step launches.  The image is
-        re-packed on every call: the actor's weights change with every update_net."""
-        if not (self.use_fused_rollout and hasattr(env, "offpolicy_rollout_supported") and hasattr(self.backend, "packed")):
+    def _rollout_sigma(self):
+        """Standard deviation of the clipped Gaussian the fused exploration kernel adds to the actor's output."""
+        raise NotImplementedError
+
+    def _explore_actions(self, obs):
+        """(stored action, env action) of one lock-step for the observation batch `obs`."""
+        raise NotImplementedError
+
+    def _packed_actor(self):
+        """ops.PackedMLP image of the actor for the fused exploration / evaluation kernels (its caller re-packs it: the weights change
+        with every update_net); None when its shape has no fused forward."""
+        if not self.use_fused_rollout or not hasattr(self.backend, "packed") or getattr(self.act, "action_dim", 1) != 1:
             return None
-        if getattr(self.act, "action_dim", 1) != 1:
-            return None
-        if self._packed_act is None or self._packed_act is False:
-            if self._packed_act is False:
-                return None
+        if self._packed_act is None:
             self._packed_act = self.backend.packed(self.act) or False
-            if self._packed_act is False:
-                return None
-        pk = self._packed_act
-        if not env.offpolicy_rollout_supported(pk):
+        return self._packed_act or None
+
+    def _fused_explore(self, env):
+        """The freshly re-packed actor if the fused exploration kernel serves `env` with it, else None -> lock-step by lock-step
+        launches."""
+        if not hasattr(env, "offpolicy_rollout_supported"):
+            return None
+        pk = self._packed_actor()
+        if pk is None or not env.offpolicy_rollout_supported(pk):
             return None
         if not hasattr(self, "_rollout_seed"):
             self._rollout_seed = int(torch.initial_seed()) & (2 ** 63 - 1)   # exploration stream follows torch's seed
             self._rollout_epoch = 0
-        pk.repack()
-        return pk
-
-    def select_action(self, state, if_deterministic=False):
-        states = torch.as_tensor(np.asarray(state)[None], dtype=torch.float32, device=self.device)
-        with torch.no_grad():
-            action = self.act(states)[0]
-            if not if_deterministic:
-                action = (action + torch.randn_like(action) * self.explore_noise).clamp(-1, 1)
-        return action.cpu().numpy()
-
-    def _env_action(self, state, action):
-        """What a one-instance env receives for the stored `action` (the residual agents add the prior term)."""
-        return action
-
-    def explore_env(self, env, buffer, target_step, reward_scale, gamma):
-        if hasattr(env, "num_envs"):
-            return self.explore_vec_env(env, buffer, target_step, reward_scale, gamma)
-        for _ in range(target_step):   # agent.py:54-70, continuing from self.state
-            action = self.select_action(self.state)
-            next_s, reward, done, _ = env.step(self._env_action(self.state, action))
-            buffer.append_buffer(self.state, (reward * reward_scale, 0.0 if done else gamma, *action))
-            self.state = env.reset() if done else next_s
-        return target_step
+        return pk.repack()
 
     def explore_vec_env(self, env, buffer, target_step, reward_scale, gamma):
         """target_step transitions = target_step / N lock-steps of all N lanes, continuing the running episodes; finished
@@ -828,7 +784,7 @@ class AgentTD3(AgentBase):
             while done_steps < steps:
                 n = min(steps - done_steps, buffer.slots)
                 self._rollout_epoch += 1
-                env.rollout_offpolicy(pk, self._rollout_priorK(), self.explore_noise, gamma, reward_scale, n, self._rollout_seed,
+                env.rollout_offpolicy(pk, self._rollout_priorK(), self._rollout_sigma(), gamma, reward_scale, n, self._rollout_seed,
                                       self._rollout_epoch, self._obs, buffer.state, buffer.other, buffer.next_slot)
                 buffer.advance(n)
                 done_steps += n
@@ -836,16 +792,178 @@ class AgentTD3(AgentBase):
         for _ in range(steps):
             obs = self._obs
             with torch.no_grad():
-                a = self.act(obs)
-                a = (a + torch.randn_like(a) * self.explore_noise).clamp(-1, 1)   # agent.py:305
-                prior = self._prior_term(obs)
-                a_env = a if prior is None else a + prior
+                a, a_env = self._explore_actions(obs)
             _, rew, done = env.step(a_env, auto_reset=True, out_obs=self._next_obs)
             with torch.no_grad():
                 mask = (1.0 - done.to(torch.float32)) * gamma
                 buffer.append_step(obs, rew * reward_scale if reward_scale != 1.0 else rew, mask, a)
             self._obs, self._next_obs = self._next_obs, self._obs
         return steps * N
+
+    # ---- update_net on the fused step --------------------------------------------------------------------
+    def _draw_tables(self, f, buffer, n_steps, batch_size, n_noise):
+        """First stage of an update on the fused step `f`: the sampled rows of ALL n_steps optimizer steps drawn at once into the
+        index tables idx / nxt (int64 [n_steps, batch_size]) that the kernels read by row; `draw_hook` injects them instead, with
+        n_noise tables of normal draws.  Then table row 0 and the next noise epoch.  Returns (idx, nxt, the list of noise tables or
+        None: Philox in the kernels)."""
+        dev = self.device
+        st = getattr(f, "tables", None)
+        if st is None or st["shape"] != (n_steps, batch_size):
+            i64 = dict(dtype=torch.int64, device=dev)
+            st = f.tables = {"shape": (n_steps, batch_size), "idx": torch.zeros((n_steps, batch_size), **i64),
+                             "nxt": torch.zeros((n_steps, batch_size), **i64), "noise": None, "graph": None, "key": None, "warm": False}
+        idx, nxt, noise = st["idx"], st["nxt"], None
+        if self.draw_hook is not None:
+            h_idx, h_nxt, *h_noise = self.draw_hook(n_steps, batch_size)
+            assert len(h_noise) == n_noise
+            idx.copy_(torch.as_tensor(h_idx).to(dev)); nxt.copy_(torch.as_tensor(h_nxt).to(dev))
+            if st["noise"] is None:
+                st["noise"] = torch.zeros((n_noise, n_steps, batch_size), dtype=torch.float32, device=dev)
+            for dst, h in zip(st["noise"], h_noise):
+                dst.copy_(torch.as_tensor(h).to(dev).reshape(n_steps, batch_size))
+            noise = list(st["noise"])
+        elif isinstance(buffer, VecReplayBuffer):   # its sample_indices for the whole table: uniform over the rows that have a successor
+            assert buffer.stored_slots >= 2, "need two stored steps before sampling"
+            N = buffer.num_envs
+            u = torch.randint(2 ** 62, (n_steps, batch_size), device=dev) % buffer._bounds[0]   # bounds live on the device (replay.py)
+            lane = u % N
+            slot = (u // N + buffer._bounds[1]) % buffer.slots                   # slots in age order start at the oldest
+            torch.add(slot * N, lane, out=idx)
+            torch.add(((slot + 1) % buffer.slots) * N, lane, out=nxt)            # successor: same lane, next slot
+        else:       # ReplayBuffer.sample_batch (replay.py:344-351): rows [0, now_len - 1), successor = the next row
+            torch.randint(buffer.now_len - 1, (n_steps, batch_size), device=dev, out=idx)
+            torch.add(idx, 1, out=nxt)
+        if not hasattr(self, "_noise_seed"):
+            self._noise_seed = (int(torch.initial_seed()) ^ 0x5DEECE66D) & (2 ** 63 - 1)   # the kernels' draws follow torch's seed
+        f.loss.zero_()
+        f.begin_update()   # table row 0; the noise epoch advances (a captured graph draws fresh noise in every replay)
+        return idx, nxt, noise
+
+    def _run_update(self, f, run, key, name, n_steps, n_updates):
+        """Second stage: `run` launches every optimizer step of the update on the current stream.  After the first (warm, eager)
+        update it is captured as ONE HIP graph, replayed while `key` -- everything the graph bakes in besides f's own tensors --
+        stays the same.  Returns f.loss as a list: the update's only host synchronisation."""
+        dev, st = self.device, f.tables
+        # data parallel: the all-reduces of every step are captured inside the update's graph where the communicator allows it
+        # (RCCL: yes; gloo and a refused capture: eager launches, decided for all ranks together)
+        in_graph_dp = self.dp is not None and self.use_graph_collective and getattr(self.dp, "graph_capturable", False)
+        can_graph = self.use_hip_graphs and (self.dp is None or in_graph_dp)
+        if can_graph and st["warm"] and (st["graph"] is None or st["key"] != key):
+            refused = None
+            try:
+                torch.cuda.synchronize(dev)
+                g = torch.cuda.CUDAGraph()
+                with _no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    run()
+                st["graph"], st["key"] = g, key
+            except RuntimeError as exc:
+                refused = exc
+            if self.dp is not None:
+                # the ranks must agree on the launch form: one MAX over the ranks decides for all of them
+                if self.dp.max_over_ranks(1.0 if refused is not None else 0.0) > 0.5:
+                    print(f"| all-reduce inside the {name.upper()} update's HIP graph refused on a rank ({refused}); every rank launches eagerly")
+                    self.use_graph_collective, can_graph = False, False
+                    torch.cuda.synchronize(dev)
+                    st["graph"] = None
+            elif refused is not None:
+                print(f"| HIP graph capture of the {name.upper()} update failed ({refused}); continuing with eager launches")
+                self.use_hip_graphs = can_graph = False
+                torch.cuda.synchronize(dev)
+                st["graph"] = None
+        go = st["graph"].replay if (can_graph and st["graph"] is not None and st["key"] == key) else run
+        if self.launch_timer is not None:
+            self.launch_timer(name + "_update", go)
+        else:
+            go()
+        st["warm"] = True
+        f.row = n_steps        # (begin_update of the next call moves them into the optimizers' step base)
+        self._n_updates += n_updates
+        tot = f.loss.tolist()
+        if self.dp is not None:
+            self.dp.check()     # a timed-out one-shot all-reduce left gradients un-averaged: fatal, here where the stream is drained
+        return tot
+
+
+# ================================================================================================= TD3
+class AgentTD3(AgentOffPolicy):
+    """Twin-delayed DDPG (agent.py:276-394): twin critics, target policy smoothing, delayed soft target updates.
+
+    One-instance env + flat ring buffer: the reference's loop, op for op (pinned against the reference's weights by
+    tests/test_td3_golden_cpu.py).  Vectorised env (`env.num_envs`) + `VecReplayBuffer`: all lanes step in lock-step through
+    the HIP env kernel, transitions stay in HBM, and `update_net` runs target_step / num_envs * repeat_times optimizer steps
+    (the reference's "one gradient step per env step" counted per LOCK-STEP, not per lane).  On the GPU an optimizer step is
+    four hand-written launches (`pime_td3_step`, csrc/td3_fused.hip: critic gradients, slab reduction + Adam + delayed soft
+    update, actor gradients through the target critic, the same for the actor), a whole update_net one HIP graph
+    (AgentOffPolicy); shapes the kernels do not serve (state_dim > 31, widths other than 64 / 128 / 256) and CPU tensors run
+    the same arithmetic as PyTorch modules (`_one_update`)."""
+    _fused_name = "fused_td3"
+
+    def __init__(self, backend=None, device=None):
+        super().__init__(backend, device)
+        self.explore_noise = 0.1
+        self.policy_noise = 0.2
+        self.update_freq = 2
+        self.use_fused_update = os.environ.get("PIME_TD3_FUSED", "1") == "1"   # the optimizer step on the hand-written kernels
+        self._graphs = None
+
+    def init(self, net_dim, state_dim, action_dim, if_per=False):
+        assert not if_per, "prioritised replay is not on the residual-control path"
+        self._pick_device()
+        from copy import deepcopy
+        self.cri = CriticTwin(net_dim, state_dim, action_dim).to(self.device)
+        self.cri_target = deepcopy(self.cri)
+        self.act = Actor(net_dim, state_dim, action_dim).to(self.device)
+        self.act_target = deepcopy(self.act)
+        self._make_optimizers()
+        self.criterion = torch.nn.SmoothL1Loss()
+        self.get_obj_critic = self.get_obj_critic_raw
+
+    def _make_optimizers(self):
+        kw = dict(fused=True, capturable=True) if self.device.type == "cuda" else {}
+        self.cri_optimizer = torch.optim.Adam(self.cri.parameters(), lr=self.learning_rate, **kw)
+        self.act_optimizer = torch.optim.Adam(self.act.parameters(), lr=self.learning_rate, **kw)
+        self._graphs = None
+        self._packed_act = None
+        self._fused_td3 = None   # its Adam moments belong to the optimizers just replaced
+
+    def weights_changed(self):
+        super().weights_changed()
+        self._graphs = None   # (the fused step reads the parameters where they live: nothing of it goes stale)
+
+    def _prior_term(self, states):
+        """Prior-controller part of the env action (none for plain TD3)."""
+        return None
+
+    def _rollout_sigma(self):
+        return self.explore_noise
+
+    def _explore_actions(self, obs):
+        a = self.act(obs)
+        a = (a + torch.randn_like(a) * self.explore_noise).clamp(-1, 1)   # agent.py:305
+        prior = self._prior_term(obs)
+        return a, (a if prior is None else a + prior)
+
+    def select_action(self, state, if_deterministic=False):
+        states = torch.as_tensor(np.asarray(state)[None], dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            action = self.act(states)[0]
+            if not if_deterministic:
+                action = (action + torch.randn_like(action) * self.explore_noise).clamp(-1, 1)
+        return action.cpu().numpy()
+
+    def _env_action(self, state, action):
+        """What a one-instance env receives for the stored `action` (the residual agents add the prior term)."""
+        return action
+
+    def explore_env(self, env, buffer, target_step, reward_scale, gamma):
+        if hasattr(env, "num_envs"):
+            return self.explore_vec_env(env, buffer, target_step, reward_scale, gamma)
+        for _ in range(target_step):   # agent.py:54-70, continuing from self.state
+            action = self.select_action(self.state)
+            next_s, reward, done, _ = env.step(self._env_action(self.state, action))
+            buffer.append_buffer(self.state, (reward * reward_scale, 0.0 if done else gamma, *action))
+            self.state = env.reset() if done else next_s
+        return target_step
 
     def get_obj_critic_raw(self, buffer, batch_size):
         with torch.no_grad():
@@ -919,50 +1037,15 @@ class AgentTD3(AgentBase):
         return float(obj_actor), float(obj_critic) / 2
 
     def _update_fused(self, f, buffer, n_steps, batch_size, n_updates):
-        """update_net on the fused step: the sampled rows of ALL n_steps optimizer steps are drawn at once into an index table that
-        the kernels read by row (a launch argument), the smoothing noise is drawn inside
-        the critic kernel (Philox stream 3; `draw_hook` injects tables instead), and from the second call on the whole update --
-        n_steps x 4 launches -- is ONE HIP graph.  The only host synchronisation is the read of the four loss words at the end."""
-        dev = self.device
-        vec = isinstance(buffer, VecReplayBuffer)
-        st = getattr(f, "tables", None)
-        if st is None or st["shape"] != (n_steps, batch_size):
-            i64 = dict(dtype=torch.int64, device=dev)
-            st = f.tables = {"shape": (n_steps, batch_size), "idx": torch.zeros((n_steps, batch_size), **i64),
-                             "nxt": torch.zeros((n_steps, batch_size), **i64), "noise": None, "graph": None, "key": None, "warm": False}
-        idx, nxt = st["idx"], st["nxt"]
-        if self.draw_hook is not None:
-            h_idx, h_nxt, h_noise = self.draw_hook(n_steps, batch_size)
-            idx.copy_(torch.as_tensor(h_idx).to(dev)); nxt.copy_(torch.as_tensor(h_nxt).to(dev))
-            if st["noise"] is None:
-                st["noise"] = torch.zeros((n_steps, batch_size), dtype=torch.float32, device=dev)
-            st["noise"].copy_(torch.as_tensor(h_noise).to(dev).reshape(n_steps, batch_size))
-        elif vec:   # VecReplayBuffer.sample_indices for the whole table: uniform over the rows that have a successor
-            assert buffer.stored_slots >= 2, "need two stored steps before sampling"
-            N = buffer.num_envs
-            u = torch.randint(2 ** 62, (n_steps, batch_size), device=dev) % buffer._bounds[0]   # bounds live on the device (replay.py)
-            lane = u % N
-            slot = (u // N + buffer._bounds[1]) % buffer.slots                   # slots in age order start at the oldest
-            torch.add(slot * N, lane, out=idx)
-            torch.add(((slot + 1) % buffer.slots) * N, lane, out=nxt)            # successor: same lane, next slot
-        else:       # ReplayBuffer.sample_batch (replay.py:344-351): rows [0, now_len - 1), successor = the next row
-            torch.randint(buffer.now_len - 1, (n_steps, batch_size), device=dev, out=idx)
-            torch.add(idx, 1, out=nxt)
-        noise = st["noise"] if self.draw_hook is not None else None
-        if not hasattr(self, "_smooth_seed"):
-            self._smooth_seed = (int(torch.initial_seed()) ^ 0x5DEECE66D) & (2 ** 63 - 1)   # smoothing noise follows torch's seed
-        f.loss.zero_()
-        f.begin_update()   # table row 0; the noise epoch advances (a captured graph draws fresh noise in every replay)
-
-        # data parallel: the two all-reduces of every step are captured inside the update's graph where the communicator allows it
-        # (RCCL: yes; gloo and a refused capture: eager launches, decided for all ranks together)
-        in_graph_dp = (self.dp is not None and getattr(self, "use_graph_collective", True)
-                       and getattr(self.dp, "graph_capturable", False))
-        can_graph = self.use_hip_graphs and (self.dp is None or in_graph_dp)
+        """update_net on the fused step (AgentOffPolicy._draw_tables / _run_update): the smoothing noise is drawn inside the critic
+        kernel (Philox stream 3; `draw_hook` injects a table instead) and the whole update -- n_steps x 4 launches -- is ONE HIP
+        graph.  The only host synchronisation is the read of the four loss words at the end."""
+        idx, nxt, noise = self._draw_tables(f, buffer, n_steps, batch_size, 1)
+        noise = None if noise is None else noise[0]
 
         def one(k, phases):   # the row is a launch argument: every node of the captured graph carries its own
             f.step(buffer.buf_state, buffer.buf_other, idx, nxt, noise, self.soft_update_tau, self.update_freq, self.policy_noise,
-                   noise_seed=self._smooth_seed, row=k, phases=phases)
+                   noise_seed=self._noise_seed, row=k, phases=phases)
 
         def run():
             """Every optimizer step's launches, in order, on the current stream."""
@@ -982,39 +1065,7 @@ class AgentTD3(AgentBase):
 
         key = (buffer.buf_state.data_ptr(), buffer.buf_other.data_ptr(), noise is None, self.soft_update_tau, self.update_freq,
                self.policy_noise, self.dp is not None)
-        if can_graph and st["warm"] and (st["graph"] is None or st["key"] != key):
-            refused = None
-            try:
-                torch.cuda.synchronize(dev)
-                g = torch.cuda.CUDAGraph()
-                with _no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    run()
-                st["graph"], st["key"] = g, key
-            except RuntimeError as exc:
-                refused = exc
-            if self.dp is not None:
-                # the ranks must agree on the launch form: one MAX over the ranks decides for all of them
-                if self.dp.max_over_ranks(1.0 if refused is not None else 0.0) > 0.5:
-                    print(f"| all-reduce inside the TD3 update's HIP graph refused on a rank ({refused}); every rank launches eagerly")
-                    self.use_graph_collective, can_graph = False, False
-                    torch.cuda.synchronize(dev)
-                    st["graph"] = None
-            elif refused is not None:
-                print(f"| HIP graph capture of the TD3 update failed ({refused}); continuing with eager launches")
-                self.use_hip_graphs = False
-                torch.cuda.synchronize(dev)
-                st["graph"] = None
-        go = st["graph"].replay if (can_graph and st["graph"] is not None and st["key"] == key) else run
-        if self.launch_timer is not None:
-            self.launch_timer("td3_update", go)
-        else:
-            go()
-        st["warm"] = True
-        f.row = n_steps        # (begin_update of the next call moves them into the optimizers' step base)
-        self._n_updates += n_updates
-        tot = f.loss.tolist()   # the update's only host synchronisation
-        if self.dp is not None:
-            self.dp.check()     # a timed-out one-shot all-reduce left gradients un-averaged: fatal, here where the stream is drained
+        tot = self._run_update(f, run, key, "td3", n_steps, n_updates)
         logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         logger.record("train/actor_loss", tot[0] / n_steps)
         logger.record("train/critic_loss", tot[1] / n_steps)

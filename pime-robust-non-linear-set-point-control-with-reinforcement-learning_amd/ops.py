@@ -383,9 +383,108 @@ class FlatAdam:
 _TD3_ACTOR_PARAMS = ["net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias", "net.6.weight", "net.6.bias"]
 _TD3_CRITIC_PARAMS = ["net_sa.0.weight", "net_sa.0.bias", "net_sa.2.weight", "net_sa.2.bias", "net_q1.weight", "net_q1.bias",
                       "net_q2.weight", "net_q2.bias"]
+_SAC_ACTOR_PARAMS = ["net_state.0.weight", "net_state.0.bias", "net_state.2.weight", "net_state.2.bias", "net_state.4.weight",
+                     "net_state.4.bias", "net_a_avg.weight", "net_a_avg.bias", "net_a_std.weight", "net_a_std.bias"]
 
 
-class FusedTD3:
+def _td3_layout(which, D, md):
+    """(parameter names, offsets, floats) of a TD3 net's flat tensor: which 0 the Actor, 1 the CriticTwin (SAC's critic too)."""
+    L = native.lib()
+    offs = (C.c_int32 * 8)()
+    native.check(L.pime_td3_param_offsets(which, D, md, offs), "pime_td3_param_offsets")
+    return (_TD3_CRITIC_PARAMS if which else _TD3_ACTOR_PARAMS), list(offs), L.pime_td3_param_floats(which, D, md)
+
+
+class _FusedOffPolicy:
+    """What the fused TD3 and SAC optimizer steps share on the host: the nets re-homed into flat tensors at the library's offsets,
+    the flat gradients and Adam moments, the step base / table row / noise epoch bookkeeping, the workspace and the argument checks
+    of `step`.  A subclass names itself (`name`: the error texts) and its workspace-size function, says which nets there are and at
+    which offsets (`_adopt`), and makes the library call."""
+    name = workspace_floats = None
+
+    def __init__(self, act, cri, md, max_batch, lr, betas, eps):
+        self.device = next(cri.parameters()).device
+        _need_cuda(next(cri.parameters()))
+        self.D, self.md = int(act.state_dim), int(md)
+        if not self.supported(act, cri):
+            raise native.PimeError(f"fused {self.name} step unsupported for state_dim {self.D} width {self.md}: {native.last_error()}")
+        self.max_batch = int(max_batch)
+        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
+
+    def _rehome(self, module, names, offs, n):
+        """The module's parameters moved into ONE flat float32 tensor of n floats: every nn.Parameter becomes a view at its offset."""
+        flat = torch.zeros(n, dtype=torch.float32, device=self.device)
+        sd = dict(module.named_parameters())
+        with torch.no_grad():
+            for name, off in zip(names, offs):
+                p = sd[name]
+                assert p.dtype == torch.float32
+                flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
+                p.data = flat[off:off + p.numel()].view_as(p)
+        return flat
+
+    def _adopt(self, act, act_layout, act_target, cri, cri_layout, cri_target, n_loss):
+        """Flat parameter tensors of the nets (act_target may be None), .grad views of the online ones, Adam moments, counters, the
+        workspace and the two native.Td3Net structs."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.act_flat, self.act_off = self._rehome(act, *act_layout), act_layout[1]
+        if act_target is not None:
+            self.act_t_flat = self._rehome(act_target, *act_layout)
+        self.cri_flat, self.cri_off = self._rehome(cri, *cri_layout), cri_layout[1]
+        self.cri_t_flat = self._rehome(cri_target, *cri_layout)
+        self.act_grad, self.cri_grad = torch.zeros_like(self.act_flat), torch.zeros_like(self.cri_flat)
+        for module, (names, offs, _), g in ((act, act_layout, self.act_grad), (cri, cri_layout, self.cri_grad)):
+            sd = dict(module.named_parameters())
+            for name, off in zip(names, offs):
+                p = sd[name]
+                p.grad = g[off:off + p.numel()].view_as(p)
+        self.state = {k: torch.zeros_like(t) for k, t in (("act_m", self.act_flat), ("act_v", self.act_flat),
+                                                          ("cri_m", self.cri_flat), ("cri_v", self.cri_flat))}
+        self.steps_done = torch.zeros(1, **f32)   # optimizer steps applied before table row 0 of the running update (all nets step together)
+        self.workspace = None
+        self.ensure_batch(self.max_batch)
+        self.loss = torch.zeros(n_loss, **f32)     # first half: sums of the objectives over the update, second half: the last step's
+        self.epoch = torch.zeros(1, dtype=torch.int64, device=self.device)   # added to the noise epoch: bumped once per update
+        self.row = 0                                                          # table row of the next step (host side: a launch argument)
+        self._actor, self._critic = self._net("act", getattr(self, "act_t_flat", None)), self._net("cri", self.cri_t_flat)
+
+    def _net(self, which, target):
+        flat, grad, s = getattr(self, which + "_flat"), getattr(self, which + "_grad"), self.state
+        return native.Td3Net(param=flat.data_ptr(), target=target.data_ptr() if target is not None else None, grad=grad.data_ptr(),
+                             exp_avg=s[which + "_m"].data_ptr(), exp_avg_sq=s[which + "_v"].data_ptr(), step=self.steps_done.data_ptr(),
+                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
+
+    def begin_update(self):
+        """Table row 0 again: the steps of the previous update move into the optimizers' step base, the noise epoch advances."""
+        if self.row:
+            self.steps_done += float(self.row)
+        self.row = 0
+        self.epoch += 1
+
+    def ensure_batch(self, batch):
+        """Workspace (one partial-gradient slab per workgroup) for minibatches of up to `batch` rows; the optimizer state stays."""
+        if self.workspace is None or batch > self.max_batch:
+            self.max_batch = max(int(batch), self.max_batch)
+            n_ws = getattr(native.lib(), self.workspace_floats)(self.D, self.md, self.max_batch)
+            if n_ws <= 0:
+                raise native.PimeError(f"fused {self.name} step: {native.last_error()}")
+            self.workspace = torch.empty(n_ws, dtype=torch.float32, device=self.device)
+
+    def _check_batch(self, buf_state, buf_other, idx, nxt, row, *noise):
+        """(B, row) of a step on table row `row` (None: self.row) after the shape / dtype / contiguity checks of its operands."""
+        _need_cuda(buf_state, buf_other, idx, nxt)
+        B = idx.shape[-1]
+        row = self.row if row is None else int(row)
+        assert idx.dim() == 2 and 0 <= row < idx.shape[0], (row, idx.shape)
+        assert B <= self.max_batch and idx.dtype == nxt.dtype == torch.int64 and idx.is_contiguous() and nxt.is_contiguous()
+        assert buf_state.dtype == buf_other.dtype == torch.float32 and buf_state.is_contiguous() and buf_other.is_contiguous()
+        assert buf_state.shape[1] == self.D and buf_other.shape[1] == 3
+        for n in noise:
+            assert n is None or (n.dtype == torch.float32 and n.is_contiguous() and n.shape == idx.shape)
+        return B, row
+
+
+class FusedTD3(_FusedOffPolicy):
     """One TD3 optimizer step -- critic objective, its gradients, Adam, delayed soft update, actor objective through the target
     critic, its gradients, Adam, delayed soft update (elegantrl/agent.py:314-331 of the reference) -- as four HIP launches
     (csrc/td3_fused.hip, `pime_td3_step`).
@@ -394,54 +493,13 @@ class FusedTD3:
     the 16-byte-aligned offsets the kernels read them at (`pime_td3_param_offsets`); every nn.Parameter becomes a view into its
     net's flat tensor and every online parameter's .grad a view into the flat gradient the step writes.  The kernels read the
     nn.Linear tensors themselves: there are no packed copies to keep in step with the weights."""
+    name, workspace_floats = "TD3", "pime_td3_workspace_floats"
 
     def __init__(self, act, act_target, cri, cri_target, max_batch, lr, betas=(0.9, 0.999), eps=1e-8):
-        dev = next(cri.parameters()).device
-        _need_cuda(next(cri.parameters()))
-        L = native.lib()
-        self.device = dev
-        self.D, self.md = int(act.state_dim), int(act.net[0].out_features)
-        if not self.supported(act, cri):
-            raise native.PimeError(f"fused TD3 step unsupported for state_dim {self.D} width {self.md}: {native.last_error()}")
-        self.max_batch = int(max_batch)
+        super().__init__(act, cri, act.net[0].out_features, max_batch, lr, betas, eps)
         self.nets = (act, act_target, cri, cri_target)
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
-        f32 = dict(dtype=torch.float32, device=dev)
-
-        def rehome(module, names, which):
-            n = L.pime_td3_param_floats(which, self.D, self.md)
-            offs = (C.c_int32 * 8)()
-            native.check(L.pime_td3_param_offsets(which, self.D, self.md, offs), "pime_td3_param_offsets")
-            flat = torch.zeros(n, **f32)
-            sd = dict(module.named_parameters())
-            with torch.no_grad():
-                for name, off in zip(names, offs):
-                    p = sd[name]
-                    assert p.dtype == torch.float32
-                    flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
-                    p.data = flat[off:off + p.numel()].view_as(p)
-            return flat, list(offs)
-
-        self.act_flat, self.act_off = rehome(act, _TD3_ACTOR_PARAMS, 0)
-        self.act_t_flat, _ = rehome(act_target, _TD3_ACTOR_PARAMS, 0)
-        self.cri_flat, self.cri_off = rehome(cri, _TD3_CRITIC_PARAMS, 1)
-        self.cri_t_flat, _ = rehome(cri_target, _TD3_CRITIC_PARAMS, 1)
-        self.act_grad, self.cri_grad = torch.zeros_like(self.act_flat), torch.zeros_like(self.cri_flat)
-        for module, names, offs, g in ((act, _TD3_ACTOR_PARAMS, self.act_off, self.act_grad),
-                                      (cri, _TD3_CRITIC_PARAMS, self.cri_off, self.cri_grad)):
-            sd = dict(module.named_parameters())
-            for name, off in zip(names, offs):
-                p = sd[name]
-                p.grad = g[off:off + p.numel()].view_as(p)
-        self.state = {k: torch.zeros_like(t) for k, t in (("act_m", self.act_flat), ("act_v", self.act_flat),
-                                                          ("cri_m", self.cri_flat), ("cri_v", self.cri_flat))}
-        self.steps_done = torch.zeros(1, **f32)   # optimizer steps applied before table row 0 of the running update (both nets step together)
-        self.workspace = None
-        self.ensure_batch(self.max_batch)
-        self.loss = torch.zeros(4, **f32)          # [0] sum of obj_actor, [1] sum of obj_critic, [2], [3] the last step's
-        self.epoch = torch.zeros(1, dtype=torch.int64, device=dev)    # added to the noise epoch: bumped once per update
-        self.row = 0                                                   # table row of the next step (host side: a launch argument)
-        self._structs()
+        # loss: [0] sum of obj_actor, [1] sum of obj_critic, [2], [3] the last step's
+        self._adopt(act, _td3_layout(0, self.D, self.md), act_target, cri, _td3_layout(1, self.D, self.md), cri_target, n_loss=4)
 
     def step_dp(self, all_reduce_mean, *args, row=None, **kw):
         """One optimizer step of a data-parallel rank: critic gradients + slab reduction, all-reduce (mean) of the critic's gradient,
@@ -455,22 +513,6 @@ class FusedTD3:
         self.step(*args, phases=128, row=r, **kw)
         if row is None:
             self.row += 1
-
-    def begin_update(self):
-        """Table row 0 again: the steps of the previous update move into the optimizers' step base, the noise epoch advances."""
-        if self.row:
-            self.steps_done += float(self.row)
-        self.row = 0
-        self.epoch += 1
-
-    def ensure_batch(self, batch):
-        """Workspace (one partial-gradient slab per workgroup) for minibatches of up to `batch` rows; the optimizer state stays."""
-        if self.workspace is None or batch > self.max_batch:
-            self.max_batch = max(int(batch), self.max_batch)
-            n_ws = native.lib().pime_td3_workspace_floats(self.D, self.md, self.max_batch)
-            if n_ws <= 0:
-                raise native.PimeError(f"fused TD3 step: {native.last_error()}")
-            self.workspace = torch.empty(n_ws, dtype=torch.float32, device=self.device)
 
     @staticmethod
     def supported(act, cri):
@@ -489,15 +531,6 @@ class FusedTD3:
         return (agent.act, agent.act_target, agent.cri, agent.cri_target) == self.nets and \
             agent.act.net[0].weight.data_ptr() == self.act_flat.data_ptr()
 
-    def _structs(self):
-        s = self.state
-        self._actor = native.Td3Net(param=self.act_flat.data_ptr(), target=self.act_t_flat.data_ptr(), grad=self.act_grad.data_ptr(),
-                                    exp_avg=s["act_m"].data_ptr(), exp_avg_sq=s["act_v"].data_ptr(), step=self.steps_done.data_ptr(),
-                                    lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
-        self._critic = native.Td3Net(param=self.cri_flat.data_ptr(), target=self.cri_t_flat.data_ptr(), grad=self.cri_grad.data_ptr(),
-                                     exp_avg=s["cri_m"].data_ptr(), exp_avg_sq=s["cri_v"].data_ptr(), step=self.steps_done.data_ptr(),
-                                     lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
-
     def step(self, buf_state, buf_other, idx, nxt, noise, tau, update_freq, policy_noise, noise_clip=0.5, noise_seed=0,
              noise_epoch=0, soft_mode=2, phases=15, row=None):
         """One optimizer step on table row `row` (default: self.row, which then advances) of idx / nxt (int64 [rows, B]) and noise
@@ -505,15 +538,8 @@ class FusedTD3:
         bakes each step's row into its nodes.  phases: bit 0 critic gradients, 1 critic apply, 2 actor gradients, 3 actor apply
         (include/pime_hip.h: what may run beside what); data-parallel callers split an apply around their all-reduce of cri_grad /
         act_grad: 16 / 64 = slab reduction only, 32 / 128 = Adam (+ soft update) from the gradient tensor (step_dp)."""
-        _need_cuda(buf_state, buf_other, idx, nxt)
-        B = idx.shape[-1]
         advance = row is None
-        row = self.row if advance else int(row)
-        assert idx.dim() == 2 and 0 <= row < idx.shape[0], (row, idx.shape)
-        assert B <= self.max_batch and idx.dtype == nxt.dtype == torch.int64 and idx.is_contiguous() and nxt.is_contiguous()
-        assert buf_state.dtype == buf_other.dtype == torch.float32 and buf_state.is_contiguous() and buf_other.is_contiguous()
-        assert buf_state.shape[1] == self.D and buf_other.shape[1] == 3
-        assert noise is None or (noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == idx.shape)
+        B, row = self._check_batch(buf_state, buf_other, idx, nxt, row, noise)
         batch = native.Td3Batch(state=buf_state.data_ptr(), other=buf_other.data_ptr(), idx=idx.data_ptr(), nxt=nxt.data_ptr(),
                                 noise=noise.data_ptr() if noise is not None else None, row=row, epoch=self.epoch.data_ptr(), B=B,
                                 noise_seed=int(noise_seed), noise_epoch=int(noise_epoch), policy_noise=float(policy_noise),
@@ -527,11 +553,7 @@ class FusedTD3:
             self.row += 1
 
 
-_SAC_ACTOR_PARAMS = ["net_state.0.weight", "net_state.0.bias", "net_state.2.weight", "net_state.2.bias", "net_state.4.weight",
-                     "net_state.4.bias", "net_a_avg.weight", "net_a_avg.bias", "net_a_std.weight", "net_a_std.bias"]
-
-
-class FusedSAC:
+class FusedSAC(_FusedOffPolicy):
     """One SAC optimizer step -- critic objective with the entropy term, its gradients, Adam, soft update, the temperature's
     objective and Adam step, actor objective through the target critic's twin heads, its gradients, Adam
     (elegantrl/agent.py:442-468 of the reference) -- as four HIP launches (csrc/sac_fused.hip, `pime_sac_step`).
@@ -540,78 +562,22 @@ class FusedSAC:
     (`pime_sac_param_offsets` for the actor, `pime_td3_param_offsets` for the critics): every nn.Parameter becomes a view into its
     net's flat tensor and every online parameter's .grad a view into the flat gradient the step writes.  The temperature is the
     agent's own one-element `alpha_log` tensor, stepped on the device."""
+    name, workspace_floats = "SAC", "pime_sac_workspace_floats"
 
     def __init__(self, act, cri, cri_target, alpha_log, max_batch, lr, lr_alpha=None, betas=(0.9, 0.999), eps=1e-8):
-        dev = next(cri.parameters()).device
-        _need_cuda(next(cri.parameters()), alpha_log)
-        L = native.lib()
-        self.device = dev
-        self.D, self.md = int(act.state_dim), int(act.net_state[0].out_features)
-        if not self.supported(act, cri):
-            raise native.PimeError(f"fused SAC step unsupported for state_dim {self.D} width {self.md}: {native.last_error()}")
-        self.max_batch = int(max_batch)
+        super().__init__(act, cri, act.net_state[0].out_features, max_batch, lr, betas, eps)
+        _need_cuda(alpha_log)
         self.nets = (act, cri, cri_target)
         self.alpha_log = alpha_log
-        self.lr, self.lr_alpha, self.betas, self.eps = float(lr), float(lr if lr_alpha is None else lr_alpha), betas, float(eps)
-        f32 = dict(dtype=torch.float32, device=dev)
-
-        def rehome(module, names, n, offs):
-            flat = torch.zeros(n, **f32)
-            sd = dict(module.named_parameters())
-            with torch.no_grad():
-                for name, off in zip(names, offs):
-                    p = sd[name]
-                    assert p.dtype == torch.float32
-                    flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
-                    p.data = flat[off:off + p.numel()].view_as(p)
-            return flat, list(offs)
-
-        a_offs, c_offs = (C.c_int32 * 10)(), (C.c_int32 * 8)()
+        self.lr_alpha = float(lr if lr_alpha is None else lr_alpha)
+        L = native.lib()
+        a_offs = (C.c_int32 * 10)()
         native.check(L.pime_sac_param_offsets(self.D, self.md, a_offs), "pime_sac_param_offsets")
-        native.check(L.pime_td3_param_offsets(1, self.D, self.md, c_offs), "pime_td3_param_offsets")
-        n_a, n_c = L.pime_sac_param_floats(self.D, self.md), L.pime_td3_param_floats(1, self.D, self.md)
-        self.act_flat, self.act_off = rehome(act, _SAC_ACTOR_PARAMS, n_a, a_offs)
-        self.cri_flat, self.cri_off = rehome(cri, _TD3_CRITIC_PARAMS, n_c, c_offs)
-        self.cri_t_flat, _ = rehome(cri_target, _TD3_CRITIC_PARAMS, n_c, c_offs)
-        self.act_grad, self.cri_grad = torch.zeros_like(self.act_flat), torch.zeros_like(self.cri_flat)
-        for module, names, offs, g in ((act, _SAC_ACTOR_PARAMS, self.act_off, self.act_grad),
-                                      (cri, _TD3_CRITIC_PARAMS, self.cri_off, self.cri_grad)):
-            sd = dict(module.named_parameters())
-            for name, off in zip(names, offs):
-                p = sd[name]
-                p.grad = g[off:off + p.numel()].view_as(p)
-        self.state = {k: torch.zeros_like(t) for k, t in (("act_m", self.act_flat), ("act_v", self.act_flat),
-                                                          ("cri_m", self.cri_flat), ("cri_v", self.cri_flat))}
-        self.state["alpha_m"], self.state["alpha_v"] = torch.zeros(1, **f32), torch.zeros(1, **f32)
-        self.steps_done = torch.zeros(1, **f32)   # optimizer steps applied before table row 0 of the running update (all three step together)
-        self.workspace = None
-        self.ensure_batch(self.max_batch)
-        self.loss = torch.zeros(8, **f32)          # sums of obj_actor, obj_critic, obj_alpha, alpha over the update; [4..7] the last step's
-        self.epoch = torch.zeros(1, dtype=torch.int64, device=dev)    # added to the noise epoch: bumped once per update
-        self.row = 0                                                   # table row of the next step (host side: a launch argument)
-        s = self.state
-        self._actor = native.Td3Net(param=self.act_flat.data_ptr(), target=None, grad=self.act_grad.data_ptr(),
-                                    exp_avg=s["act_m"].data_ptr(), exp_avg_sq=s["act_v"].data_ptr(), step=self.steps_done.data_ptr(),
-                                    lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
-        self._critic = native.Td3Net(param=self.cri_flat.data_ptr(), target=self.cri_t_flat.data_ptr(), grad=self.cri_grad.data_ptr(),
-                                     exp_avg=s["cri_m"].data_ptr(), exp_avg_sq=s["cri_v"].data_ptr(), step=self.steps_done.data_ptr(),
-                                     lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
-
-    def begin_update(self):
-        """Table row 0 again: the steps of the previous update move into the optimizers' step base, the noise epoch advances."""
-        if self.row:
-            self.steps_done += float(self.row)
-        self.row = 0
-        self.epoch += 1
-
-    def ensure_batch(self, batch):
-        """Workspace (one partial-gradient slab per workgroup) for minibatches of up to `batch` rows; the optimizer state stays."""
-        if self.workspace is None or batch > self.max_batch:
-            self.max_batch = max(int(batch), self.max_batch)
-            n_ws = native.lib().pime_sac_workspace_floats(self.D, self.md, self.max_batch)
-            if n_ws <= 0:
-                raise native.PimeError(f"fused SAC step: {native.last_error()}")
-            self.workspace = torch.empty(n_ws, dtype=torch.float32, device=self.device)
+        # loss: sums of obj_actor, obj_critic, obj_alpha, alpha over the update; [4..7] the last step's
+        self._adopt(act, (_SAC_ACTOR_PARAMS, list(a_offs), L.pime_sac_param_floats(self.D, self.md)), None,
+                    cri, _td3_layout(1, self.D, self.md), cri_target, n_loss=8)
+        for k in ("alpha_m", "alpha_v"):
+            self.state[k] = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     @staticmethod
     def supported(act, cri):
@@ -635,16 +601,8 @@ class FusedSAC:
         """One optimizer step on table row `row` (default: self.row, which then advances) of idx / nxt (int64 [rows, B]) and the two
         noise tables (float32 [rows, B], or both None: Philox in the kernels).  phases: bit 0 critic gradients, 1 critic apply +
         temperature step, 2 actor gradients, 3 actor apply (include/pime_hip.h)."""
-        _need_cuda(buf_state, buf_other, idx, nxt)
-        B = idx.shape[-1]
         advance = row is None
-        row = self.row if advance else int(row)
-        assert idx.dim() == 2 and 0 <= row < idx.shape[0], (row, idx.shape)
-        assert B <= self.max_batch and idx.dtype == nxt.dtype == torch.int64 and idx.is_contiguous() and nxt.is_contiguous()
-        assert buf_state.dtype == buf_other.dtype == torch.float32 and buf_state.is_contiguous() and buf_other.is_contiguous()
-        assert buf_state.shape[1] == self.D and buf_other.shape[1] == 3
-        for n in (noise_next, noise_pg):
-            assert n is None or (n.dtype == torch.float32 and n.is_contiguous() and n.shape == idx.shape)
+        B, row = self._check_batch(buf_state, buf_other, idx, nxt, row, noise_next, noise_pg)
         temp = native.SacTemperature(alpha_log=self.alpha_log.data_ptr(), exp_avg=self.state["alpha_m"].data_ptr(),
                                      exp_avg_sq=self.state["alpha_v"].data_ptr(), lr=self.lr_alpha, beta1=self.betas[0],
                                      beta2=self.betas[1], eps=self.eps, target_entropy=float(target_entropy))
