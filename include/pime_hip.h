@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 21
+#define PIME_ABI_VERSION 22
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -278,6 +278,12 @@ int64_t pime_ppo_bwd_image_floats(int32_t kind, int32_t D, int32_t Di, int32_t m
  * pime_ppo_repack / pime_ppo_pack_bwd. */
 int64_t pime_ppo_bwd_image_f32_floats(int32_t kind, int32_t D, int32_t Di, int32_t md);
 int64_t pime_ppo_workspace_floats(int32_t kind, int32_t B, int32_t md);
+/* Workgroups (= gradient slabs per net) of the LDS-resident fused gradient kernels for a minibatch of B: one per 256-sample group
+ * up to a cap; beyond it a workgroup takes several groups and accumulates them in its slab. */
+int32_t pime_ppo_fused_grid(int32_t B);
+/* 1 if pime_ppo_minibatch_grad / _step serve an actor of this kind and a critic of the same width on the same D-float state with
+ * the pair kernel (a group's actor and critic in one workgroup), 0 if another kernel serves them. */
+int pime_ppo_pair_fits(int32_t actor_kind, int32_t D, int32_t Di, int32_t md);
 int pime_ppo_pack_bwd(int32_t kind, int32_t D, int32_t Di, int32_t md, const float* const* params, float* image,
                       pime_stream stream);
 /* Re-packs img_fwd and img_bwd of both nets from their `params` in ONE launch (after every optimizer step; the four

@@ -100,6 +100,7 @@ int launch_ppo_fused(int, int, const PpoArgs&, hipStream_t);
 int launch_ppo_fused_dual(int, int, const PpoArgs&, const PpoArgs&, hipStream_t);
 int64_t fused_stash_floats(int, int, int);
 bool fused_fits(int, int, int, int);
+bool fused_pair_fits(int, int, int, int);
 int launch_repack(const PackArgs&, const PackArgs&, float*, float*, float*, float*, hipStream_t);
 int launch_grad_reduce(const PpoArgs&, const PpoArgs&, int, int, int, int, bool, bool, bool, bool, int, int, float* const*,
                        float* const*, float*, float*, double*, float*, int, int64_t*, const ReduceAdam*, float*, hipStream_t);
@@ -674,6 +675,20 @@ int64_t pime_ppo_workspace_floats(int32_t kind, int32_t B, int32_t md) {
     return ppo_workspace_floats(kind, B, md);
 }
 
+int pime_ppo_pair_fits(int32_t actor_kind, int32_t D, int32_t Di, int32_t md) {
+    if (family16_grad(actor_kind, md, D, Di) || family16_grad(PIME_MLP_CRITIC, md, D, 0)) return 0;
+    if (!fused_fits(actor_kind, D, Di, md) || !fused_fits(PIME_MLP_CRITIC, D, 0, md)) return 0;
+    return fused_pair_fits(actor_kind, D, Di, md) ? 1 : 0;
+}
+
+int32_t pime_ppo_fused_grid(int32_t B) {
+    if (B < 1) {
+        set_error("pime_ppo_fused_grid: B=%d", B);
+        return 0;
+    }
+    return fused_grid(B);
+}
+
 int pime_ppo_pack_bwd(int32_t kind, int32_t D, int32_t Di, int32_t md, const float* const* params, float* image,
                       pime_stream stream) {
     PIME_REQUIRE(params != nullptr && image != nullptr, "pime_ppo_pack_bwd: NULL params/image");
@@ -1078,7 +1093,8 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
         }
     }
     PpoArgs slab_args[2];
-    // both nets on the LDS-resident fused kernel and of one width: ONE launch serves them (ppo_fused_dual_kernel)
+    // both nets on the LDS-resident fused kernel and of one width: ONE launch serves them (ppo_fused_pair_kernel where its merged LDS
+    // map fits -- pH and tank observations do --, else ppo_fused_dual_kernel)
     const bool dual = mode[0] == FUSED && mode[1] == FUSED && critic->md == actor->md;
     for (int k = 0; k < 2; ++k) {
         const pime_ppo_net* n = nets[k];

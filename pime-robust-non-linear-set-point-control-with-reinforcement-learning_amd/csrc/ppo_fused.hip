@@ -1,5 +1,6 @@
-// PPO minibatch gradients, one launch per net: forward, loss gradient, backward chain AND the weight gradients of a
-// 256-sample group are formed by one 8-wave workgroup without the dZ tensors ever leaving the CU.
+// PPO minibatch gradients: forward, loss gradient, backward chain AND the weight gradients of a 256-sample group are formed by
+// one 8-wave workgroup without the dZ tensors ever leaving the CU -- one launch per net (ppo_fused_kernel), or, for an actor and a
+// critic of one width, one launch in which a workgroup runs a group's actor and then its critic (ppo_fused_pair_kernel).
 //
 // replaces (reference, /root/reference/elegantrl/agent.py:629-657): minibatch gather, compute_logprob
 // (net_residual.py:48-54,182-190), clipped surrogate + entropy proxy (:637-645), CriticAdv forward + SmoothL1
@@ -440,10 +441,16 @@ __device__ __forceinline__ void bias_store(float bsum, float* __restrict__ gb, i
 // (feature f, slice q) then reads its samples four at a time (ds_read_b128) and the padded state rows xsp[s] = (x_0 .. x_{D-1},
 // 1, 0 ..) as one or two broadcast ds_read_b128: per sample 1/4 + 1 LDS instructions and P fmas for ALL columns and the
 // bias at once.  The Q slices are combined in a fixed order (reproducible).
-template <int T>
+struct NoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+// w_dead(): called once behind the first barrier, i.e. when every wave has left the dX step in front of this job and the W image is
+// dead (the pair kernel starts the next body's forward image there)
+template <int T, class Hook = NoHook>
 __device__ __forceinline__ void first_grad_valu(float* __restrict__ X, int lane, int wave, const f32x16 (&dz)[T],
                                                 const float* __restrict__ xsp, int D, int col0, int Din,
-                                                float* __restrict__ gW, float* __restrict__ gb, bool accum) {
+                                                float* __restrict__ gW, float* __restrict__ gb, bool accum,
+                                                const Hook& w_dead = Hook()) {
     constexpr int R = T * 32, Q = kFusedThreads / R, SP = 128, GPT = SP / Q / 4;   // groups of 4 samples per thread and pass
     static_assert(2 * SP == kFusedWaves * 32 && SP * R <= 2 * (tsize(T) + tsize(T)), "two passes over the X region");
     const int tid = wave * 64 + lane, f = tid % R, q = tid / R, h = lane >> 5, li = lane & 31;
@@ -454,6 +461,7 @@ __device__ __forceinline__ void first_grad_valu(float* __restrict__ X, int lane,
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         PIME_LDS_BARRIER();  // X free
+        if (pass == 0) w_dead();
         if ((wave >> 2) == pass) {
             const int s = (wave & 3) * 32 + li;
             float* p = X + (4 * h) * SP + (s & 3);
@@ -536,32 +544,19 @@ __device__ __forceinline__ void half_sums16(const float (&p)[16], float (&out)[2
     }
 }
 
-// bid / nb: this workgroup's index among the nb workgroups that work on THIS net (ppo_fused_kernel: the grid; ppo_fused_dual_kernel:
-// the net's share of a grid that serves both nets)
+// ---- The pieces of a body.  ppo_fused_kernel (one net per launch) and ppo_fused_pair_kernel (a group's actor AND critic in one
+// workgroup) are built from the same four: the per-net setup, the gather, a group's forward / loss / backward / gradients, and
+// the workgroup totals.
+
+// Per-net setup: the small segments (first-layer image, biases, head) live in LDS for the whole kernel.
 template <int T, int KIND>
-__device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restrict__ lds, const int bid, const int nb) {
+__device__ __forceinline__ void fused_net_setup(const PpoArgs& a, float* __restrict__ lds, const FusedLds& F, const int tid) {
     constexpr bool MODULAR = KIND == MLP_MODULAR_ACTOR;
-    constexpr bool CRITIC = KIND == MLP_CRITIC;
-    constexpr int ACT = CRITIC ? 0 : 1;
     constexpr int H = T / 2 > 0 ? T / 2 : 1;
     constexpr int md = T * 32;
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntiles = (a.B + 31) / 32, ngroups = (ntiles + kFusedWaves - 1) / kFusedWaves;
-    const float invB = 1.0f / (float)a.B;
-    const FusedLds F = fused_lds(KIND, a.D, a.Di, T);
     const MlpLayout L = mlp_layout(KIND, a.D, a.Di, md);
-    const BwdLayout Lb = bwd_layout(KIND, a.D, a.Di, md);
-    float* const wbuf = lds + F.wbuf;
-    float* const X = lds + F.x;
-    float* const xs = lds + F.xs;
-    float* const xsp = lds + F.xsp;
-    float* const hacc = lds + F.hacc;   // head weight gradient of the workgroup
-    const int Do = a.D - a.Di;
-
-    const float asl = CRITIC ? 0.f : a.a_std_log[0];
-    for (int e = tid; e < kFusedWaves * md; e += kFusedThreads) hacc[e] = 0.f;
-    // small segments live in LDS for the whole kernel.  All their loads are issued before the first LDS write: one
+    [[maybe_unused]] const int Do = a.D - a.Di;
+    // All their loads are issued before the first LDS write: one
     // L2 round trip instead of one per segment (7 segments cost the modular actor 10 us).  Named registers, not an array:
     // hipcc put a float4 v[NS] on the stack (144 B of scratch per lane; every reload waits on the shared vmcnt counter).
     {
@@ -598,26 +593,121 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
 #undef PIME_SEG_LOAD
 #undef PIME_SEG_STORE
     }
-    // scalar sums (losses, d/d a_std_log, head bias gradient, target moments): reduced over the wave right where they
-    // are produced and kept in LDS, not in loop-carried registers (which hipcc spills around the MFMA phases)
+}
+
+// The workgroup's sums: per-wave head weight gradients, and the scalar sums (losses, d/d a_std_log, head bias gradient, target
+// moments), which are reduced over the wave right where they are produced and kept in LDS, not in loop-carried registers (which
+// hipcc spills around the MFMA phases)
+template <int T>
+__device__ __forceinline__ void fused_zero_sums(float* __restrict__ lds, const FusedLds& F, const int tid) {
+    float* const hacc = lds + F.hacc;
+    for (int e = tid; e < kFusedWaves * T * 32; e += kFusedThreads) hacc[e] = 0.f;
     double* const wsum = reinterpret_cast<double*>(lds + F.wsum);   // [wave][6]
     if (tid < kFusedWaves * 6) wsum[tid] = 0.0;
+}
 
-#pragma unroll 1
-    for (int group = bid; group < ngroups; group += nb) {
-        // Lane-derived offsets are made loop-variant on purpose: hipcc otherwise hoists ~100 per-lane LDS / global
-        // offsets of the whole body out of this (usually single-trip) loop and spills them.
-        int lane = tid & 63;
-        asm volatile("" : "+v"(lane));
+// The minibatch gather (index -> row -> per-sample inputs): two dependent HBM round trips, started before the weight staging so
+// that the two overlap.  The pair kernel gathers ONCE per group for both nets.
+struct Gathered {
+    bool valid;
+    const float* xrow;
+    float rsum, action, logprob, adv;
+    float x0, x1, x2, x3;   // the first state columns ride along (all of them for the pH / tank envs)
+};
+template <bool WANT_ACTOR, bool WANT_CRITIC>
+__device__ __forceinline__ Gathered fused_gather(const PpoArgs& a, const int tile, const int li) {
+    Gathered g;
+    const int pos = tile * 32 + li;   // tiles past the batch run on clamped rows with dOut = 0
+    g.valid = pos < a.B;
+    const int64_t* const idx = a.indices + (a.index_row ? (size_t)a.index_row[0] * a.B : 0);
+    const long long row = idx[g.valid ? pos : a.B - 1];
+    g.xrow = a.state + (size_t)row * a.D;
+    g.rsum = WANT_CRITIC ? a.r_sum[row] : 0.f;
+    g.action = WANT_ACTOR ? a.action[row] : 0.f;
+    g.logprob = WANT_ACTOR ? a.logprob[row] : 0.f;
+    g.adv = WANT_ACTOR ? a.adv[row] : 0.f;
+    g.x0 = g.x1 = g.x2 = g.x3 = 0.f;
+    if (a.D > 0) g.x0 = g.xrow[0];
+    if (a.D > 1) g.x1 = g.xrow[1];
+    if (a.D > 2) g.x2 = g.xrow[2];
+    if (a.D > 3) g.x3 = g.xrow[3];
+    return g;
+}
+// the group's states into LDS: xs [wave][sample][D], and the padded rows of first_grad_valu (xsp).  rs: NULL, or the pair kernel's
+// [wave][32] segment that parks the critic's targets while the actor's body runs (a VGPR live across that body would be spilled)
+__device__ __forceinline__ void fused_gather_store(const PpoArgs& a, const Gathered& g, float* __restrict__ xs,
+                                                   float* __restrict__ xsp, float* __restrict__ rs, const int wave,
+                                                   const int li, const int h) {
+    const float x0 = g.x0, x1 = g.x1, x2 = g.x2, x3 = g.x3;
+    int D = a.D;
+    asm volatile("" : "+s"(D));   // per group: the column tests below are not hoisted out of the group loop as per-lane 0 / 1 registers
+    const float* xrow = g.xrow;
+    if (h == 0) {
+        float* xw = xs + (wave * 32 + li) * D;
+        if (D > 0) xw[0] = x0;
+        if (D > 1) xw[1] = x1;
+        if (D > 2) xw[2] = x2;
+        if (D > 3) xw[3] = x3;
+        for (int c = 4; c < D; ++c) xw[c] = xrow[c];
+        if (const int P = first_valu_pad(D)) {   // padded copy: columns [0, D) the state, column D the constant 1
+            auto col = [&](int c, float v) { return c < D ? v : (c == D ? 1.f : 0.f); };
+            float4* xp = reinterpret_cast<float4*>(xsp + (wave * 32 + li) * P);
+            xp[0] = make_float4(col(0, x0), col(1, x1), col(2, x2), col(3, x3));
+            if (P == 8)
+                xp[1] = make_float4(col(4, D > 4 ? xrow[4] : 0.f), col(5, D > 5 ? xrow[5] : 0.f),
+                                    col(6, D > 6 ? xrow[6] : 0.f), col(7, 0.f));
+        }
+        if (rs) rs[wave * 32 + li] = g.rsum;
+    }
+}
+
+// The forward images of a net, in the order the layers read them; each layer waits for its own (fused_group's counted waits)
+template <int T, int KIND>
+__device__ __forceinline__ void fused_issue_images(const PpoArgs& a, float* __restrict__ wbuf, float* __restrict__ X, const int tid) {
+    constexpr int H = T / 2 > 0 ? T / 2 : 1;
+    constexpr int NI_TT = T * T * 1024 / (kFusedThreads * 4), NI_TH = T * H * 1024 / (kFusedThreads * 4);   // 8 KB pieces
+    static_assert(T * H * 1024 % (kFusedThreads * 4) == 0, "image = whole 8 KB pieces");
+    const MlpLayout L = mlp_layout(KIND, a.D, a.Di, T * 32);
+    if constexpr (KIND == MLP_MODULAR_ACTOR) {
+        dma_image<NI_TH>(X, a.img_fwd + L.off[1], tid);
+        dma_image<NI_TH>(X + T * H * 1024, a.img_fwd + L.off[4], tid);
+        dma_image<NI_TT>(wbuf, a.img_fwd + L.off[6], tid);
+    } else {
+        dma_image<NI_TT>(wbuf, a.img_fwd + L.off[1], tid);
+        dma_image<NI_TT>(X, a.img_fwd + L.off[3], tid);
+    }
+}
+
+// One 256-sample group of one net: forward, loss gradient, backward chain and weight gradients (into the workgroup's slab `bid`).
+// On entry the group's states are in LDS and the net's forward images are in flight (fused_issue_images' order).  `lane` comes
+// from the caller made opaque per group: hipcc otherwise hoists ~100 per-lane LDS / global offsets of the whole body out of the
+// (usually single-trip) group loop and spills them.  w_dead(): called once where the actor bodies are done with the W image for
+// good (only on the vector-ALU first-layer path, D <= kFirstValuMaxD; never by the critic's body).
+template <int T, int KIND, class Hook = NoHook>
+__device__ __forceinline__ void fused_group(const PpoArgs& a, float* __restrict__ lds, const FusedLds& F, const int bid,
+                                            const int group, const int lane, const int wave, const bool valid,
+                                            const float in_rsum, const float in_action, const float in_logprob,
+                                            const float in_adv, const float asl, const Hook& w_dead = Hook()) {
+    constexpr bool MODULAR = KIND == MLP_MODULAR_ACTOR;
+    constexpr bool CRITIC = KIND == MLP_CRITIC;
+    constexpr int ACT = CRITIC ? 0 : 1;
+    constexpr int H = T / 2 > 0 ? T / 2 : 1;
+    constexpr int md = T * 32;
+    const int tid = wave * 64 + lane;
+    const int ntiles = (a.B + 31) / 32, ngroups = (ntiles + kFusedWaves - 1) / kFusedWaves;
+    const float invB = 1.0f / (float)a.B;
+    [[maybe_unused]] const MlpLayout L = mlp_layout(KIND, a.D, a.Di, md);
+    const BwdLayout Lb = bwd_layout(KIND, a.D, a.Di, md);
+    float* const wbuf = lds + F.wbuf;
+    float* const X = lds + F.x;
+    float* const xs = lds + F.xs;
+    float* const xsp = lds + F.xsp;
+    float* const hacc = lds + F.hacc;   // head weight gradient of the workgroup
+    double* const wsum = reinterpret_cast<double*>(lds + F.wsum);   // [wave][6]
+    [[maybe_unused]] const int Do = a.D - a.Di;
+    {
         const int h = lane >> 5, li = lane & 31;
-        // the minibatch gather (index -> row -> per-sample inputs) is two dependent HBM round trips: start it before
-        // the weight staging so that the two overlap
-        const int tile = group * kFusedWaves + wave;  // tiles past the batch run on clamped rows with dOut = 0
-        const int pos = tile * 32 + li;
-        const bool valid = pos < a.B;
-        const int64_t* const idx = a.indices + (a.index_row ? (size_t)a.index_row[0] * a.B : 0);
-        const long long row = idx[valid ? pos : a.B - 1];
-        const float* xrow = a.state + (size_t)row * a.D;
+        const int tile = group * kFusedWaves + wave;
         float* st = a.stash + (size_t)tile * T * 1024;
         const float* st0 = a.stash + (size_t)group * kFusedWaves * T * 1024;  // the group's first tile
         // Stash regions 1 (and 2): the FIRST-layer activations (round 3).  Rounds 1-2 recomputed them from the states wherever the
@@ -629,46 +719,9 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
         const float* st1_0 = st0 + region;
         [[maybe_unused]] float* st2 = st + 2 * region;
         [[maybe_unused]] const float* st2_0 = st0 + 2 * region;
-        const float in_rsum = CRITIC ? a.r_sum[row] : 0.f;
-        const float in_action = CRITIC ? 0.f : a.action[row];
-        const float in_logprob = CRITIC ? 0.f : a.logprob[row];
-        const float in_adv = CRITIC ? 0.f : a.adv[row];
-        float x0 = 0.f, x1 = 0.f, x2 = 0.f, x3 = 0.f;   // the first state columns ride along (all of them for the pH / tank envs)
-        if (a.D > 0) x0 = xrow[0];
-        if (a.D > 1) x1 = xrow[1];
-        if (a.D > 2) x2 = xrow[2];
-        if (a.D > 3) x3 = xrow[3];
-        __syncthreads();  // the previous group's backward is done with W / X
-        // the forward images, in the order the layers read them; each layer waits for its own (see the forward below)
         constexpr int NI_TT = T * T * 1024 / (kFusedThreads * 4), NI_TH = T * H * 1024 / (kFusedThreads * 4);   // 8 KB pieces
         constexpr int kStashOps = T * 4;   // vector-memory instructions of one stash_put (vmcnt is an in-order 6-bit counter: the
         //                                   counted waits below name how many YOUNGER operations may stay outstanding)
-        static_assert(T * H * 1024 % (kFusedThreads * 4) == 0, "image = whole 8 KB pieces");
-        if constexpr (MODULAR) {
-            dma_image<NI_TH>(X, a.img_fwd + L.off[1], tid);
-            dma_image<NI_TH>(X + T * H * 1024, a.img_fwd + L.off[4], tid);
-            dma_image<NI_TT>(wbuf, a.img_fwd + L.off[6], tid);
-        } else {
-            dma_image<NI_TT>(wbuf, a.img_fwd + L.off[1], tid);
-            dma_image<NI_TT>(X, a.img_fwd + L.off[3], tid);
-        }
-        if (h == 0) {
-            float* xw = xs + (wave * 32 + li) * a.D;
-            if (a.D > 0) xw[0] = x0;
-            if (a.D > 1) xw[1] = x1;
-            if (a.D > 2) xw[2] = x2;
-            if (a.D > 3) xw[3] = x3;
-            for (int c = 4; c < a.D; ++c) xw[c] = xrow[c];
-            if (const int P = first_valu_pad(a.D)) {   // padded copy: columns [0, D) the state, column D the constant 1
-                auto col = [&](int c, float v) { return c < a.D ? v : (c == a.D ? 1.f : 0.f); };
-                float4* xp = reinterpret_cast<float4*>(xsp + (wave * 32 + li) * P);
-                xp[0] = make_float4(col(0, x0), col(1, x1), col(2, x2), col(3, x3));
-                if (P == 8)
-                    xp[1] = make_float4(col(4, a.D > 4 ? xrow[4] : 0.f), col(5, a.D > 5 ? xrow[5] : 0.f),
-                                        col(6, a.D > 6 ? xrow[6] : 0.f), col(7, 0.f));
-            }
-        }
-        PIME_LDS_BARRIER();   // the states are in LDS (the images are still in flight)
         const float* xl = xs + (wave * 32 + li) * a.D;   // this lane's state row
 
         // ---------------------------------------------------------------------------------- forward + loss gradient
@@ -847,8 +900,8 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
             PIME_LDS_BARRIER();
             if constexpr (T == 4) {
                 // One branch at a time (64 instead of 128 live dZ registers): dX with act'(h1) formed behind its MFMAs,
-                // then that branch's first-layer gradient.  The branch's transposed image (its half of W) is dead by
-                // then and holds the partial sums of the vector form.
+                // then that branch's first-layer gradient (which works in X only: dZ image and partial sums).  The branch's
+                // transposed image (its half of W) is dead by then.
 #pragma unroll
                 for (int br = 0; br < 2; ++br) {
                     const int Din = br ? a.Di : Do, col0 = br ? Do : 0;
@@ -862,7 +915,9 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                     }
                     float* gW = sl + a.poff[br ? 4 : 0], *gb = sl + a.poff[br ? 5 : 1];
                     if (a.D <= kFirstValuMaxD) {
-                        first_grad_valu<T>(X, lane, wave, d1, xsp, a.D, col0, Din, gW, gb, accum);
+                        // (the second branch's dX step above was the last reader of W)
+                        if (br == 1) first_grad_valu<T>(X, lane, wave, d1, xsp, a.D, col0, Din, gW, gb, accum, w_dead);
+                        else first_grad_valu<T>(X, lane, wave, d1, xsp, a.D, col0, Din, gW, gb, accum);
                     } else {
                         f32x16 acc[DwPlan<T, 1>::PER];
                         float bsum;
@@ -891,7 +946,7 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                 }
                 if (a.D <= kFirstValuMaxD) {   // other_net.0, integrator_net.0 on the vector ALUs
                     first_grad_valu<T>(X, lane, wave, *reinterpret_cast<f32x16(*)[T]>(&d1[0]), xsp, a.D, 0, Do,
-                                       sl + a.poff[0], sl + a.poff[1], accum);
+                                       sl + a.poff[0], sl + a.poff[1], accum, w_dead);
                     first_grad_valu<T>(X, lane, wave, *reinterpret_cast<f32x16(*)[T]>(&d1[T]), xsp, a.D, Do, a.Di,
                                        sl + a.poff[4], sl + a.poff[5], accum);
                 } else {
@@ -953,8 +1008,8 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
                 stash_get<T>(st1, lane, hh);                                                        // H1
                 times_act_grad<T, ACT>(d, hh);                                                      // dZ1
             }
-            if (a.D <= kFirstValuMaxD) {   // net.0 on the vector ALUs (W is dead: its LDS holds the partial sums)
-                first_grad_valu<T>(X, lane, wave, d, xsp, a.D, 0, a.D, sl + a.poff[0], sl + a.poff[1], accum);
+            if (a.D <= kFirstValuMaxD) {   // net.0 on the vector ALUs (in X: dZ image and partial sums; W is dead from here on)
+                first_grad_valu<T>(X, lane, wave, d, xsp, a.D, 0, a.D, sl + a.poff[0], sl + a.poff[1], accum, w_dead);
             } else {
                 f32x16 acc[DwPlan<T, 1>::PER];
                 float bsum;
@@ -963,38 +1018,165 @@ __device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restri
             }
         }
     }
+}
 
-    // ---- workgroup totals of the scalar sums, combined in a fixed order (the slabs make the gradients reproducible
-    // bit for bit; only the loss sums, which are for logging, use atomics)
-    __syncthreads();
+// Workgroup totals: the head weight gradient and the scalar sums, combined in a fixed order (the slabs make the gradients
+// reproducible bit for bit; only the loss sums, which are for logging, use atomics).  The caller has put a barrier behind the last
+// group.  accum: add to what the workgroup stored for an earlier group (the pair kernel writes its totals group by group, because
+// its two nets share the sums' LDS).
+template <int T, int KIND>
+__device__ __forceinline__ void fused_totals(const PpoArgs& a, const float* __restrict__ lds, const FusedLds& F, const int bid,
+                                             const int tid, const bool accum) {
+    constexpr int md = T * 32;
+    constexpr int NP = KIND == MLP_MODULAR_ACTOR ? 12 : 8;
+    const float* const hacc = lds + F.hacc;
+    const double* const wsum = reinterpret_cast<const double*>(lds + F.wsum);
     float* const sl = a.slab + (size_t)bid * a.slab_stride;
-    constexpr int NP = MODULAR ? 12 : 8;
     if (tid < md) {   // head weight
         float t = hacc[tid];
         for (int w = 1; w < kFusedWaves; ++w) t += hacc[w * md + tid];
-        sl[a.poff[NP - 2] + tid] = t;
+        float* q = &sl[a.poff[NP - 2] + tid];
+        *q = accum ? *q + t : t;
     }
     if (tid == 0) {
         double t[6] = {0, 0, 0, 0, 0, 0};
         for (int w = 0; w < kFusedWaves; ++w)
             for (int k = 0; k < 6; ++k) t[k] += wsum[w * 6 + k];
-        sl[a.poff[NP - 1]] = (float)t[3];                 // head bias
-        if constexpr (CRITIC) {
+        float* qb = &sl[a.poff[NP - 1]];
+        *qb = accum ? *qb + (float)t[3] : (float)t[3];    // head bias
+        if constexpr (KIND == MLP_CRITIC) {
             atomicAdd(&a.loss_sums[2], (float)t[0]);
             double* mo = reinterpret_cast<double*>(sl + a.poff[NP]);
-            mo[0] = t[4]; mo[1] = t[5];
+            mo[0] = accum ? mo[0] + t[4] : t[4];
+            mo[1] = accum ? mo[1] + t[5] : t[5];
         } else {
             atomicAdd(&a.loss_sums[0], (float)t[0]);
             atomicAdd(&a.loss_sums[1], (float)t[1]);
-            sl[a.poff[NP]] = (float)t[2];                 // d loss / d a_std_log
+            float* qs = &sl[a.poff[NP]];
+            *qs = accum ? *qs + (float)t[2] : (float)t[2];   // d loss / d a_std_log
         }
     }
+}
+
+// One net: the workgroup runs the body on its groups.  bid / nb: this workgroup's index among the nb workgroups that work on THIS
+// net (ppo_fused_kernel: the grid; ppo_fused_dual_kernel: the net's share of a grid that serves both nets)
+template <int T, int KIND>
+__device__ __forceinline__ void ppo_fused_body(const PpoArgs& a, float* __restrict__ lds, const int bid, const int nb) {
+    constexpr bool CRITIC = KIND == MLP_CRITIC;
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntiles = (a.B + 31) / 32, ngroups = (ntiles + kFusedWaves - 1) / kFusedWaves;
+    const FusedLds F = fused_lds(KIND, a.D, a.Di, T);
+    const float asl = CRITIC ? 0.f : a.a_std_log[0];
+    fused_net_setup<T, KIND>(a, lds, F, tid);
+    fused_zero_sums<T>(lds, F, tid);
+#pragma unroll 1
+    for (int group = bid; group < ngroups; group += nb) {
+        int lane = tid & 63;
+        asm volatile("" : "+v"(lane));   // loop-variant on purpose (fused_group)
+        const int h = lane >> 5, li = lane & 31;
+        const Gathered g = fused_gather<!CRITIC, CRITIC>(a, group * kFusedWaves + wave, li);
+        __syncthreads();  // the previous group's backward is done with W / X
+        fused_issue_images<T, KIND>(a, lds + F.wbuf, lds + F.x, tid);
+        fused_gather_store(a, g, lds + F.xs, lds + F.xsp, nullptr, wave, li, h);
+        PIME_LDS_BARRIER();   // the states are in LDS (the images are still in flight)
+        fused_group<T, KIND>(a, lds, F, bid, group, lane, wave, g.valid, g.rsum, g.action, g.logprob, g.adv, asl);
+    }
+    __syncthreads();
+    fused_totals<T, KIND>(a, lds, F, bid, tid, false);
 }
 
 template <int T, int KIND>
 __global__ __launch_bounds__(kFusedThreads) void ppo_fused_kernel(PpoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     ppo_fused_body<T, KIND>(a, lds, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// ---- actor and critic of a group in ONE workgroup ---------------------------------------------------------------------------
+// LDS map of the pair kernel: the actor's map, then the critic's small segments and the [wave][32] targets.  The critic uses the
+// actor's W / X / xs / xsp / hacc / wsum (the same 256 samples; the sums are written out and re-zeroed between the bodies).
+struct PairLds {
+    FusedLds a, c;
+    int rsum, total;
+};
+__host__ __device__ inline PairLds pair_lds(int akind, int D, int Di, int T) {
+    PairLds P{};
+    P.a = fused_lds(akind, D, Di, T);
+    P.c = P.a;
+    const int md = T * 32;
+    int o = P.a.total;
+    auto seg = [&](int& f, int floats) { f = o; o = align4(o + floats); };
+    seg(P.c.bias[0], md);
+    seg(P.c.bias[1], md);
+    P.c.bias[2] = 0;
+    seg(P.c.headw, md);
+    seg(P.c.headb, 4);
+    seg(P.rsum, kFusedWaves * 32);
+    seg(P.c.first0, md * (D + 1));
+    P.c.first1 = 0;
+    P.total = P.c.total = o;
+    return P;
+}
+
+// Workgroup `bid` runs, for each of its groups, the actor's body and then the critic's on the same 8 tiles.  Against the dual
+// kernel (an actor workgroup retires, a critic workgroup is dispatched on the compute unit and pays a full preamble with the
+// matrix pipe idle) the group is gathered ONCE, the critic's small segments are loaded once per kernel beside the actor's, and the
+// critic's two forward images are started behind the actor's tail: net.2's when the actor's last dX step has read W (w_dead),
+// net.4's when its first-layer gradient is done with X -- so the critic's first layer starts with no exposed round trip.
+// Slab indices and layout, stash tile indexing and the order of every sum of a group are those of the single bodies; a workgroup
+// with ONE group (every batch up to 256 x 256 samples) produces the same bits as the dual kernel.  With several groups the
+// workgroup totals (head weight / bias, scalars) are added group by group instead of wave by wave.
+template <int T, int AKIND>
+__global__ __launch_bounds__(kFusedThreads) void ppo_fused_pair_kernel(PpoArgs actor, PpoArgs critic) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int NI_TT = T * T * 1024 / (kFusedThreads * 4);
+    const int bid = (int)blockIdx.x, nb = (int)gridDim.x;
+    const int tid0 = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    const int ntiles = (actor.B + 31) / 32, ngroups = (ntiles + kFusedWaves - 1) / kFusedWaves;
+    const PairLds P = pair_lds(AKIND, actor.D, actor.Di, T);
+    float* const wbuf = lds + P.a.wbuf;
+    float* const X = lds + P.a.x;
+    float* const rs = lds + P.rsum;
+    const MlpLayout Lc = mlp_layout(MLP_CRITIC, critic.D, critic.Di, T * 32);
+    const float asl0 = actor.a_std_log[0];
+    fused_net_setup<T, AKIND>(actor, lds, P.a, tid0);
+    fused_net_setup<T, MLP_CRITIC>(critic, lds, P.c, tid0);
+    const bool early_w = actor.D <= kFirstValuMaxD;   // the actor's body calls w_dead
+#pragma unroll 1
+    for (int group = bid; group < ngroups; group += nb) {
+        const bool accum = group != bid;
+        // loop-variant on purpose (fused_group), the thread index too: everything derived from it (totals' slab addresses, the
+        // zeroing, the DMA offsets) would otherwise be hoisted out of the loop and spilled
+        int tid = tid0;
+        asm volatile("" : "+v"(tid));
+        const int lane = tid & 63;
+        float asl = asl0;
+        asm volatile("" : "+s"(asl));
+        const Gathered g = fused_gather<true, true>(actor, group * kFusedWaves + wave, lane & 31);
+        __syncthreads();  // the previous group's critic is done with W / X, its totals have been read
+        fused_zero_sums<T>(lds, P.a, tid);
+        fused_issue_images<T, AKIND>(actor, wbuf, X, tid);
+        fused_gather_store(actor, g, lds + P.a.xs, lds + P.a.xsp, rs, wave, lane & 31, lane >> 5);
+        PIME_LDS_BARRIER();   // the states are in LDS (the images are still in flight)
+        fused_group<T, AKIND>(actor, lds, P.a, bid, group, lane, wave, g.valid, 0.f, g.action, g.logprob, g.adv, asl,
+                              [&]() { dma_image<NI_TT>(wbuf, critic.img_fwd + Lc.off[1], tid); });
+        PIME_LDS_BARRIER();   // the actor is done with X (and W); its sums are complete
+        // the critic's forward images, in fused_issue_images' order: net.2's (unless it is in flight already), then net.4's
+        if (!early_w) dma_image<NI_TT>(wbuf, critic.img_fwd + Lc.off[1], tid);
+        dma_image<NI_TT>(X, critic.img_fwd + Lc.off[3], tid);
+        fused_totals<T, AKIND>(actor, lds, P.a, bid, tid, accum);
+        PIME_LDS_BARRIER();   // the totals have been read
+        int tid_c = tid0;
+        asm volatile("" : "+v"(tid_c));
+        fused_zero_sums<T>(lds, P.c, tid_c);   // (ordered before the critic's first sum by the barriers of its forward)
+        const int lane_c = tid_c & 63;
+        const bool valid = (group * kFusedWaves + wave) * 32 + (lane_c & 31) < critic.B;
+        const float rsum = rs[wave * 32 + (lane_c & 31)];
+        fused_group<T, MLP_CRITIC>(critic, lds, P.c, bid, group, lane_c, wave, valid, rsum, 0.f, 0.f, 0.f, 0.f);
+        PIME_LDS_BARRIER();   // the critic's sums are complete
+        fused_totals<T, MLP_CRITIC>(critic, lds, P.c, bid, tid_c, accum);
+    }
 }
 
 // Both nets of an optimizer step in ONE launch: workgroups [0, na) run the actor's body, [na, na + nc) the critic's.  The two
@@ -1330,15 +1512,38 @@ static int launch_dual(const PpoArgs& actor, const PpoArgs& critic, hipStream_t 
     return PIME_OK;
 }
 
-// Actor and critic of the same width in one launch (see ppo_fused_dual_kernel); PIME_ERR_ARG if there is no instantiation.
+bool fused_pair_fits(int actor_kind, int D, int Di, int md);
+
+template <int T, int AKIND>
+static int launch_pair(const PpoArgs& actor, const PpoArgs& critic, hipStream_t s) {
+    const size_t lds_bytes = sizeof(float) * (size_t)pair_lds(AKIND, actor.D, actor.Di, T).total;
+    static LdsLimit lds_limit;  // per instantiation
+    PIME_RAISE_LDS(lds_limit, (ppo_fused_pair_kernel<T, AKIND>), 160 * 1024);
+    hipLaunchKernelGGL((ppo_fused_pair_kernel<T, AKIND>), dim3(fused_grid(actor.B)), dim3(kFusedThreads), lds_bytes, s, actor, critic);
+    PIME_HIP_TRY(hipGetLastError());
+    return PIME_OK;
+}
+
+// Actor and critic of the same width in one launch: ppo_fused_pair_kernel (a group's two nets in one workgroup) where its merged
+// LDS map fits and both nets see the same batch, else ppo_fused_dual_kernel (one workgroup per net and group); PIME_ERR_ARG if
+// there is no instantiation.
 int launch_ppo_fused_dual(int actor_kind, int md, const PpoArgs& actor, const PpoArgs& critic, hipStream_t s) {
     const int T = md / 32;
-#define PIME_DUAL(TT, KK) \
-    if (T == TT && actor_kind == KK) return launch_dual<TT, KK>(actor, critic, s);
+    const bool pair = actor.B == critic.B && actor.D == critic.D && fused_pair_fits(actor_kind, actor.D, actor.Di, md);
+#define PIME_DUAL(TT, KK)                    \
+    if (T == TT && actor_kind == KK)          \
+        return pair ? launch_pair<TT, KK>(actor, critic, s) : launch_dual<TT, KK>(actor, critic, s);
     PIME_DUAL(4, MLP_MODULAR_ACTOR) PIME_DUAL(4, MLP_PLAIN_ACTOR) PIME_DUAL(2, MLP_MODULAR_ACTOR) PIME_DUAL(2, MLP_PLAIN_ACTOR)
 #undef PIME_DUAL
     set_error("no dual fused PPO instantiation for actor kind %d width %d", actor_kind, md);
     return PIME_ERR_ARG;
+}
+
+// Does the pair kernel serve an actor of this kind beside a critic of the same width and state?  (else: the dual kernel)
+bool fused_pair_fits(int actor_kind, int D, int Di, int md) {
+    const int T = md / 32;
+    if (!(T == 2 || T == 4) || !(actor_kind == MLP_MODULAR_ACTOR || actor_kind == MLP_PLAIN_ACTOR)) return false;
+    return sizeof(float) * (size_t)pair_lds(actor_kind, D, Di, T).total <= 160 * 1024;
 }
 
 // Does the kernel's LDS map fit?  (wide observations, e.g. the stacked water tank, do not: the caller then uses the
