@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 22
+#define PIME_ABI_VERSION 23
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -284,6 +284,21 @@ int32_t pime_ppo_fused_grid(int32_t B);
 /* 1 if pime_ppo_minibatch_grad / _step serve an actor of this kind and a critic of the same width on the same D-float state with
  * the pair kernel (a group's actor and critic in one workgroup), 0 if another kernel serves them. */
 int pime_ppo_pair_fits(int32_t actor_kind, int32_t D, int32_t Di, int32_t md);
+/* Workgroups (= gradient slabs) of the streamed 16-tile family for a net of this shape and a minibatch of B: one per 64-sample
+ * group up to a cap that depends on the net's LDS map; 0 (and an error text) for a shape the family has no kernel for. */
+int32_t pime_ppo_grid16(int32_t kind, int32_t B, int32_t md, int32_t D, int32_t Di);
+/* Host-only: which kernels pime_ppo_minibatch_grad / _step run for an actor of this kind and width beside a critic of width
+ * critic_md on the same D-float state -- computed by the function that the two calls themselves dispatch on.  route[0] / route[1]:
+ * the actor's / the critic's family (PIME_PPO_FAMILY_*); route[2]: the launch form (PIME_PPO_LAUNCH_*) of the nets on the
+ * LDS-resident family.  The answer follows the process's PIME_MLP16 setting, as the calls do. */
+#define PIME_PPO_FAMILY_16TILE 0 /* streamed 16-tile kernels (csrc/mlp16.hip), per-workgroup slabs */
+#define PIME_PPO_FAMILY_LDS 1    /* LDS-resident fused kernels (csrc/ppo_fused.hip), per-workgroup slabs */
+#define PIME_PPO_FAMILY_SPLIT 2  /* net + dW pipeline (csrc/ppo_train.hip), float atomics */
+#define PIME_PPO_FAMILY_NONE 3   /* no kernel (the LDS map of the 16-tile kernel does not fit): the query and the calls return an error */
+#define PIME_PPO_LAUNCH_SINGLE 0 /* every net in a launch of its own */
+#define PIME_PPO_LAUNCH_DUAL 1   /* ppo_fused_dual_kernel: one launch, one workgroup per net and group */
+#define PIME_PPO_LAUNCH_PAIR 2   /* ppo_fused_pair_kernel: one launch, a group's actor and critic in one workgroup */
+int pime_ppo_route(int32_t actor_kind, int32_t D, int32_t Di, int32_t actor_md, int32_t critic_md, int32_t* route);
 int pime_ppo_pack_bwd(int32_t kind, int32_t D, int32_t Di, int32_t md, const float* const* params, float* image,
                       pime_stream stream);
 /* Re-packs img_fwd and img_bwd of both nets from their `params` in ONE launch (after every optimizer step; the four

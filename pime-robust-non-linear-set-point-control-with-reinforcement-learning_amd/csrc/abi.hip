@@ -97,7 +97,7 @@ inline int stash_tiles_of(int kind, int md) { return (kind == 2 ? 6 : 5) * (md /
 int launch_pack_bwd(int, int, int, int, const float* const*, float*, hipStream_t);
 int launch_ppo_net(int, int, const PpoArgs&, hipStream_t);
 int launch_ppo_fused(int, int, const PpoArgs&, hipStream_t);
-int launch_ppo_fused_dual(int, int, const PpoArgs&, const PpoArgs&, hipStream_t);
+int launch_ppo_fused_dual(int, int, const PpoArgs&, const PpoArgs&, bool pair, hipStream_t);
 int64_t fused_stash_floats(int, int, int);
 bool fused_fits(int, int, int, int);
 bool fused_pair_fits(int, int, int, int);
@@ -110,6 +110,7 @@ bool family16(int, int);
 bool family16_grad(int, int, int, int);
 int64_t ppo_fwd_image_floats(int, int, int, int);
 int grid16(int, int, int, int, int);
+bool ppo16_fits(int, int, int, int);
 int launch_pack16(const PackArgs&, float*, float*, hipStream_t);
 int launch_pack16_b3(const PackArgs&, float*, hipStream_t);
 bool b3_grad(int, int, int, int);
@@ -675,10 +676,55 @@ int64_t pime_ppo_workspace_floats(int32_t kind, int32_t B, int32_t md) {
     return ppo_workspace_floats(kind, B, md);
 }
 
+// Which kernel serves which net of a minibatch gradient, and in which launch form.  The ONE place that decides it:
+// minibatch_impl dispatches on the answer, pime_ppo_route and pime_ppo_pair_fits report it.
+//   16TILE the streamed 16-tile family (mlp16.hip): width 256, and 64 / 128 on observations too wide for LDS; slabs
+//   LDS    the LDS-resident kernel (ppo_fused.hip): 64 / 128 while its LDS map fits; slabs
+//   SPLIT  the net + dW pipeline (ppo_train.hip, float atomics): a modular actor on a wide observation
+//   NONE   no kernel: a net of the 16-tile family whose LDS map does not fit (the calls refuse it, the query says so)
+// Both nets on the LDS-resident kernel and of one width: ONE launch serves them (ppo_fused_pair_kernel where its merged LDS map
+// fits -- pH and tank observations do --, else ppo_fused_dual_kernel); every other combination launches each net by itself.
+struct PpoRoute {
+    int family[2];   // index 0 = critic, 1 = actor: PIME_PPO_FAMILY_*
+    int launch;      // PIME_PPO_LAUNCH_*
+};
+static PpoRoute ppo_route(int actor_kind, int D, int Di, int actor_md, int critic_md) {
+    PpoRoute r{};
+    const int kind[2] = {PIME_MLP_CRITIC, actor_kind}, di[2] = {0, Di}, md[2] = {critic_md, actor_md};
+    for (int k = 0; k < 2; ++k) {
+        if (family16_grad(kind[k], md[k], D, di[k])) r.family[k] = ppo16_fits(kind[k], md[k], D, di[k]) ? PIME_PPO_FAMILY_16TILE : PIME_PPO_FAMILY_NONE;
+        else r.family[k] = fused_fits(kind[k], D, di[k], md[k]) ? PIME_PPO_FAMILY_LDS : PIME_PPO_FAMILY_SPLIT;
+    }
+    r.launch = PIME_PPO_LAUNCH_SINGLE;
+    if (r.family[0] == PIME_PPO_FAMILY_LDS && r.family[1] == PIME_PPO_FAMILY_LDS && critic_md == actor_md)
+        r.launch = fused_pair_fits(actor_kind, D, Di, actor_md) ? PIME_PPO_LAUNCH_PAIR : PIME_PPO_LAUNCH_DUAL;
+    return r;
+}
+
 int pime_ppo_pair_fits(int32_t actor_kind, int32_t D, int32_t Di, int32_t md) {
-    if (family16_grad(actor_kind, md, D, Di) || family16_grad(PIME_MLP_CRITIC, md, D, 0)) return 0;
-    if (!fused_fits(actor_kind, D, Di, md) || !fused_fits(PIME_MLP_CRITIC, D, 0, md)) return 0;
-    return fused_pair_fits(actor_kind, D, Di, md) ? 1 : 0;
+    if (mlp_check(actor_kind, D, Di, md) != PIME_OK || actor_kind == PIME_MLP_CRITIC || actor_kind == PIME_MLP_SAC_ACTOR) return 0;
+    return ppo_route(actor_kind, D, Di, md, md).launch == PIME_PPO_LAUNCH_PAIR ? 1 : 0;
+}
+
+int pime_ppo_route(int32_t actor_kind, int32_t D, int32_t Di, int32_t actor_md, int32_t critic_md, int32_t* route) {
+    PIME_REQUIRE(route != nullptr, "pime_ppo_route: NULL route");
+    PIME_REQUIRE(actor_kind == PIME_MLP_PLAIN_ACTOR || actor_kind == PIME_MLP_MODULAR_ACTOR, "pime_ppo_route: actor kind %d", actor_kind);
+    if (int rc = mlp_check(actor_kind, D, Di, actor_md)) return rc;
+    if (int rc = mlp_check(PIME_MLP_CRITIC, D, 0, critic_md)) return rc;
+    const PpoRoute r = ppo_route(actor_kind, D, Di, actor_md, critic_md);
+    route[0] = r.family[1]; route[1] = r.family[0]; route[2] = r.launch;
+    PIME_REQUIRE(r.family[0] != PIME_PPO_FAMILY_NONE && r.family[1] != PIME_PPO_FAMILY_NONE,
+                 "pime_ppo_route: no gradient kernel for the %s (state_dim %d, integrator_dim %d, widths %d / %d): its LDS map does not fit",
+                 r.family[1] == PIME_PPO_FAMILY_NONE ? "actor" : "critic", D, Di, actor_md, critic_md);
+    return PIME_OK;
+}
+
+int32_t pime_ppo_grid16(int32_t kind, int32_t B, int32_t md, int32_t D, int32_t Di) {
+    if (B < 1 || mlp_check(kind, D, Di, md) != PIME_OK || kind == PIME_MLP_SAC_ACTOR) {
+        if (B < 1) set_error("pime_ppo_grid16: B=%d", B);
+        return 0;
+    }
+    return grid16(kind, B, md, D, Di);
 }
 
 int32_t pime_ppo_fused_grid(int32_t B) {
@@ -1053,19 +1099,15 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
     PIME_REQUIRE(actor->D == critic->D, "actor and critic state_dim differ");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DwArgs dw{};
-    // Which kernel serves which net (index 0 = critic, 1 = actor):
-    //   F16   the streamed 16-tile family (mlp16.hip): width 256, and 64 / 128 on observations too wide for FUSED; slabs
-    //   FUSED the LDS-resident kernel (ppo_fused.hip): 64 / 128 while its LDS map fits; slabs
-    //   SPLIT the net + dW pipeline (ppo_train.hip, float atomics): a modular actor on a wide observation
+    // Which kernel serves which net (index 0 = critic, 1 = actor) and in which launch form: ppo_route above.
     // Slab nets are finished by ppo_grad_reduce_kernel (which also derives the critic scale); a split critic by critic_scale_kernel.
-    enum { F16, FUSED, SPLIT };
+    enum { F16 = PIME_PPO_FAMILY_16TILE, FUSED = PIME_PPO_FAMILY_LDS, SPLIT = PIME_PPO_FAMILY_SPLIT };
     const pime_ppo_net* nets[2] = {critic, actor};
-    int mode[2];
-    for (int k = 0; k < 2; ++k) {
-        const pime_ppo_net* n = nets[k];
-        if (family16_grad(n->kind, n->md, n->D, n->Di)) mode[k] = F16;
-        else mode[k] = fused_fits(n->kind, n->D, n->Di, n->md) ? FUSED : SPLIT;
-    }
+    const PpoRoute route = ppo_route(actor->kind, actor->D, actor->Di, actor->md, critic->md);
+    const int mode[2] = {route.family[0], route.family[1]};
+    PIME_REQUIRE(mode[0] != PIME_PPO_FAMILY_NONE && mode[1] != PIME_PPO_FAMILY_NONE,
+                 "%s: no gradient kernel for the %s (state_dim %d, widths %d / %d): its LDS map does not fit",
+                 opt ? "pime_ppo_minibatch_step" : "pime_ppo_minibatch_grad", mode[1] == PIME_PPO_FAMILY_NONE ? "actor" : "critic", actor->D, actor->md, critic->md);
     const bool any_split = mode[0] == SPLIT || mode[1] == SPLIT, any_slab = mode[0] != SPLIT || mode[1] != SPLIT;
     PIME_REQUIRE(!(b->dp_moments && mode[0] == SPLIT), "pime_ppo_minibatch_grad: dp_moments needs the critic on a slab kernel (it takes the split pipeline here)");
     PIME_REQUIRE(!(b->dp_moments && opt), "pime_ppo_minibatch_step: dp_moments with a fused optimizer step (the all-reduce has to come first)");
@@ -1093,9 +1135,7 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
         }
     }
     PpoArgs slab_args[2];
-    // both nets on the LDS-resident fused kernel and of one width: ONE launch serves them (ppo_fused_pair_kernel where its merged LDS
-    // map fits -- pH and tank observations do --, else ppo_fused_dual_kernel)
-    const bool dual = mode[0] == FUSED && mode[1] == FUSED && critic->md == actor->md;
+    const bool dual = route.launch != PIME_PPO_LAUNCH_SINGLE;   // one launch serves both nets (pair or dual kernel)
     for (int k = 0; k < 2; ++k) {
         const pime_ppo_net* n = nets[k];
         PpoArgs a{};
@@ -1114,7 +1154,7 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
         int psize[12];
         if (mode[k] == F16) {
             a.slab = n->workspace;
-            a.slab_stride = n->kind == PIME_MLP_MODULAR_ACTOR ? slab_layout16m(n->md, a.poff, psize) : slab_layout16(n->D, n->md, a.poff, psize);
+            a.slab_stride = n->kind == PIME_MLP_MODULAR_ACTOR ? slab_layout16m(n->D, n->Di, n->md, a.poff, psize) : slab_layout16(n->D, n->md, a.poff, psize);
             slab_args[k] = a;
             if (int rc = launch_ppo16(n->kind, n->md, a, s)) return rc;
         } else if (mode[k] == FUSED) {
@@ -1123,7 +1163,7 @@ static int minibatch_impl(const pime_ppo_net* actor, const pime_ppo_net* critic,
             slab_args[k] = a;
             if (dual) {
                 if (k == 1)
-                    if (int rc = launch_ppo_fused_dual(actor->kind, actor->md, slab_args[1], slab_args[0], s)) return rc;
+                    if (int rc = launch_ppo_fused_dual(actor->kind, actor->md, slab_args[1], slab_args[0], route.launch == PIME_PPO_LAUNCH_PAIR, s)) return rc;
             } else if (int rc = launch_ppo_fused(n->kind, n->md, a, s)) return rc;
         } else {
             slab_args[k] = a;

@@ -1421,7 +1421,7 @@ struct Lds16M {
     int w0o, b0o, b1o, w0i, b0i, b1i, bn, w3, b3, wsum, region, total;
 };
 template <int T>
-__host__ __device__ inline Lds16M lds16m(int D, int Di, bool grad) {
+__host__ __device__ inline Lds16M lds16m(int D, int Di, bool grad, bool b3 = true) {   // b3 = false: the f32 kernels' region (it is the LAST segment: every offset is the same)
     const int md = T * 16;
     const Layout16M L = layout16m(D, Di, md);
     Lds16M S{};
@@ -1436,10 +1436,10 @@ __host__ __device__ inline Lds16M lds16m(int D, int Di, bool grad) {
     if (grad) {
         constexpr int RT = T <= 8 ? 4 : 2;
         int dwf = mx(dw16_lds_floats<T, T, RT>(), mx(dw16_lds_floats<T / 2, T, RT>(), dw16_lds_floats<T, 1, RT>()));
-        if constexpr (T == 4 * k16Waves) dwf = mx(dwf, mx(Dw16Sliced<T>::FLOATS, Dw16SlicedB3<T>::FLOATS));
+        if constexpr (T == 4 * k16Waves) dwf = mx(dwf, mx(Dw16Sliced<T>::FLOATS, b3 ? Dw16SlicedB3<T>::FLOATS : 0));
         region = mx(region, mx(dwf, k16Waves * md));
         if constexpr (T >= 8)
-            region = mx(region, mx(layer16_b3_lds_floats<T, T>(), mx(layer16_b3_lds_floats<T, T / 2>(), layer16_b3_lds_floats<T / 2, T>())));
+            if (b3) region = mx(region, mx(layer16_b3_lds_floats<T, T>(), mx(layer16_b3_lds_floats<T, T / 2>(), layer16_b3_lds_floats<T / 2, T>())));
     }
     seg(S.region, region);
     S.total = o;
@@ -1642,8 +1642,13 @@ __global__ __launch_bounds__(k16Threads, T <= 8 ? 2 : 1) void ppo16m_kernel(PpoA
 #pragma unroll
                 for (int r = 0; r < 4; ++r) d1[t][r] *= act_grad_from_output<ACT>(t1[t][r]);                                         // dZ1
             PIME_NO_HOIST();
-            if (br == 0) dw16<T, 1, RT>(region, lane, wave, PubAcc16<T>{d1, g}, PubX16{xo, g, L.KS0o, 16}, sl + a.poff[0], sl + a.poff[1], accum);
-            else dw16<T, 1, RT>(region, lane, wave, PubAcc16<T>{d1, g}, PubX16{xi, g, L.KS0i, 16}, sl + a.poff[4], sl + a.poff[5], accum);
+            // a tower that reads more than 16 floats has two column tiles (slab_layout16m: tb16), like the plain net's first layer
+            const float(&xt)[8] = br == 0 ? xo : xi;
+            const int ks0 = br == 0 ? L.KS0o : L.KS0i;
+            if (ks0 <= 4)
+                dw16<T, 1, RT>(region, lane, wave, PubAcc16<T>{d1, g}, PubX16{xt, g, ks0, 16}, sl + a.poff[br ? 4 : 0], sl + a.poff[br ? 5 : 1], accum);
+            else
+                dw16<T, 2, RT>(region, lane, wave, PubAcc16<T>{d1, g}, PubX16{xt, g, ks0, 32}, sl + a.poff[br ? 4 : 0], sl + a.poff[br ? 5 : 1], accum);
             PIME16_BARRIER();   // the next chain layer / the next group writes the region
         }
     }
@@ -1968,12 +1973,18 @@ static int wgs_per_cu(size_t lds_bytes) {
     return by_lds < by_regs ? (by_lds < 1 ? 1 : by_lds) : by_regs;
 }
 
+// LDS of ppo16m_kernel<T, B3>.  The f32 kernel at width 256 asks for its own region only: with the bf16x3 one (120 KB) a plant tower of
+// 29 floats or more -- 32 KB of first-layer image -- would not fit.  grid16, ppo16_fits and the launch all size the kernel by this one function.
+template <int T>
+static size_t lds16m_bytes(int D, int Di, bool b3) {
+    return sizeof(float) * (size_t)lds16m<T>(D, Di, true, b3 || T != 16).total;
+}
 int grid16(int kind, int B, int md, int D, int Di) {
     const int ngroups = (B + k16Group - 1) / k16Group;
     size_t lds = 0;
     int per = 1;
-    if (kind == MLP_MODULAR_ACTOR && md == 128) { lds = sizeof(float) * lds16m<8>(D, Di, true).total; per = wgs_per_cu<8>(lds); }
-    else if (kind == MLP_MODULAR_ACTOR) { lds = sizeof(float) * lds16m<16>(D, Di, true).total; per = wgs_per_cu<16>(lds); }
+    if (kind == MLP_MODULAR_ACTOR && md == 128) { lds = lds16m_bytes<8>(D, Di, b3_grad(kind, md, D, Di)); per = wgs_per_cu<8>(lds); }
+    else if (kind == MLP_MODULAR_ACTOR) { lds = lds16m_bytes<16>(D, Di, b3_grad(kind, md, D, Di)); per = wgs_per_cu<16>(lds); }
     else if (md == 64) { lds = sizeof(float) * lds16<4>(D, true).total; per = wgs_per_cu<4>(lds); }
     else if (md == 128) { lds = sizeof(float) * lds16<8>(D, true).total; per = wgs_per_cu<8>(lds); }
     else { lds = sizeof(float) * lds16<16>(D, true).total; per = wgs_per_cu<16>(lds); }
@@ -2026,10 +2037,21 @@ static int launch_grad16(const PpoArgs& a, hipStream_t s) {
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
+// Does a gradient kernel of this family fit the net?  (launch_ppo16 refuses a net that does not; the route query says so up front)
+bool ppo16_fits(int kind, int md, int D, int Di) {
+    if (kind == MLP_MODULAR_ACTOR) {
+        if (md != 128 && md != 256) return false;
+        const bool b3 = b3_grad(kind, md, D, Di);
+        return (md == 128 ? lds16m_bytes<8>(D, Di, b3) : lds16m_bytes<16>(D, Di, b3)) <= 160 * 1024;
+    }
+    const size_t floats = md == 64 ? lds16<4>(D, true).total : md == 128 ? lds16<8>(D, true).total : lds16<16>(D, true).total;
+    return sizeof(float) * floats <= 160 * 1024;
+}
+
 template <int T, bool B3>
 static int launch_grad16m(const PpoArgs& a, hipStream_t s) {
-    const size_t lds_bytes = sizeof(float) * (size_t)lds16m<T>(a.D, a.Di, true).total;
-    PIME_REQUIRE(lds_bytes <= 160 * 1024, "16-tile modular PPO kernel needs %zu B of LDS", lds_bytes);
+    const size_t lds_bytes = lds16m_bytes<T>(a.D, a.Di, B3);
+    PIME_REQUIRE(lds_bytes <= 160 * 1024, "16-tile modular PPO kernel needs %zu B of LDS (state_dim %d, integrator_dim %d)", lds_bytes, a.D, a.Di);
     static LdsLimit lds_limit;  // per instantiation
     PIME_RAISE_LDS(lds_limit, (ppo16m_kernel<T, B3>), 160 * 1024);
     hipLaunchKernelGGL((ppo16m_kernel<T, B3>), dim3(grid16(MLP_MODULAR_ACTOR, a.B, T * 16, a.D, a.Di)), dim3(k16Threads), lds_bytes, s, a);

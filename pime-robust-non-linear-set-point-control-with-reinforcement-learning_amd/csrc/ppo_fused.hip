@@ -1428,11 +1428,11 @@ int launch_grad_reduce(const PpoArgs& critic, const PpoArgs& actor, int kind_c, 
     auto add_net = [&](const PpoArgs& a, int kind, int md, bool f16, float* const* grads, int net, int* scalar_off) {
         const int np = kind == MLP_MODULAR_ACTOR ? 12 : 8;
         if (f16 && kind == MLP_MODULAR_ACTOR) {   // slab_layout16m: five block-major matrices
-            slab_layout16m(md, poff, psize);
+            slab_layout16m(a.D, a.Di, md, poff, psize);
             const int T = md / 16, Do = a.D - a.Di;
             for (int i = 0; i < np; ++i) {
-                if (i == 0) add(grads[i], poff[i], psize[i], net, 1, Do, Do);
-                else if (i == 4) add(grads[i], poff[i], psize[i], net, 1, a.Di, a.Di);
+                if (i == 0) add(grads[i], poff[i], psize[i], net, tb16(Do), Do, Do);
+                else if (i == 4) add(grads[i], poff[i], psize[i], net, tb16(a.Di), a.Di, a.Di);
                 else if (i == 2 || i == 6 || i == 8) add(grads[i], poff[i], psize[i], net, T, md, md);
                 else add(grads[i], poff[i], psize[i], net);
             }
@@ -1524,12 +1524,13 @@ static int launch_pair(const PpoArgs& actor, const PpoArgs& critic, hipStream_t 
     return PIME_OK;
 }
 
-// Actor and critic of the same width in one launch: ppo_fused_pair_kernel (a group's two nets in one workgroup) where its merged
-// LDS map fits and both nets see the same batch, else ppo_fused_dual_kernel (one workgroup per net and group); PIME_ERR_ARG if
-// there is no instantiation.
-int launch_ppo_fused_dual(int actor_kind, int md, const PpoArgs& actor, const PpoArgs& critic, hipStream_t s) {
+// Actor and critic of the same width in one launch: ppo_fused_pair_kernel (a group's two nets in one workgroup) where the caller's
+// route says so (`pair`: the merged LDS map fits and both nets see the same batch), else ppo_fused_dual_kernel (one workgroup per
+// net and group); PIME_ERR_ARG if there is no instantiation.
+int launch_ppo_fused_dual(int actor_kind, int md, const PpoArgs& actor, const PpoArgs& critic, bool pair, hipStream_t s) {
     const int T = md / 32;
-    const bool pair = actor.B == critic.B && actor.D == critic.D && fused_pair_fits(actor_kind, actor.D, actor.Di, md);
+    PIME_REQUIRE(!pair || (actor.B == critic.B && actor.D == critic.D && fused_pair_fits(actor_kind, actor.D, actor.Di, md)),
+                 "the pair kernel needs one batch, one state width and a merged LDS map that fits (state_dim %d, width %d)", actor.D, md);
 #define PIME_DUAL(TT, KK)                    \
     if (T == TT && actor_kind == KK)          \
         return pair ? launch_pair<TT, KK>(actor, critic, s) : launch_dual<TT, KK>(actor, critic, s);

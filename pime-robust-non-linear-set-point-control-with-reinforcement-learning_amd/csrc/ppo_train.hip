@@ -565,7 +565,7 @@ int64_t ppo_workspace_floats(int kind, int B, int md) {
         g = g > g2 ? g : g2;
         f16 = (int64_t)g * stride;
     } else if (md == 256 || md == 128) {
-        f16 = (int64_t)grid16(kind, B, md, 4, 1) * slab_layout16m(md, poff, psize);   // (the grid does not depend on the state width)
+        f16 = (int64_t)grid16(kind, B, md, 4, 1) * slab_floats16m_max(md);   // (the grid does not grow with the state width; the slab's upper bound)
     }
     if (md == 256) return f16;
     const int64_t ntiles = ((B + 31) / 32 + 7) / 8 * 8;

@@ -92,14 +92,21 @@ inline int slab_layout16(int D, int md, int* poff, int* psize) {
 }
 
 // The modular actor in the 16-tile family (mlp16.hip: ppo16m_kernel), parameter order of pime_ppo_net (other_net.0, other_net.2,
-// integrator_net.0, integrator_net.2, net.0, net.2; W, b each): the five weight matrices block-major in accumulator order (first
-// layers padded to one 16-column tile), biases and the head in tensor order.
-inline int slab_layout16m(int md, int* poff, int* psize) {
-    const int s[12] = {md * 16, md, (md / 2) * md, md / 2, md * 16, md, (md / 2) * md, md / 2, md * md, md, md, 1};
+// integrator_net.0, integrator_net.2, net.0, net.2; W, b each): the five weight matrices block-major in accumulator order, biases
+// and the head in tensor order.  The first layer of a tower is padded to one 16-column tile, to two where the tower reads more than
+// 16 floats (tb16 below: the kernel's dW round and the slab reduction take the same count).
+inline int tb16(int cols) { return ((cols + 3) & ~3) <= 16 ? 1 : 2; }
+inline int slab_layout16m(int D, int Di, int md, int* poff, int* psize) {
+    const int s[12] = {md * 16 * tb16(D - Di), md, (md / 2) * md, md / 2, md * 16 * tb16(Di), md, (md / 2) * md, md / 2, md * md, md, md, 1};
     int o = 0;
     for (int i = 0; i < 12; ++i) { psize[i] = s[i]; poff[i] = o; o += (s[i] + 3) & ~3; }
     poff[12] = o;
     return o + 4;
+}
+// the largest slab of any (D, Di): what a workspace that is sized without the state width has to hold per workgroup
+inline int slab_floats16m_max(int md) {
+    int poff[13], psize[12];
+    return slab_layout16m(34, 17, md, poff, psize);   // both towers on two tiles (no real net has both: an upper bound)
 }
 
 constexpr int kMaxDwJobs = 16;

@@ -147,9 +147,11 @@ def test_width_256_modular_agent_takes_the_hip_path():
 
 @pytest.mark.parametrize("md,D,B", [(128, 30, 2048), (64, 30, 1000), (128, 12, 4096)])
 def test_wide_observation_gradients_are_deterministic(md, D, B):
-    """Stacking10 / Stacking4 observations at width 64 / 128: too wide for the LDS-resident gradient kernel, served by the
-    16-tile family's slabs (bit-for-bit reproducible; the split pipeline's float atomics were not) -- check_grads asserts both
-    the autograd match and the bitwise repeat."""
+    """Stacking10 / Stacking4 observations at width 64 / 128.  Only (128, 30) is too wide for the LDS-resident gradient kernel and
+    served by the 16-tile family's slabs (bit-for-bit reproducible; the split pipeline's float atomics were not): pime_ppo_route
+    answers the pair kernel for width 64 at every state width up to 32 and the dual kernel for (128, 12) -- the LDS map of
+    width 128 fits up to 13 floats (tests/ppo_cases.py: expected_route, held against the library by
+    tests/test_ppo_cases_cpu.py).  check_grads asserts both the autograd match and the bitwise repeat on whichever family serves."""
     check_grads("resid", md, D, B)
 
 

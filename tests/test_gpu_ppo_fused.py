@@ -1,6 +1,8 @@
 """Fused PPO minibatch-gradient kernels (csrc/ppo_train.hip) against PyTorch fp32 autograd of the reference's loss
 (elegantrl/agent.py:637-655) on the same minibatch.  A floating-point kernel: the checker is a plain torch fp32
-implementation on the same device, with tolerances stated per assertion."""
+implementation on the same device, with tolerances stated per assertion.  The data here are the reference's initialisation
+and a random table (nearly every sample in the linear SmoothL1 branch, no margin to the kinks) at a few shapes; every route,
+first-layer variant and batch regime against a float64 oracle on vetted inputs is tests/test_gpu_ppo_sweep.py."""
 import numpy as np
 import pytest
 import torch

@@ -3,7 +3,10 @@ the critic's targets parked in LDS, its small segments and forward images loaded
 written out and re-zeroed between the two bodies.  The four (actor kind, width) instantiations, at the smallest batches at which
 the merged workgroup can go wrong, against torch fp32 autograd at the bar of test_gpu_ppo_fused.py (3e-4 of each tensor's largest
 entry; loss sums 1e-3-level), plus bit-level properties: reproducibility, independence of what the workspace held, and the Adam
-step fused into the slab reduction."""
+step fused into the slab reduction.  These are the reference's own initialisation and random data at D = 3 and 4; the pair kernel's
+other shapes (width 64 up to D = 32, width 128 at D = 1, 2 and 8 -- the only one whose actor body does not free the weight
+buffer early), batches below a group, NaN in the trajectory rows the indices do not name and frozen parameters are swept against a
+float64 oracle on vetted inputs by tests/test_gpu_ppo_sweep.py."""
 import numpy as np
 import pytest
 import torch
