@@ -1249,6 +1249,25 @@ static int check_offpolicy_net(const char* fn, const pime_td3_net* n, const char
     return PIME_OK;
 }
 
+// the workspace of a step: the critic's slabs, the actor's slabs, then the gathered rows [B][td3_xg_stride(D)] -- written by the critic
+// launch of a table row, read by its actor launch (td3_workspace_floats)
+struct OffpolicyWorkspace { float *slab_c, *slab_a, *xg; };
+static OffpolicyWorkspace carve_offpolicy_workspace(float* workspace, int grid, const Td3SlabLayout& LC, const Td3SlabLayout& LA) {
+    float* const slab_a = workspace + (size_t)grid * LC.stride;
+    return OffpolicyWorkspace{workspace, slab_a, slab_a + (size_t)grid * LA.stride};
+}
+// an apply launch's arguments from the net it steps; the caller sets mode, soft and (SAC's critic) temp
+static Td3ApplyArgs offpolicy_apply_args(const pime_td3_net* n, const Td3SlabLayout& L, const float* slab, int nslabs, float tau, long long row,
+                                         int B, float* loss, int loss_slot, int loss_last) {
+    Td3ApplyArgs a{};
+    a.L = L; a.slab = slab; a.nslabs = nslabs;
+    a.param = n->param; a.target = n->target; a.grad = n->grad; a.exp_avg = n->exp_avg; a.exp_avg_sq = n->exp_avg_sq; a.step = n->step;
+    a.lr = n->lr; a.b1 = n->beta1; a.b2 = n->beta2; a.eps = n->eps; a.tau = tau;
+    a.row = row;
+    a.loss = loss; a.loss_slot = loss_slot; a.inv_B = 1.0f / (float)B; a.loss_last = loss_last;
+    return a;
+}
+
 int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_td3_net* critic, const pime_td3_batch* b, float tau,
                   int32_t update_freq, int32_t soft_mode, int32_t phases, float* workspace, float* loss, pime_stream stream) {
     PIME_REQUIRE(td3_supported(D, 1, md), "pime_td3_step: no kernel for state_dim %d width %d (1 <= D <= %d, width 64 | 128 | 256)", D, md, kTd3MaxD);
@@ -1264,36 +1283,29 @@ int pime_td3_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = td3_grid(b->B), ngroups = (b->B + 15) / 16;
     const Td3SlabLayout LA = td3_actor_slab(D, md), LC = td3_critic_slab(D, md);
-    float* const slab_c = workspace;
-    float* const slab_a = workspace + (size_t)grid * LC.stride;
-    // [B][td3_xg_stride(D)] gathered rows: written by the critic launch of a row, read by its actor launch
-    float* const xg = slab_a + (size_t)grid * LA.stride;
+    const OffpolicyWorkspace w = carve_offpolicy_workspace(workspace, grid, LC, LA);
     Td3Batch tb{b->state, b->other, b->idx, b->nxt, b->noise, (long long)b->row, b->epoch, b->B, b->noise_seed, b->noise_epoch, b->policy_noise, b->noise_clip};
     auto apply = [&](const pime_td3_net* n, const Td3SlabLayout& L, const float* slab, int slot, int mode) {
-        Td3ApplyArgs a{};
-        a.L = L; a.slab = slab; a.nslabs = grid; a.mode = mode;
-        a.param = n->param; a.target = n->target; a.grad = n->grad; a.exp_avg = n->exp_avg; a.exp_avg_sq = n->exp_avg_sq; a.step = n->step;
-        a.lr = n->lr; a.b1 = n->beta1; a.b2 = n->beta2; a.eps = n->eps; a.tau = tau;
-        a.row = (long long)b->row; a.soft = soft;
-        a.loss = loss; a.loss_slot = slot; a.inv_B = 1.0f / (float)b->B; a.loss_last = 2;
+        Td3ApplyArgs a = offpolicy_apply_args(n, L, slab, grid, tau, (long long)b->row, b->B, loss, slot, 2);
+        a.mode = mode; a.soft = soft;
         return launch_td3_apply(a, s);
     };
     if (phases & 1) {
-        Td3GradArgs g{tb, D, actor->target, critic->param, critic->target, slab_c, xg, LC.stride, ngroups};
+        Td3GradArgs g{tb, D, actor->target, critic->param, critic->target, w.slab_c, w.xg, LC.stride, ngroups};
         if (int rc = launch_td3_grad(true, md, g, grid, s)) return rc;
     }
     if (phases & (2 | 16))
-        if (int rc = apply(critic, LC, slab_c, 1, (phases & 16) ? 1 : 0)) return rc;
+        if (int rc = apply(critic, LC, w.slab_c, 1, (phases & 16) ? 1 : 0)) return rc;
     if (phases & 32)
-        if (int rc = apply(critic, LC, slab_c, 1, 2)) return rc;
+        if (int rc = apply(critic, LC, w.slab_c, 1, 2)) return rc;
     if (phases & 4) {
-        Td3GradArgs g{tb, D, actor->param, critic->target, nullptr, slab_a, xg, LA.stride, ngroups};
+        Td3GradArgs g{tb, D, actor->param, critic->target, nullptr, w.slab_a, w.xg, LA.stride, ngroups};
         if (int rc = launch_td3_grad(false, md, g, grid, s)) return rc;
     }
     if (phases & (8 | 64))
-        if (int rc = apply(actor, LA, slab_a, 0, (phases & 64) ? 1 : 0)) return rc;
+        if (int rc = apply(actor, LA, w.slab_a, 0, (phases & 64) ? 1 : 0)) return rc;
     if (phases & 128)
-        if (int rc = apply(actor, LA, slab_a, 0, 2)) return rc;
+        if (int rc = apply(actor, LA, w.slab_a, 0, 2)) return rc;
     return PIME_OK;
 }
 
@@ -1343,32 +1355,26 @@ int pime_sac_step(int32_t D, int32_t md, const pime_td3_net* actor, const pime_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = td3_grid(b->B), ngroups = (b->B + 15) / 16;
     const Td3SlabLayout LA = sac_actor_slab(D, md), LC = td3_critic_slab(D, md);
-    float* const slab_c = workspace;
-    float* const slab_a = workspace + (size_t)grid * LC.stride;
-    float* const xg = slab_a + (size_t)grid * LA.stride;   // [B][8] gathered rows: written by the critic launch of a row, read by its actor launch
+    const OffpolicyWorkspace w = carve_offpolicy_workspace(workspace, grid, LC, LA);
     const SacBatch sb{b->state, b->other, b->idx, b->nxt, b->noise_next, b->noise_pg, (long long)b->row, b->epoch, b->B, b->noise_seed, b->noise_epoch};
     auto apply = [&](const pime_td3_net* n, const Td3SlabLayout& L, const float* slab, int slot, bool is_critic) {
-        Td3ApplyArgs a{};
-        a.L = L; a.slab = slab; a.nslabs = grid; a.mode = 0;
-        a.param = n->param; a.target = n->target; a.grad = n->grad; a.exp_avg = n->exp_avg; a.exp_avg_sq = n->exp_avg_sq; a.step = n->step;
-        a.lr = n->lr; a.b1 = n->beta1; a.b2 = n->beta2; a.eps = n->eps; a.tau = tau;
-        a.row = (long long)b->row; a.soft = is_critic ? 1 : 0;   // the target critic follows on EVERY step; there is no actor target
-        a.loss = loss; a.loss_slot = slot; a.inv_B = 1.0f / (float)b->B; a.loss_last = 4;
+        Td3ApplyArgs a = offpolicy_apply_args(n, L, slab, grid, tau, (long long)b->row, b->B, loss, slot, 4);
+        a.mode = 0; a.soft = is_critic ? 1 : 0;   // the target critic follows on EVERY step; there is no actor target
         if (is_critic) a.temp = {temp->alpha_log, temp->exp_avg, temp->exp_avg_sq, temp->lr, temp->beta1, temp->beta2, temp->eps, temp->target_entropy};
         return launch_td3_apply(a, s);
     };
     if (phases & 1) {
-        SacGradArgs g{sb, D, actor->param, critic->param, critic->target, temp->alpha_log, slab_c, xg, LC.stride, ngroups};
+        SacGradArgs g{sb, D, actor->param, critic->param, critic->target, temp->alpha_log, w.slab_c, w.xg, LC.stride, ngroups};
         if (int rc = launch_sac_grad(true, md, g, grid, s)) return rc;
     }
     if (phases & 2)
-        if (int rc = apply(critic, LC, slab_c, 1, true)) return rc;
+        if (int rc = apply(critic, LC, w.slab_c, 1, true)) return rc;
     if (phases & 4) {
-        SacGradArgs g{sb, D, actor->param, critic->target, nullptr, temp->alpha_log, slab_a, xg, LA.stride, ngroups};
+        SacGradArgs g{sb, D, actor->param, critic->target, nullptr, temp->alpha_log, w.slab_a, w.xg, LA.stride, ngroups};
         if (int rc = launch_sac_grad(false, md, g, grid, s)) return rc;
     }
     if (phases & 8)
-        if (int rc = apply(actor, LA, slab_a, 0, false)) return rc;
+        if (int rc = apply(actor, LA, w.slab_a, 0, false)) return rc;
     return PIME_OK;
 }
 

@@ -1,21 +1,22 @@
 // One SAC optimizer step as FOUR launches: critic gradients (+ the batch sum of the policy-gradient sample's "logprob"), critic
 // apply (+ the temperature's Adam step), actor gradients, actor apply.
 //
-// replaces (reference, /root/reference/elegantrl/agent.py): AgentSAC.update_net's loop body (:442-468) -- get_obj_critic_raw
+// replaces (reference, elegantrl/agent.py): AgentSAC.update_net's loop body (:442-468) -- get_obj_critic_raw
 // (:519-527: minibatch gather, act.get_action_logprob(next_s) on the ONLINE actor (net.py:207-239), twin target heads + min + the
 // entropy term, online twin forward, SmoothL1 x 2), obj_critic.backward(), cri_optimizer.step(), soft_update(cri_target) on every
 // step (:116-124), act.get_action_logprob(state), obj_alpha and alpha_optimizer.step() (:452-458), alpha = exp(alpha_log),
 // obj_actor = -(min(cri_target.get_q1_q2(state, a_pg)) + logprob * alpha).mean() (:461-463), obj_actor.backward(),
 // act_optimizer.step().
 //
-// The decomposition is td3_fused.hip's (td3_device.hpp): a workgroup owns a 16-sample tile, its waves split every layer's output
-// features, activations meet in LDS as chain images, md x md weights go global -> registers a layer ahead, every workgroup leaves a
-// partial-gradient slab and td3_apply_kernel reduces the slabs in slab order, applies Adam and the soft update.  What SAC adds:
-//   * the stochastic actor: ReLU, Hardswish, Hardswish body (the backward needs the Hardswish PRE-activations: they stay in
-//     registers, the chain images hold the activations for the weight gradients), a mean and a log-std head, the re-parameterised
-//     sample a = tanh(avg + exp(clamp(ls, -20, 2)) eps) and its "logprob" -- the reference's name for the NEGATIVE log-density
-//     ls + log sqrt(2 pi) + eps^2 / 2 + log(1.000001 - a^2), used with that sign throughout.  (The reference writes the third term as
-//     ((avg - u) / std)^2 / 2; its derivatives with respect to avg and std cancel, so nothing is propagated through it.)
+// The decomposition is the TD3 step's (td3_fused.hip's header describes it), and so is most of the device code: the tile context, the
+// gather, the twin target heads, the online twin-critic step, the target critic's forward and backward to the action, the actor
+// body's backward and the launch dispatch are the shared pieces of td3_device.hpp; the apply launches are td3_apply_kernel.  What is
+// this file's own:
+//   * the stochastic actor (sac_actor_fwd): ReLU, Hardswish, Hardswish body (the backward needs the Hardswish PRE-activations: they
+//     stay in registers, the chain images hold the activations for the weight gradients), a mean and a log-std head, the
+//     re-parameterised sample a = tanh(avg + exp(clamp(ls, -20, 2)) eps) and its "logprob" -- the reference's name for the NEGATIVE
+//     log-density ls + log sqrt(2 pi) + eps^2 / 2 + log(1.000001 - a^2), used with that sign throughout.  (The reference writes the
+//     third term as ((avg - u) / std)^2 / 2; its derivatives with respect to avg and std cancel, so nothing is propagated through it.)
 //   * a grid-wide dependency in the middle of the step: the actor objective needs alpha AFTER the temperature's step, which needs the
 //     batch mean of the policy-gradient sample's logprob.  The actor does not change between the critic launch and the temperature
 //     step, so the critic launch -- which holds the gathered state rows and the actor's small tensors anyway -- also runs the actor
@@ -23,7 +24,8 @@
 //     the critic's apply launch, which reduces the slabs anyway, steps alpha_log (td3_apply_kernel, Td3ApplyArgs::temp); the actor
 //     launch reads the new alpha_log and recomputes that forward, whose activations its backward needs anyway.  Cost: one extra
 //     actor forward per sample (~66 k of ~550 k flop at width 128) instead of a fifth launch and a second pass over the batch.
-//   * min(q1, q2) under the actor objective: both target heads are evaluated and the backward starts from each sample's own head.
+//   * the entropy term of the label, and min(q1, q2) under the actor objective: both target heads are evaluated and the backward
+//     starts from each sample's own head; the two heads' gradients and the Hardswish gates of the actor's backward.
 // Draws: two tables of normals per step (parity tests inject the reference's) or Philox streams 4 (next-state sample) and 5
 // (policy-gradient sample) in the kernels; both launches of a step form the same policy-gradient draw from (seed, epoch, row, position).
 #include "sac.hpp"
@@ -45,6 +47,9 @@ __device__ __forceinline__ f32x4_t hsg4(f32x4_t d, const f32x4_t& z) {
     for (int r = 0; r < 4; ++r) d[r] = z[r] < -3.0f ? 0.f : (z[r] <= 3.0f ? d[r] * (z[r] * (1.0f / 3.0f) + 0.5f) : d[r]);
     return d;
 }
+struct GateHardswish {   // actor_body_bwd's gate (td3_device.hpp), on the stored pre-activations
+    static __device__ __forceinline__ f32x4_t bwd(const f32x4_t& d, const f32x4_t& z) { return hsg4(d, z); }
+};
 
 // the small tensors of ActorSAC (everything but the two md x md matrices) as one LDS image, in flat order (td3_device.hpp)
 struct SacSmallActor { int W1, b1, b2, b3, wa, ba, ws, bs, total; };
@@ -53,22 +58,8 @@ __host__ __device__ inline SacSmallActor sac_small_actor(int D, int md) {
     const int mm = md * md;
     return SacSmallActor{P.W1, P.b1, P.b2 - mm, P.b3 - 2 * mm, P.wa - 2 * mm, P.ba - 2 * mm, P.ws - 2 * mm, P.bs - 2 * mm, P.total - 2 * mm};
 }
-struct SacLds {
-    int buf[4], xin, red, small[3], total;
-};
-__host__ __device__ inline SacLds sac_lds(int NT, int D) {
-    SacLds L{};
-    int o = 0;
-    for (int k = 0; k < 4; ++k) { L.buf[k] = o; o += td3_buf_floats(NT); }
-    L.xin = o; o += 16 * td3_xin_width(D);
-    L.red = o; o += 8 * kRedSlot;
-    const int md = NT * 16, sa = sac_small_actor(D, md).total, sc = td3_small_critic(D, md).total;
-    L.small[0] = o; o += sa;                 // the online actor
-    L.small[1] = o; o += sc;                 // critic launch: the online critic; actor launch: the target critic
-    L.small[2] = o; o += sc;                 // critic launch only: the target critic
-    L.total = o;
-    return L;
-}
+// TD3's LDS map around ActorSAC's small image (small[0]: the online actor, in both launches)
+__host__ __device__ inline Td3Lds sac_lds(int NT, int D) { return td3_lds(NT, D, sac_small_actor(D, NT * 16).total); }
 
 __device__ __forceinline__ float sac_noise(const SacBatch& b, const float* table, uint32_t stream, long long trow, int pos) {
     if (table) return table[(size_t)trow * b.B + pos];
@@ -133,11 +124,12 @@ __device__ __forceinline__ void sac_actor_fwd(const float* __restrict__ actg, co
 // DD: the state width as a compile-time constant (3: pH, 4: water tank Integrator), 0: read from the arguments (td3_fused.hip).
 template <int MD, int DD, int NW>
 __global__ __launch_bounds__(NW * 64, 1) void sac_critic_kernel(SacGradArgs a) {
-    constexpr int NT = MD / 16, PER = NT / NW, KF = 2, XW = 16, XG = 4 * KF;
+    constexpr int NT = MD / 16, PER = NT / NW, KF = 2, XW = 16;
+    constexpr bool S = false;   // register-resident md x md weights (width <= 128)
     static_assert(PER >= 1 && PER * NW == NT, "the waves split a layer's output tiles evenly");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = DD ? DD : a.D, Dc = D + 1;
-    const SacLds F = sac_lds(NT, D);
+    const Td3Lds F = sac_lds(NT, D);
     float* const B0 = lds + F.buf[0];
     float* const B1 = lds + F.buf[1];
     float* const B2 = lds + F.buf[2];
@@ -161,179 +153,62 @@ __global__ __launch_bounds__(NW * 64, 1) void sac_critic_kernel(SacGradArgs a) {
 
 #pragma unroll 1
     for (int group = blockIdx.x; group < a.ngroups; group += gridDim.x) {
-        int lane = tid & 63;
-        asm volatile("" : "+v"(lane));
-        const int j = lane & 15, q = lane >> 4;
-        const bool accum = group != (int)blockIdx.x;
-        const int pos = group * kTd3Tile + j;
-        const bool valid = pos < a.b.B;
-        const int p = valid ? pos : a.b.B - 1;
-        const long long row = a.b.idx[(size_t)trow * a.b.B + p], nrow = a.b.nxt[(size_t)trow * a.b.B + p];
-        Wts<NT, PER, false> wA, wB;
+        const Td3Tile T = td3_tile(tid, group, a.b.B);
+        const int lane = T.lane;
+        Td3Gather<KF> G;
+        gather_index(G, a.b, T);
+        Wts<NT, PER, S> wA, wB;
         f32x4_t in[NT];
         wload(wA, a.act + PA.W2, t0, lane);   // the first md x md weights: in flight behind the gather's two round trips
-        if (!accum) {   // the nets' small tensors (first group only)
-            small_copy<NW * 64>(lds + F.small[0], a.act, PA.W1, PA.W2, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b2, a.act, PA.b2, PA.W3, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b3, a.act, PA.b3, PA.total, tid);
-            small_copy<NW * 64>(lds + F.small[1], a.cri, PC.W1, PC.W2, tid);
-            small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
-            small_copy<NW * 64>(lds + F.small[2], a.cri_target, PC.W1, PC.W2, tid);
-            small_copy<NW * 64>(lds + F.small[2] + SC.b2, a.cri_target, PC.b2, PC.total, tid);
+        if (!T.accum) {   // the nets' small tensors (first group only)
+            small_copy_actor<NW * 64>(lds + F.small[0], a.act, PA.W1, PA, SA, tid);
+            small_copy_critic<NW * 64>(lds + F.small[1], a.cri, PC.W1, PC, SC, tid);
+            small_copy_critic<NW * 64>(lds + F.small[2], a.cri_target, PC.W1, PC, SC, tid);
         }
-        // first-layer B operands: input column 4 k + q of sample j
-        const float* srow = a.b.state + (size_t)row * D;
-        const float* nsrow = a.b.state + (size_t)nrow * D;
-        float sx[KF], nx[KF];
-#pragma unroll
-        for (int k = 0; k < KF; ++k) {
-            sx[k] = 4 * k + q < D ? srow[4 * k + q] : 0.f;
-            nx[k] = 4 * k + q < D ? nsrow[4 * k + q] : 0.f;
-        }
-        const float* orow = a.b.other + (size_t)row * 3;
-        const float reward = orow[0], mask = orow[1], action = orow[2];
-        const float eps_next = sac_noise(a.b, a.b.noise_next, STREAM_SAC_NEXT, trow, p);
-        const float eps_pg = sac_noise(a.b, a.b.noise_pg, STREAM_SAC_PG, trow, p);
+        gather_rows(G, a.b, D, T);
+        const float eps_next = sac_noise(a.b, a.b.noise_next, STREAM_SAC_NEXT, trow, T.p);
+        const float eps_pg = sac_noise(a.b, a.b.noise_pg, STREAM_SAC_PG, trow, T.p);
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
-        // the online critic's input [s, a, 0 ..]: column 4 k + q of sample j (this lane's first-layer B operands)
-        float xs[KF];
-#pragma unroll
-        for (int k = 0; k < KF; ++k) xs[k] = 4 * k + q < D ? sx[k] : (4 * k + q == D ? action : 0.f);
-        if (wave == 0) {   // ... as rows [16 samples][XW columns] for its first-layer weight gradient, and for the actor launch
-#pragma unroll
-            for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? xs[k] : 0.f;
-            if (valid) {
-#pragma unroll
-                for (int k = 0; k < KF; ++k) a.xg[(size_t)pos * XG + 4 * k + q] = xs[k];
-            }
-        }
+        gather_publish<KF, XW>(G, D, T, wave, xin, a.xg);
 
         // ------------------------------------------------------------------ next_a, next_lp = act.get_action_logprob(s')
         float next_a, next_lp;
         {
             f32x4_t h1[PER], z2[PER], z3[PER];
             float avg, raw;
-            sac_actor_fwd<NT, PER, NW, KF, true>(a.act, PA, ac, SA, D, B0, B1, red, 0, wave, t0, lane, nx, wA, wB, nullptr, in, h1, z2, z3, avg, raw);
+            sac_actor_fwd<NT, PER, NW, KF, true>(a.act, PA, ac, SA, D, B0, B1, red, 0, wave, t0, lane, G.nx, wA, wB, nullptr, in, h1, z2, z3, avg, raw);
             const SacSample s = sac_sample(avg, raw, eps_next);
             next_a = s.a;
             next_lp = s.lp;
             // ---------------------------------------------------------------- lp of a_pg = act.get_action_logprob(s): the temperature's gradient
-            sac_actor_fwd<NT, PER, NW, KF, false>(a.act, PA, ac, SA, D, B0, B1, red, 2, wave, t0, lane, sx, wA, wB, a.cri_target + PC.W2, in, h1, z2,
-                                                  z3, avg, raw);
+            sac_actor_fwd<NT, PER, NW, KF, false>(a.act, PA, ac, SA, D, B0, B1, red, 2, wave, t0, lane, G.sx, wA, wB, a.cri_target + PC.W2, in, h1,
+                                                  z2, z3, avg, raw);
             const SacSample g = sac_sample(avg, raw, eps_pg);
-            if (valid && wave == 0 && q == 0) lp_acc += g.lp;
+            if (T.valid && wave == 0 && T.q == 0) lp_acc += g.lp;
         }
         // ------------------------------------------------------------------ q_label = r + mask * (min(cri_target twin heads)(s', next_a) + next_lp alpha)
         wload(wB, a.cri + PC.W2, t0, lane);
-        float label;
-        {
-            float xt[KF];
-#pragma unroll
-            for (int k = 0; k < KF; ++k) xt[k] = 4 * k + q < D ? nx[k] : (4 * k + q == D ? next_a : 0.f);
-            f32x4_t h[PER];
-            layer_first<PER, KF>(ct + SC.W1, ct + SC.b1, Dc, t0, lane, xt, h);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) chain_put(B0, lane, t0 + n, relu4(h[n]));
-            bias_get<PER>(ct + SC.b2, t0, lane, h);
-            TD3_BARRIER();
-            chain_get<NT>(B0, lane, in);
-            wlayer(wA, in, h);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) h[n] = relu4(h[n]);
-            red_put(red, 4, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, h));
-            red_put(red, 5, wave, lane, head_partial<PER>(ct + SC.q2w, t0, lane, h));
-            TD3_BARRIER();
-            const float tq1 = red_get<NW>(red, 4, lane) + ct[SC.q1b], tq2 = red_get<NW>(red, 5, lane) + ct[SC.q2b];
-            label = reward + mask * (fminf(tq1, tq2) + next_lp * alpha);
-        }
-        // ------------------------------------------------------------------ online twin critic on (s, a): forward
-        f32x4_t h1[PER], h2[PER];
-        {
-            layer_first<PER, KF>(cr + SC.W1, cr + SC.b1, Dc, t0, lane, xs, h1);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { h1[n] = relu4(h1[n]); chain_put(B1, lane, t0 + n, h1[n]); }
-        }
-        wload_t(wA, a.cri + PC.W2, t0, lane);   // for dH1 = W2^T dZ2
-        bias_get<PER>(cr + SC.b2, t0, lane, h2);
-        TD3_BARRIER();
-        chain_get<NT>(B1, lane, in);
-        wlayer(wB, in, h2);
-#pragma unroll
-        for (int n = 0; n < PER; ++n) h2[n] = relu4(h2[n]);
-        red_put(red, 6, wave, lane, head_partial<PER>(cr + SC.q1w, t0, lane, h2));
-        red_put(red, 7, wave, lane, head_partial<PER>(cr + SC.q2w, t0, lane, h2));
-        TD3_BARRIER();
-        // ------------------------------------------------------------------ SmoothL1 x 2 (beta = 1, mean) and its gradient
-        float g1 = 0.f, g2 = 0.f;
-        {
-            const float d1 = red_get<NW>(red, 6, lane) + cr[SC.q1b] - label, d2 = red_get<NW>(red, 7, lane) + cr[SC.q2b] - label;
-            const float a1 = fabsf(d1), a2 = fabsf(d2);
-            if (valid) {
-                g1 = (a1 < 1.f ? d1 : (d1 > 0.f ? 1.f : -1.f)) * invB;
-                g2 = (a2 < 1.f ? d2 : (d2 > 0.f ? 1.f : -1.f)) * invB;
-                if (wave == 0 && q == 0) loss_acc += (a1 < 1.f ? 0.5f * d1 * d1 : a1 - 0.5f) + (a2 < 1.f ? 0.5f * d2 * d2 : a2 - 0.5f);
-            }
-        }
-        // heads: weight / bias gradients, dZ2 = (g1 wq1 + g2 wq2) [h2 > 0]
-        {
-            f32x4_t v1[PER], v2[PER], dz[PER];
-#pragma unroll
-            for (int n = 0; n < PER; ++n) {
-                const f32x4_t w1 = ld4(cr + SC.q1w + 16 * (t0 + n) + 4 * q), w2 = ld4(cr + SC.q2w + 16 * (t0 + n) + 4 * q);
-                v1[n] = h2[n] * g1;
-                v2[n] = h2[n] * g2;
-                dz[n] = gate4(w1 * g1 + w2 * g2, h2[n]);
-                chain_put(B2, lane, t0 + n, dz[n]);
-            }
-            vec_grad<PER>(sl + SL.seg[4].slab_off, t0, lane, v1, accum);
-            vec_grad<PER>(sl + SL.seg[6].slab_off, t0, lane, v2, accum);
-            vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, dz, accum);   // net_sa.2 bias
-            if (wave == 0) {
-                const float b1 = row_sum16(g1), b2 = row_sum16(g2);
-                if (lane == 0) {
-                    float* p1 = sl + SL.seg[5].slab_off;
-                    float* p2 = sl + SL.seg[7].slab_off;
-                    p1[0] = accum ? p1[0] + b1 : b1;
-                    p2[0] = accum ? p2[0] + b2 : b2;
-                }
-            }
-        }
-        TD3_BARRIER();   // dZ2 published
-        dw_slab<NT, PER, false>(B2, B1, sl + SL.seg[2].slab_off, t0, lane, accum);   // net_sa.2 weight gradient
-        TD3_NO_HOIST();
-        chain_get<NT>(B2, lane, in);
-        {
-            f32x4_t d1[PER];
-            zero4<PER>(d1);
-            wlayer(wA, in, d1);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { d1[n] = gate4(d1[n], h1[n]); chain_put(B0, lane, t0 + n, d1[n]); }
-            vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d1, accum);   // net_sa.0 bias
-        }
-        TD3_BARRIER();   // dZ1 published
-        {
-            f32x4_t acc[PER][1];
-            dw_first<PER, XW>(B0, xin, t0, lane, acc);
-            float* seg = sl + SL.seg[0].slab_off;
-#pragma unroll
-            for (int n = 0; n < PER; ++n) slab_put(seg + ((t0 + n) * 64 + lane) * 4, acc[n][0], accum);
-        }
+        float xt[KF], tq1, tq2;
+        critic_input<KF>(G.nx, next_a, D, T.q, xt);
+        twin_heads<NT, PER, NW, KF, S>(ct + SC.W1, ct, SC, Dc, B0, red, 4, wave, t0, lane, xt, wA, in, tq1, tq2);
+        const float label = G.reward + G.mask * (fminf(tq1, tq2) + next_lp * alpha);
+        // ------------------------------------------------------------------ online twin critic on (s, a): loss, backward, weight gradients
+        online_critic_step<NT, PER, NW, KF, XW, S>(cr + SC.W1, cr, SC, a.cri + PC.W2, Dc, B0, B1, B2, xin, red, 6, wave, t0, T, G.xs, label, invB,
+                                                   wA, wB, in, sl, SL, loss_acc);
     }
-    if (wave == 0) {
-        const float t = row_sum16(loss_acc), l = row_sum16(lp_acc);
-        if (tid == 0) st4(sl + SL.scalar_off, f32x4_t{t, l, 0.f, 0.f});
-    }
+    tile_scalars_put(sl + SL.scalar_off, wave, tid, {loss_acc, lp_acc});
 }
 
 // ======================================================================================================== actor gradients
 // obj_actor = -mean(min(cri_target.get_q1_q2(s, a_pg)) + lp alpha)  (agent.py:461-463), differentiated down to the actor's parameters
 template <int MD, int DD, int NW>
 __global__ __launch_bounds__(NW * 64, 1) void sac_actor_kernel(SacGradArgs a) {
-    constexpr int NT = MD / 16, PER = NT / NW, KF = 2, XW = 16, XG = 4 * KF;
+    constexpr int NT = MD / 16, PER = NT / NW, KF = 2, XW = 16;
+    constexpr bool S = false;   // register-resident md x md weights (width <= 128)
     static_assert(PER >= 1 && PER * NW == NT, "the waves split a layer's output tiles evenly");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = DD ? DD : a.D, Dc = D + 1;
-    const SacLds F = sac_lds(NT, D);
+    const Td3Lds F = sac_lds(NT, D);
     float* const B0 = lds + F.buf[0];
     float* const B1 = lds + F.buf[1];
     float* const B2 = lds + F.buf[2];
@@ -357,33 +232,21 @@ __global__ __launch_bounds__(NW * 64, 1) void sac_actor_kernel(SacGradArgs a) {
 
 #pragma unroll 1
     for (int group = blockIdx.x; group < a.ngroups; group += gridDim.x) {
-        int lane = tid & 63;
-        asm volatile("" : "+v"(lane));
-        const int j = lane & 15, q = lane >> 4;
-        const bool accum = group != (int)blockIdx.x;
-        const int pos = group * kTd3Tile + j;
-        const bool valid = pos < a.b.B;
-        const int p = valid ? pos : a.b.B - 1;
-        Wts<NT, PER, false> wA, wB;
+        const Td3Tile T = td3_tile(tid, group, a.b.B);
+        const int lane = T.lane, q = T.q;
+        const bool accum = T.accum;
+        Wts<NT, PER, S> wA, wB;
         f32x4_t in[NT];
         wload(wA, a.act + PA.W2, t0, lane);
-        // the minibatch's state rows as the critic launch of this step gathered them (one round trip instead of index -> row)
         float sx[KF];
-#pragma unroll
-        for (int k = 0; k < KF; ++k) sx[k] = 4 * k + q < D ? a.xg[(size_t)p * XG + 4 * k + q] : 0.f;
-        const float eps_pg = sac_noise(a.b, a.b.noise_pg, STREAM_SAC_PG, trow, p);
+        gather_read<KF>(a.xg, D, T, sx);
+        const float eps_pg = sac_noise(a.b, a.b.noise_pg, STREAM_SAC_PG, trow, T.p);
         if (!accum) {   // the small tensors (first group only)
-            small_copy<NW * 64>(lds + F.small[0], a.act, PA.W1, PA.W2, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b2, a.act, PA.b2, PA.W3, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b3, a.act, PA.b3, PA.total, tid);
-            small_copy<NW * 64>(lds + F.small[1], a.cri, PC.W1, PC.W2, tid);
-            small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
+            small_copy_actor<NW * 64>(lds + F.small[0], a.act, PA.W1, PA, SA, tid);
+            small_copy_critic<NW * 64>(lds + F.small[1], a.cri, PC.W1, PC, SC, tid);
         }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
-        if (wave == 0) {   // the actor's input rows [16 samples][XW columns, zero beyond D] for its first-layer weight gradient
-#pragma unroll
-            for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? sx[k] : 0.f;
-        }
+        if (wave == 0) xin_put<KF, XW>(xin, T, sx);   // the actor's input rows, for its first-layer weight gradient
         f32x4_t a1[PER], z2[PER], z3[PER], c1[PER], c2[PER];
 
         // ------------------------------------------------------------------ a_pg, lp = act.get_action_logprob(s): h1 in B0, h2 in B1
@@ -391,31 +254,19 @@ __global__ __launch_bounds__(NW * 64, 1) void sac_actor_kernel(SacGradArgs a) {
         sac_actor_fwd<NT, PER, NW, KF, true>(a.act, PA, ac, SA, D, B0, B1, red, 0, wave, t0, lane, sx, wA, wB, a.cri + PC.W2, in, a1, z2, z3, avg, raw);
         const SacSample s = sac_sample(avg, raw, eps_pg);
         // ------------------------------------------------------------------ q1, q2 = cri_target.get_q1_q2(s, a_pg)
-        {
-            float xt[KF];
-#pragma unroll
-            for (int k = 0; k < KF; ++k) xt[k] = 4 * k + q < D ? sx[k] : (4 * k + q == D ? s.a : 0.f);
-            layer_first<PER, KF>(ct + SC.W1, ct + SC.b1, Dc, t0, lane, xt, c1);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { c1[n] = relu4(c1[n]); chain_put(B2, lane, t0 + n, c1[n]); }
-        }
-        wload_t(wB, a.cri + PC.W2, t0, lane);   // dC1 = W2^T dZc2
-        bias_get<PER>(ct + SC.b2, t0, lane, c2);
-        TD3_BARRIER();
-        chain_get<NT>(B2, lane, in);
-        wlayer(wA, in, c2);
-#pragma unroll
-        for (int n = 0; n < PER; ++n) c2[n] = relu4(c2[n]);
+        float xt[KF];
+        critic_input<KF>(sx, s.a, D, q, xt);
+        target_critic_fwd<NT, PER, KF, S>(ct + SC.W1, ct, SC, a.cri + PC.W2, Dc, B2, t0, lane, xt, wA, wB, in, c1, c2);
         red_put(red, 2, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, c2));
         red_put(red, 3, wave, lane, head_partial<PER>(ct + SC.q2w, t0, lane, c2));
         wload_t(wA, a.act + PA.W3, t0, lane);   // dA2 = W3^T dZ3
         TD3_BARRIER();
         // ------------------------------------------------------------------ backward through the critic to the action, from each sample's own head
-        const float g = valid ? -invB : 0.f;   // d obj / d (min q + lp alpha)
+        const float g = T.valid ? -invB : 0.f;   // d obj / d (min q + lp alpha)
         {
             const float q1 = red_get<NW>(red, 2, lane) + ct[SC.q1b], q2 = red_get<NW>(red, 3, lane) + ct[SC.q2b];
             const bool first = q1 <= q2;
-            if (valid && wave == 0 && q == 0) q_acc += (first ? q1 : q2) + s.lp * alpha;
+            if (T.valid && wave == 0 && q == 0) q_acc += (first ? q1 : q2) + s.lp * alpha;
 #pragma unroll
             for (int n = 0; n < PER; ++n) {
                 const f32x4_t w1 = ld4(ct + SC.q1w + 16 * (t0 + n) + 4 * q), w2 = ld4(ct + SC.q2w + 16 * (t0 + n) + 4 * q);
@@ -423,28 +274,11 @@ __global__ __launch_bounds__(NW * 64, 1) void sac_actor_kernel(SacGradArgs a) {
             }
         }
         TD3_BARRIER();
-        chain_get<NT>(B3, lane, in);
-        float g_u, g_raw;
-        {
-            f32x4_t d[PER];
-            zero4<PER>(d);
-            wlayer(wB, in, d);
-            float pa = 0.f;   // d obj / d action through the critic = sum_f W1[f][D] dZc1[f]
-#pragma unroll
-            for (int n = 0; n < PER; ++n) {
-                d[n] = gate4(d[n], c1[n]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pa = fmaf(d[n][r], ct[SC.W1 + (16 * (t0 + n) + 4 * q + r) * Dc + D], pa);
-            }
-            pa += __shfl_xor(pa, 16);
-            pa += __shfl_xor(pa, 32);
-            red_put(red, 4, wave, lane, pa);
-            TD3_BARRIER();
-            const float g_lp = g * alpha;                                             // d obj / d lp
-            const float g_a = red_get<NW>(red, 4, lane) + g_lp * (-2.0f * s.a / s.corr);   // + the tanh correction log(1.000001 - a^2)
-            g_u = g_a * (1.0f - s.a * s.a);                                           // tanh'; d u / d avg = 1
-            g_raw = s.open ? g_u * s.std * s.eps + g_lp : 0.f;                        // u = avg + exp(ls) eps, lp = ls + ...; the clamp's gate
-        }
+        const float g_lp = g * alpha;                                              // d obj / d lp
+        const float g_a = critic_to_action<NT, PER, NW, S>(ct + SC.W1, D, B3, red, 4, wave, t0, lane, wB, in, c1)
+                          + g_lp * (-2.0f * s.a / s.corr);                         // + the tanh correction log(1.000001 - a^2)
+        const float g_u = g_a * (1.0f - s.a * s.a);                                // tanh'; d u / d avg = 1
+        const float g_raw = s.open ? g_u * s.std * s.eps + g_lp : 0.f;             // u = avg + exp(ls) eps, lp = ls + ...; the clamp's gate
         // ------------------------------------------------------------------ actor backward + weight gradients
         {
             f32x4_t va[PER], vs[PER], dz[PER];
@@ -470,76 +304,28 @@ __global__ __launch_bounds__(NW * 64, 1) void sac_actor_kernel(SacGradArgs a) {
                 }
             }
         }
-        wload_t(wB, a.act + PA.W2, t0, lane);   // dA1 = W2^T dZ2
-        TD3_BARRIER();   // dZ3 published
-        dw_slab<NT, PER, false>(B2, B1, sl + SL.seg[4].slab_off, t0, lane, accum);   // net_state.4: dZ3^T H2
-        TD3_NO_HOIST();
-        chain_get<NT>(B2, lane, in);
-        {
-            f32x4_t d[PER];
-            zero4<PER>(d);
-            wlayer(wA, in, d);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { d[n] = hsg4(d[n], z2[n]); chain_put(B3, lane, t0 + n, d[n]); }
-            vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, d, accum);    // net_state.2 bias
-        }
-        TD3_BARRIER();   // dZ2 published
-        dw_slab<NT, PER, false>(B3, B0, sl + SL.seg[2].slab_off, t0, lane, accum);   // net_state.2: dZ2^T H1
-        TD3_NO_HOIST();
-        chain_get<NT>(B3, lane, in);
-        {
-            f32x4_t d[PER];
-            zero4<PER>(d);
-            wlayer(wB, in, d);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { d[n] = gate4(d[n], a1[n]); chain_put(B1, lane, t0 + n, d[n]); }
-            vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d, accum);    // net_state.0 bias
-        }
-        TD3_BARRIER();   // dZ1 published
-        {
-            f32x4_t acc[PER][1];
-            dw_first<PER, XW>(B1, xin, t0, lane, acc);
-            float* seg = sl + SL.seg[0].slab_off;
-#pragma unroll
-            for (int n = 0; n < PER; ++n) slab_put(seg + ((t0 + n) * 64 + lane) * 4, acc[n][0], accum);
-        }
+        actor_body_bwd<GateHardswish, NT, PER, XW, S>(a.act + PA.W2, B0, B1, B2, B3, xin, t0, T, wA, wB, in, a1, z2, sl, SL);
     }
-    if (wave == 0) {
-        const float t = row_sum16(q_acc);
-        if (tid == 0) st4(sl + SL.scalar_off, f32x4_t{t, 0.f, 0.f, 0.f});
-    }
+    tile_scalars_put(sl + SL.scalar_off, wave, tid, {q_acc});
 }
 
 // ======================================================================================================== host side
 bool sac_supported(int D, int A, int md) { return A == 1 && D >= 1 && D <= kSacMaxD && (md == 64 || md == 128); }
-int64_t sac_workspace_floats(int D, int md, int B) {
-    const int64_t g = td3_grid(B);
-    // slabs + the gathered rows [B][td3_xg_stride(D)]
-    return g * (sac_actor_slab(D, md).stride + td3_critic_slab(D, md).stride) + (int64_t)B * td3_xg_stride(D);
-}
+int64_t sac_workspace_floats(int D, int md, int B) { return td3_workspace_floats(sac_actor_slab(D, md), D, md, B); }
 
-// waves per workgroup as for TD3: four at width 64 (one per SIMD), eight at width 128
-template <int MD, int DD>
-static int launch_grad_d(bool critic, const SacGradArgs& a, int grid, hipStream_t s) {
-    constexpr int NW = MD == 64 ? 4 : 8;
-    const size_t lds_bytes = sizeof(float) * (size_t)sac_lds(MD / 16, a.D).total;
-    if (critic) hipLaunchKernelGGL((sac_critic_kernel<MD, DD, NW>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
-    else hipLaunchKernelGGL((sac_actor_kernel<MD, DD, NW>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
-    PIME_HIP_TRY(hipGetLastError());
-    return PIME_OK;
-}
-template <int MD>
-static int launch_grad(bool critic, const SacGradArgs& a, int grid, hipStream_t s) {
-    if (a.D == 3) return launch_grad_d<MD, 3>(critic, a, grid, s);   // pH observation
-    if (a.D == 4) return launch_grad_d<MD, 4>(critic, a, grid, s);   // water-tank Integrator observation
-    return launch_grad_d<MD, 0>(critic, a, grid, s);
-}
+struct SacKernels {   // td3_device.hpp: grad_dispatch
+    using Args = SacGradArgs;
+    template <int MD, int KF> static constexpr bool serves() { return MD <= 128 && KF == 2; }   // sac_supported, in the dispatch's terms
+    static int lds_floats(int NT, int D) { return sac_lds(NT, D).total; }
+    template <int MD, int DD, int NW, int KF> static constexpr auto critic() { return sac_critic_kernel<MD, DD, NW>; }
+    template <int MD, int DD, int NW, int KF> static constexpr auto actor() { return sac_actor_kernel<MD, DD, NW>; }
+};
 int launch_sac_grad(bool critic, int md, const SacGradArgs& a, int grid, hipStream_t s) {
     if (!sac_supported(a.D, 1, md)) {
         set_error("no fused SAC instantiation for state_dim %d width %d", a.D, md);
         return PIME_ERR_ARG;
     }
-    return md == 128 ? launch_grad<128>(critic, a, grid, s) : launch_grad<64>(critic, a, grid, s);
+    return grad_dispatch<SacKernels>(critic, md, a, grid, s);
 }
 
 }  // namespace pime

@@ -131,6 +131,7 @@ struct Td3ApplyArgs {
 // td3_fused.hip, host side
 int td3_grid(int B);                                    // workgroups (= slabs) of a gradient launch on a minibatch of B rows
 int64_t td3_workspace_floats(int D, int md, int B);     // both nets' slabs + the gathered rows
+int64_t td3_workspace_floats(const Td3SlabLayout& actor, int D, int md, int B);   // ... with another actor's slab (SAC)
 bool td3_supported(int D, int action_dim, int md);
 int launch_td3_grad(bool critic, int md, const Td3GradArgs& a, int grid, hipStream_t s);
 int launch_td3_apply(const Td3ApplyArgs& a, hipStream_t s);

@@ -1,6 +1,10 @@
-// Device code shared by the fused off-policy optimizer steps (td3_fused.hip, sac_fused.hip): the chain-layout activation images in
-// LDS, the register-resident / streamed weight blocks, the layers on v_mfma_f32_16x16x4_f32, the weight-gradient slabs and the
-// small-tensor images.  td3_fused.hip's header comment describes the decomposition these pieces serve.
+// Device code shared by the fused off-policy optimizer steps (td3_fused.hip, sac_fused.hip).  First the building blocks: the
+// chain-layout activation images in LDS, the register-resident / streamed weight blocks, the layers on v_mfma_f32_16x16x4_f32, the
+// weight-gradient slabs and the small-tensor images.  Then the pieces the four gradient kernels are made of -- the tile context, the
+// minibatch gather, the twin target heads, the online twin-critic step, the target critic's forward and backward to the action, the
+// actor body's backward -- and the host-side dispatch of (width, state width) to an instantiation.  What differs between the agents
+// (the actors' forwards, the labels, the heads' gradients) is in their .hip files.  td3_fused.hip's header comment describes the
+// decomposition all of this serves.
 #pragma once
 #include "td3.hpp"
 #include "pime_common.hpp"
@@ -369,19 +373,21 @@ struct Td3Lds {
 __host__ __device__ constexpr int td3_buf_floats(int NT) { return NT * kTP; }
 // the tile's input rows in LDS: [16 samples][XW columns], XW = 16 (KF = 2) or 32 (KF = 8)
 __host__ __device__ constexpr int td3_xin_width(int D) { return 16 * td3_first_tiles(D); }
-__host__ __device__ inline Td3Lds td3_lds(int NT, int D) {
+// sa: floats of the actor's small image (td3_small_actor / sac_small_actor: the one size in which the two agents' maps differ)
+__host__ __device__ inline Td3Lds td3_lds(int NT, int D, int sa) {
     Td3Lds L{};
     int o = 0;
     for (int k = 0; k < 4; ++k) { L.buf[k] = o; o += td3_buf_floats(NT); }
     L.xin = o; o += 16 * td3_xin_width(D);
     L.red = o; o += 8 * kRedSlot;
-    const int md = NT * 16, sa = td3_small_actor(D, md).total, sc = td3_small_critic(D, md).total;
-    L.small[0] = o; o += sa;                 // the launch's actor (critic launch: the target actor)
+    const int sc = td3_small_critic(D, NT * 16).total;
+    L.small[0] = o; o += sa;                 // the launch's actor (TD3's critic launch: the target actor)
     L.small[1] = o; o += sc;                 // the launch's critic (critic launch: the online critic; actor launch: the target critic)
     L.small[2] = o; o += sc;                 // critic launch only: the target critic
     L.total = o;
     return L;
 }
+__host__ __device__ inline Td3Lds td3_lds(int NT, int D) { return td3_lds(NT, D, td3_small_actor(D, NT * 16).total); }
 
 // up to 256 16-byte words of a flat tensor, this thread's share: loaded here, written to LDS by small_store (the caller puts other
 // loads in between, so that one memory round trip covers them all)
@@ -398,6 +404,19 @@ template <int NTH>
 __device__ __forceinline__ void small_copy(float* __restrict__ dst, const float* __restrict__ src, int lo, int hi, int tid) {
     for (int u = tid; u < (hi - lo) / 4; u += NTH) st4(dst + 4 * u, ld4(src + lo + 4 * u));
 }
+// a whole net's small image that way, from flat float `lo` on (its W1, or b1 where td3_w1_global).  P / I: the net's flat and
+// small-image offsets (Td3ActorOff / Td3SmallActor, SacActorOff / SacSmallActor: three runs around the two md x md matrices)
+template <int NTH, class Off, class Img>
+__device__ __forceinline__ void small_copy_actor(float* img, const float* src, int lo, const Off& P, const Img& I, int tid) {
+    small_copy<NTH>(img, src, lo, P.W2, tid);
+    small_copy<NTH>(img + I.b2, src, P.b2, P.W3, tid);
+    small_copy<NTH>(img + I.b3, src, P.b3, P.total, tid);
+}
+template <int NTH>
+__device__ __forceinline__ void small_copy_critic(float* img, const float* src, int lo, const Td3CriticOff& P, const Td3SmallCritic& I, int tid) {
+    small_copy<NTH>(img, src, lo, P.W2, tid);
+    small_copy<NTH>(img + I.b2, src, P.b2, P.total, tid);
+}
 
 // a standard normal draw of the optimizer steps: Philox4x32-10 keyed by seed, counter (batch position, epoch, table row, stream)
 __device__ __forceinline__ float philox_normal_f32(uint64_t seed, uint32_t pos, uint32_t epoch, uint32_t trow, uint32_t stream) {
@@ -413,6 +432,343 @@ __device__ __forceinline__ float td3_noise(const Td3Batch& b, long long trow, in
     if (b.noise) return b.noise[(size_t)trow * b.B + pos];
     const uint32_t epoch = b.noise_epoch + (b.epoch ? (uint32_t)b.epoch[0] : 0u);   // bumped by the host per update
     return philox_normal_f32(b.noise_seed, (uint32_t)pos, epoch, (uint32_t)trow, STREAM_TD3_SMOOTH);
+}
+
+// ==== the pieces the four gradient kernels (td3_critic / td3_actor / sac_critic / sac_actor) are made of ===========================
+// Each piece is a stretch of a kernel's group iteration, inlined where it is called.  The kernels' schedule lives in them: a piece
+// takes the weights to prefetch as arguments and issues the load where the stretch always had it (a layer ahead of its use, in front
+// of a barrier); its barriers are the kernel's barriers.  Common arguments: wave, t0 = the wave's first output tile, T = the tile
+// context; B0 .. B3 = chain images, red = the reduction slots, sl / SL = the workgroup's slab and its layout; wA / wB = the two
+// weight blocks a wave holds; in = the activation's B operands (scratch registers of the caller).
+
+// ---- tile context: what a lane is in this group iteration ---------------------------------------------------------------------------
+struct Td3Tile {
+    int lane, j, q;   // lane of the wave = (lane group q, sample j of the tile)
+    int pos, p;       // the sample's batch position, and the position it reads (the last row's where the tile runs past the batch)
+    bool accum;       // a later group of this workgroup: the slab accumulates
+    bool valid;       // pos < B
+};
+__device__ __forceinline__ Td3Tile td3_tile(int tid, int group, int B) {
+    int lane = tid & 63;
+    asm volatile("" : "+v"(lane));   // opaque per iteration: nothing derived from the lane is kept live across the group loop
+    const int pos = group * kTd3Tile + (lane & 15);
+    const bool valid = pos < B;
+    return Td3Tile{lane, lane & 15, lane >> 4, pos, valid ? pos : B - 1, group != (int)blockIdx.x, valid};
+}
+// the workgroup's sums over its samples (wave 0, lanes 0..15 hold the terms) -> the slab's scalar slot, words [0 .. N)
+template <int N>
+__device__ __forceinline__ void tile_scalars_put(float* slot, int wave, int tid, const float (&acc)[N]) {
+    static_assert(N <= 4, "the scalar slot is one 16-byte word");
+    if (wave == 0) {
+        f32x4_t v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int n = 0; n < N; ++n) v[n] = row_sum16(acc[n]);
+        if (tid == 0) st4(slot, v);
+    }
+}
+
+// ---- minibatch gather -------------------------------------------------------------------------------------------------------------------
+// first-layer B operands of a critic on [s, act, 0 ..]: column 4 k + q of the lane's sample
+template <int KF>
+__device__ __forceinline__ void critic_input(const float (&s)[KF], float act, int D, int q, float (&x)[KF]) {
+#pragma unroll
+    for (int k = 0; k < KF; ++k) x[k] = 4 * k + q < D ? s[k] : (4 * k + q == D ? act : 0.f);
+}
+// wave 0: the tile's input rows [16 samples][XW columns, zero beyond 4 KF] for a first-layer weight gradient
+template <int KF, int XW>
+__device__ __forceinline__ void xin_put(float* xin, const Td3Tile& T, const float (&x)[KF]) {
+#pragma unroll
+    for (int k = 0; k < XW / 4; ++k) xin[T.j * XW + 4 * k + T.q] = k < KF ? x[k] : 0.f;
+}
+// The critic launch's gather in its three steps -- index, rows, publish -- between which the kernel issues its first weight load,
+// stages the small tensors, draws its noise and passes the group's first barrier.  Batch: Td3Batch | SacBatch.
+template <int KF>
+struct Td3Gather {
+    long long row, nrow;
+    float sx[KF], nx[KF];          // state / next-state columns 4 k + q of the lane's sample (0 beyond D)
+    float reward, mask, action;
+    float xs[KF];                  // the online critic's input [s, a, 0 ..] (gather_publish)
+};
+template <int KF, class Batch>
+__device__ __forceinline__ void gather_index(Td3Gather<KF>& G, const Batch& b, const Td3Tile& T) {
+    G.row = b.idx[(size_t)b.row * b.B + T.p];
+    G.nrow = b.nxt[(size_t)b.row * b.B + T.p];
+}
+template <int KF, class Batch>
+__device__ __forceinline__ void gather_rows(Td3Gather<KF>& G, const Batch& b, int D, const Td3Tile& T) {
+    const float* srow = b.state + (size_t)G.row * D;
+    const float* nsrow = b.state + (size_t)G.nrow * D;
+#pragma unroll
+    for (int k = 0; k < KF; ++k) {
+        G.sx[k] = 4 * k + T.q < D ? srow[4 * k + T.q] : 0.f;
+        G.nx[k] = 4 * k + T.q < D ? nsrow[4 * k + T.q] : 0.f;
+    }
+    const float* orow = b.other + (size_t)G.row * 3;
+    G.reward = orow[0]; G.mask = orow[1]; G.action = orow[2];
+}
+// behind the group's first barrier: xs, and by wave 0 the rows for the first-layer weight gradient (xin) and for the actor launch (xg)
+template <int KF, int XW>
+__device__ __forceinline__ void gather_publish(Td3Gather<KF>& G, int D, const Td3Tile& T, int wave, float* xin, float* xg) {
+    critic_input<KF>(G.sx, G.action, D, T.q, G.xs);
+    if (wave == 0) {
+        xin_put<KF, XW>(xin, T, G.xs);
+        if (T.valid) {
+#pragma unroll
+            for (int k = 0; k < KF; ++k) xg[(size_t)T.pos * (4 * KF) + 4 * k + T.q] = G.xs[k];
+        }
+    }
+}
+// the actor launch: the state rows as the critic launch of this step gathered them (one round trip instead of index -> row)
+template <int KF>
+__device__ __forceinline__ void gather_read(const float* xg, int D, const Td3Tile& T, float (&sx)[KF]) {
+#pragma unroll
+    for (int k = 0; k < KF; ++k) sx[k] = 4 * k + T.q < D ? xg[(size_t)T.p * (4 * KF) + 4 * k + T.q] : 0.f;
+}
+
+// ---- CriticTwin ---------------------------------------------------------------------------------------------------------------------------
+// Twin heads of the critic whose small image is ct (first layer W1: there, or in global memory) on the prepared first-layer operand
+// xt: the lane's sample's q1, q2.  wA holds its W2.  h1 passes through `img`; reduction slots slot, slot + 1.  Ends behind a barrier.
+template <int NT, int PER, int NW, int KF, bool S>
+__device__ __forceinline__ void twin_heads(const float* W1, const float* ct, const Td3SmallCritic& SC, int Dc, float* img, float* red, int slot,
+                                           int wave, int t0, int lane, const float (&xt)[KF], const Wts<NT, PER, S>& wA, f32x4_t (&in)[NT],
+                                           float& tq1, float& tq2) {
+    f32x4_t h[PER];
+    layer_first<PER, KF>(W1, ct + SC.b1, Dc, t0, lane, xt, h);
+#pragma unroll
+    for (int n = 0; n < PER; ++n) chain_put(img, lane, t0 + n, relu4(h[n]));
+    bias_get<PER>(ct + SC.b2, t0, lane, h);
+    TD3_BARRIER();
+    chain_get<NT>(img, lane, in);
+    wlayer(wA, in, h);
+#pragma unroll
+    for (int n = 0; n < PER; ++n) h[n] = relu4(h[n]);
+    red_put(red, slot, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, h));
+    red_put(red, slot + 1, wave, lane, head_partial<PER>(ct + SC.q2w, t0, lane, h));
+    TD3_BARRIER();
+    tq1 = red_get<NW>(red, slot, lane) + ct[SC.q1b];
+    tq2 = red_get<NW>(red, slot + 1, lane) + ct[SC.q2b];
+}
+
+// The online twin critic (small image cr, first layer W1, md x md weights W2 in global memory) on (s, a) = xs against `label`:
+// forward, SmoothL1 x 2 (beta = 1, mean) and its gradient, backward, every weight gradient into the slab; the loss terms add to
+// loss_acc (wave 0, lanes 0..15).  wB holds W2 on entry; W2^T is loaded into wA here.  h1 in B1, dZ2 in B2, dZ1 in B0; reduction
+// slots slot, slot + 1; xin as gather_publish left it.
+template <int NT, int PER, int NW, int KF, int XW, bool S>
+__device__ __forceinline__ void online_critic_step(const float* W1, const float* cr, const Td3SmallCritic& SC, const float* W2, int Dc, float* B0,
+                                                   float* B1, float* B2, const float* xin, float* red, int slot, int wave, int t0,
+                                                   const Td3Tile& T, const float (&xs)[KF], float label, float invB, Wts<NT, PER, S>& wA,
+                                                   const Wts<NT, PER, S>& wB, f32x4_t (&in)[NT], float* sl, const Td3SlabLayout& SL,
+                                                   float& loss_acc) {
+    constexpr int CT = XW / 16;
+    const int lane = T.lane, q = T.q;
+    const bool accum = T.accum;
+    // ------------------------------------------------------------------ forward
+    f32x4_t h1[PER], h2[PER];
+    {
+        layer_first<PER, KF>(W1, cr + SC.b1, Dc, t0, lane, xs, h1);
+#pragma unroll
+        for (int n = 0; n < PER; ++n) { h1[n] = relu4(h1[n]); chain_put(B1, lane, t0 + n, h1[n]); }
+    }
+    wload_t(wA, W2, t0, lane);   // for dH1 = W2^T dZ2
+    bias_get<PER>(cr + SC.b2, t0, lane, h2);
+    TD3_BARRIER();
+    chain_get<NT>(B1, lane, in);
+    wlayer(wB, in, h2);
+#pragma unroll
+    for (int n = 0; n < PER; ++n) h2[n] = relu4(h2[n]);
+    red_put(red, slot, wave, lane, head_partial<PER>(cr + SC.q1w, t0, lane, h2));
+    red_put(red, slot + 1, wave, lane, head_partial<PER>(cr + SC.q2w, t0, lane, h2));
+    TD3_BARRIER();
+    // ------------------------------------------------------------------ SmoothL1 x 2 (beta = 1, mean) and its gradient
+    float g1 = 0.f, g2 = 0.f;
+    {
+        const float d1 = red_get<NW>(red, slot, lane) + cr[SC.q1b] - label, d2 = red_get<NW>(red, slot + 1, lane) + cr[SC.q2b] - label;
+        const float a1 = fabsf(d1), a2 = fabsf(d2);
+        if (T.valid) {
+            g1 = (a1 < 1.f ? d1 : (d1 > 0.f ? 1.f : -1.f)) * invB;
+            g2 = (a2 < 1.f ? d2 : (d2 > 0.f ? 1.f : -1.f)) * invB;
+            if (wave == 0 && q == 0) loss_acc += (a1 < 1.f ? 0.5f * d1 * d1 : a1 - 0.5f) + (a2 < 1.f ? 0.5f * d2 * d2 : a2 - 0.5f);
+        }
+    }
+    // heads: weight / bias gradients, dZ2 = (g1 wq1 + g2 wq2) [h2 > 0]
+    {
+        f32x4_t v1[PER], v2[PER], dz[PER];
+#pragma unroll
+        for (int n = 0; n < PER; ++n) {
+            const f32x4_t w1 = ld4(cr + SC.q1w + 16 * (t0 + n) + 4 * q), w2 = ld4(cr + SC.q2w + 16 * (t0 + n) + 4 * q);
+            v1[n] = h2[n] * g1;
+            v2[n] = h2[n] * g2;
+            dz[n] = gate4(w1 * g1 + w2 * g2, h2[n]);
+            chain_put(B2, lane, t0 + n, dz[n]);
+        }
+        vec_grad<PER>(sl + SL.seg[4].slab_off, t0, lane, v1, accum);
+        vec_grad<PER>(sl + SL.seg[6].slab_off, t0, lane, v2, accum);
+        vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, dz, accum);   // net_sa.2 bias
+        if (wave == 0) {
+            const float b1 = row_sum16(g1), b2 = row_sum16(g2);
+            if (lane == 0) {
+                float* p1 = sl + SL.seg[5].slab_off;
+                float* p2 = sl + SL.seg[7].slab_off;
+                p1[0] = accum ? p1[0] + b1 : b1;
+                p2[0] = accum ? p2[0] + b2 : b2;
+            }
+        }
+    }
+    TD3_BARRIER();   // dZ2 published
+    dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[2].slab_off, t0, lane, accum);   // net_sa.2 weight gradient
+    TD3_NO_HOIST();
+    chain_get<NT>(B2, lane, in);
+    {
+        f32x4_t d1[PER];
+        zero4<PER>(d1);
+        wlayer(wA, in, d1);
+#pragma unroll
+        for (int n = 0; n < PER; ++n) { d1[n] = gate4(d1[n], h1[n]); chain_put(B0, lane, t0 + n, d1[n]); }
+        vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d1, accum);   // net_sa.0 bias
+    }
+    TD3_BARRIER();   // dZ1 published
+    {
+        f32x4_t acc[PER][CT];
+        dw_first<PER, XW>(B0, xin, t0, lane, acc);
+        float* seg = sl + SL.seg[0].slab_off;
+#pragma unroll
+        for (int n = 0; n < PER; ++n)
+#pragma unroll
+            for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
+    }
+}
+
+// The target critic on (s, a_policy) = xt in the actor launches, keeping c1 = relu(z1) (also in `img`) and c2 = relu(z2) for the
+// backward.  wA holds its W2 on entry; W2^T is loaded into wB here.  The caller reduces the head(s) it needs from c2, writes the
+// seed of the backward -- dZc2 = d obj / d q * w_head [c2 > 0] -- to a chain image and passes a barrier; then:
+template <int NT, int PER, int KF, bool S>
+__device__ __forceinline__ void target_critic_fwd(const float* W1, const float* ct, const Td3SmallCritic& SC, const float* W2, int Dc, float* img,
+                                                  int t0, int lane, const float (&xt)[KF], const Wts<NT, PER, S>& wA, Wts<NT, PER, S>& wB,
+                                                  f32x4_t (&in)[NT], f32x4_t (&c1)[PER], f32x4_t (&c2)[PER]) {
+    layer_first<PER, KF>(W1, ct + SC.b1, Dc, t0, lane, xt, c1);
+#pragma unroll
+    for (int n = 0; n < PER; ++n) { c1[n] = relu4(c1[n]); chain_put(img, lane, t0 + n, c1[n]); }
+    wload_t(wB, W2, t0, lane);   // dC1 = W2^T dZc2
+    bias_get<PER>(ct + SC.b2, t0, lane, c2);
+    TD3_BARRIER();
+    chain_get<NT>(img, lane, in);
+    wlayer(wA, in, c2);
+#pragma unroll
+    for (int n = 0; n < PER; ++n) c2[n] = relu4(c2[n]);
+}
+// ... d obj / d action through the critic = sum_f W1[f][D] dZc1[f], dZc1 = (W2^T dZc2) [c1 > 0], from the seed in `seed` (wB: W2^T).
+// Ends behind a barrier.
+template <int NT, int PER, int NW, bool S>
+__device__ __forceinline__ float critic_to_action(const float* W1, int D, const float* seed, float* red, int slot, int wave, int t0, int lane,
+                                                  const Wts<NT, PER, S>& wB, f32x4_t (&in)[NT], const f32x4_t (&c1)[PER]) {
+    const int q = lane >> 4, Dc = D + 1;
+    chain_get<NT>(seed, lane, in);
+    f32x4_t d[PER];
+    zero4<PER>(d);
+    wlayer(wB, in, d);
+    float pa = 0.f;
+#pragma unroll
+    for (int n = 0; n < PER; ++n) {
+        d[n] = gate4(d[n], c1[n]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pa = fmaf(d[n][r], W1[(16 * (t0 + n) + 4 * q + r) * Dc + D], pa);
+    }
+    pa += __shfl_xor(pa, 16);
+    pa += __shfl_xor(pa, 32);
+    red_put(red, slot, wave, lane, pa);
+    TD3_BARRIER();
+    return red_get<NW>(red, slot, lane);
+}
+
+// ---- three-layer actor body: backward + weight gradients ------------------------------------------------------------------------------
+// The gate of the two upper layers is the agent's: TD3's body is ReLU throughout (the gate reads the stored activations), SAC's upper
+// layers are Hardswish (sac_fused.hip: the gate reads the stored pre-activations).  The first layer is ReLU in both.
+struct GateRelu {
+    static __device__ __forceinline__ f32x4_t bwd(const f32x4_t& d, const f32x4_t& h) { return gate4(d, h); }
+};
+// From the last hidden layer's dZ3 (the caller has put it in B2, with that layer's bias gradient and the heads' gradients in the slab)
+// down to the first layer: slab segments 0 .. 4.  B0 / B1 hold the first / second layer's activations, xin the input rows; a1 = the
+// first layer's activations, s2 = what Gate reads of the second layer.  wA holds W3^T on entry; W2^T is loaded into wB here.
+template <class Gate, int NT, int PER, int XW, bool S>
+__device__ __forceinline__ void actor_body_bwd(const float* W2, float* B0, float* B1, float* B2, float* B3, const float* xin, int t0,
+                                               const Td3Tile& T, const Wts<NT, PER, S>& wA, Wts<NT, PER, S>& wB, f32x4_t (&in)[NT],
+                                               const f32x4_t (&a1)[PER], const f32x4_t (&s2)[PER], float* sl, const Td3SlabLayout& SL) {
+    constexpr int CT = XW / 16;
+    const int lane = T.lane;
+    const bool accum = T.accum;
+    wload_t(wB, W2, t0, lane);   // dA1 = W2^T dZ2
+    TD3_BARRIER();   // dZ3 published
+    dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[4].slab_off, t0, lane, accum);   // third layer: dZ3^T A2
+    TD3_NO_HOIST();
+    chain_get<NT>(B2, lane, in);
+    {
+        f32x4_t d[PER];
+        zero4<PER>(d);
+        wlayer(wA, in, d);
+#pragma unroll
+        for (int n = 0; n < PER; ++n) { d[n] = Gate::bwd(d[n], s2[n]); chain_put(B3, lane, t0 + n, d[n]); }
+        vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, d, accum);    // second layer's bias
+    }
+    TD3_BARRIER();   // dZ2 published
+    dw_slab<NT, PER, S>(B3, B0, sl + SL.seg[2].slab_off, t0, lane, accum);   // second layer: dZ2^T A1
+    TD3_NO_HOIST();
+    chain_get<NT>(B3, lane, in);
+    {
+        f32x4_t d[PER];
+        zero4<PER>(d);
+        wlayer(wB, in, d);
+#pragma unroll
+        for (int n = 0; n < PER; ++n) { d[n] = gate4(d[n], a1[n]); chain_put(B1, lane, t0 + n, d[n]); }
+        vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d, accum);    // first layer's bias
+    }
+    TD3_BARRIER();   // dZ1 published
+    {
+        f32x4_t acc[PER][CT];
+        dw_first<PER, XW>(B1, xin, t0, lane, acc);
+        float* seg = sl + SL.seg[0].slab_off;
+#pragma unroll
+        for (int n = 0; n < PER; ++n)
+#pragma unroll
+            for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
+    }
+}
+
+// ==== host side: one dispatch for both agents' gradient launches =====================================================================
+// K names an agent's kernel pair: K::Args, K::serves<MD, KF>(), K::lds_floats(NT, D), K::critic<MD, DD, NW, KF>() / K::actor<...>()
+// (the kernels).  The state width is compiled in for the environments' observations (3: pH, 4: water-tank Integrator, 12 / 30:
+// water-tank Stacking4 / Stacking10), else read from the arguments.
+// Waves per workgroup.  Width 64 has four output tiles: four waves, one per SIMD.  Widths 128 and 256: eight waves, two per SIMD,
+// owning one / two of a layer's eight / sixteen output tiles (the non-MFMA instructions of one wave issue behind the other's MFMAs);
+// at width 128 that measured 60.4 us per optimizer step against 63.1 on four waves (profiles/r04_u_td3_waves_ab.txt).
+template <class K, int MD, int DD, int KF>
+static int grad_launch(bool critic, const typename K::Args& a, int grid, hipStream_t s) {
+    if constexpr (K::template serves<MD, KF>()) {
+        constexpr int NW = MD == 64 ? 4 : 8;
+        const size_t lds_bytes = sizeof(float) * (size_t)K::lds_floats(MD / 16, a.D);
+        if (critic) hipLaunchKernelGGL((K::template critic<MD, DD, NW, KF>()), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
+        else hipLaunchKernelGGL((K::template actor<MD, DD, NW, KF>()), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
+        PIME_HIP_TRY(hipGetLastError());
+        return PIME_OK;
+    } else {
+        // not reached while the callers refuse what K::serves refuses; says so if one of them is widened alone
+        set_error("no fused instantiation for width %d with %d first-layer k-steps", MD, KF);
+        return PIME_ERR_ARG;
+    }
+}
+template <class K, int MD>
+static int grad_dispatch_d(bool critic, const typename K::Args& a, int grid, hipStream_t s) {
+    if (a.D == 3) return grad_launch<K, MD, 3, 2>(critic, a, grid, s);
+    if (a.D == 4) return grad_launch<K, MD, 4, 2>(critic, a, grid, s);
+    if (a.D == 12) return grad_launch<K, MD, 12, 8>(critic, a, grid, s);
+    if (a.D == 30) return grad_launch<K, MD, 30, 8>(critic, a, grid, s);
+    if (td3_first_ksteps(a.D) == 2) return grad_launch<K, MD, 0, 2>(critic, a, grid, s);
+    return grad_launch<K, MD, 0, 8>(critic, a, grid, s);
+}
+template <class K>
+static int grad_dispatch(bool critic, int md, const typename K::Args& a, int grid, hipStream_t s) {
+    if (md == 256) return grad_dispatch_d<K, 256>(critic, a, grid, s);
+    if (md == 128) return grad_dispatch_d<K, 128>(critic, a, grid, s);
+    return grad_dispatch_d<K, 64>(critic, a, grid, s);
 }
 
 }  // namespace pime

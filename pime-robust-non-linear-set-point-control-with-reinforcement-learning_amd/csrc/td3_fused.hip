@@ -1,6 +1,6 @@
 // One TD3 optimizer step as FOUR launches: critic gradients, critic apply, actor gradients, actor apply.
 //
-// replaces (reference, /root/reference/elegantrl/agent.py): AgentTD3.update_net's loop body (:314-331) -- get_obj_critic_raw
+// replaces (reference, elegantrl/agent.py): AgentTD3.update_net's loop body (:314-331) -- get_obj_critic_raw
 // (:361-370: minibatch gather, target actor + clamped smoothing noise (net.py:107-110), twin target heads + min, online twin
 // forward, SmoothL1 x 2), obj_critic.backward(), cri_optimizer.step(), the delayed soft update of cri_target (:116-124),
 // obj_actor = -cri_target(state, act(state)).mean() (:323-324; the reference differentiates through the TARGET critic's first head),
@@ -30,6 +30,12 @@
 // (Wts / wlayer: a register block of a layer would be 128 VGPRs), forms the md x md weight gradients in column slices, and at KF = 8
 // reads the first-layer weights from global memory (they do not fit beside the chain images in LDS).  The round-4 instantiations
 // (width 64 / 128, D <= 7) compile to the same arithmetic as before.
+//
+// What is this file's own: the two kernels' sequence -- which net runs where, the sv[] staging of the small tensors behind the index
+// loads (round-4 shapes), the ReLU actor's forward, the smoothed target action and the label, the seed of the actor objective's
+// backward (the target critic's first head) and the actor's single head -- and td3_apply_kernel, which SAC uses too.  Everything a
+// SAC step (sac_fused.hip) does the same way is in td3_device.hpp: the tile context, the gather, the twin target heads, the online
+// twin-critic step, the target critic's forward and its backward to the action, the actor body's backward, the launch dispatch.
 #include "td3_device.hpp"
 
 namespace pime {
@@ -46,7 +52,7 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
     constexpr bool S = MD == 256;                     // streamed md x md weights (Wts)
     constexpr bool W1G = MD == 256 && KF == 8;        // first-layer weights read from global memory (td3_w1_global)
     constexpr bool GEN = KF == 8 || MD == 256;        // small tensors staged by small_copy (the round-4 shapes: sv[] below)
-    constexpr int XW = KF == 2 ? 16 : 32, CT = XW / 16, XG = 4 * KF;
+    constexpr int XW = KF == 2 ? 16 : 32;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = DD ? DD : a.D, Dc = D + 1;
     const Td3Lds F = td3_lds(NT, D);
@@ -72,19 +78,15 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
 
 #pragma unroll 1
     for (int group = blockIdx.x; group < a.ngroups; group += gridDim.x) {
-        int lane = tid & 63;
-        asm volatile("" : "+v"(lane));
-        const int j = lane & 15, q = lane >> 4;
-        const bool accum = group != (int)blockIdx.x;
-        const int pos = group * kTd3Tile + j;
-        const bool valid = pos < a.b.B;
-        const int p = valid ? pos : a.b.B - 1;
-        const long long row = a.b.idx[(size_t)trow * a.b.B + p], nrow = a.b.nxt[(size_t)trow * a.b.B + p];
+        const Td3Tile T = td3_tile(tid, group, a.b.B);
+        const int lane = T.lane;
+        Td3Gather<KF> G;
+        gather_index(G, a.b, T);
         Wts<NT, PER, S> wA, wB;
         f32x4_t in[NT];
         wload(wA, a.act + PA.W2, t0, lane);   // the first md x md weights: in flight behind the gather's two round trips
         // the nets' small tensors ride behind the index loads (first group only): seven 16-byte loads per thread, one round trip
-        const bool stage = !accum;
+        const bool stage = !T.accum;
         const int nA0 = (PA.W2 - PA.W1) / 4, nA1 = MD / 4, nA2 = (PA.total - PA.b3) / 4, nC0 = (PC.W2 - PC.W1) / 4, nC1 = (PC.total - PC.b2) / 4;
         f32x4_t sv[9];
         if (!GEN && stage) {
@@ -93,18 +95,8 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
             sv[5] = small_load(a.cri_target + PC.W1, nC0, tid); sv[6] = small_load(a.cri_target + PC.b2, nC1, tid);
             sv[7] = small_load(a.cri + PC.W1 + 1024, nC0 - 256, tid); sv[8] = small_load(a.cri_target + PC.W1 + 1024, nC0 - 256, tid);   // D = 7 only
         }
-        // first-layer B operands: input column 4 k + q of sample j
-        const float* srow = a.b.state + (size_t)row * D;
-        const float* nsrow = a.b.state + (size_t)nrow * D;
-        float sx[KF], nx[KF];
-#pragma unroll
-        for (int k = 0; k < KF; ++k) {
-            sx[k] = 4 * k + q < D ? srow[4 * k + q] : 0.f;
-            nx[k] = 4 * k + q < D ? nsrow[4 * k + q] : 0.f;
-        }
-        const float* orow = a.b.other + (size_t)row * 3;
-        const float reward = orow[0], mask = orow[1], action = orow[2];
-        const float eps = td3_noise(a.b, trow, p);
+        gather_rows(G, a.b, D, T);
+        const float eps = td3_noise(a.b, trow, T.p);
         if (!GEN && stage) {
             float* const w = lds + F.small[0];
             small_store(w + SA.W1, nA0, tid, sv[0]); small_store(w + SA.b2, nA1, tid, sv[1]); small_store(w + SA.b3, nA2, tid, sv[2]);
@@ -116,32 +108,17 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         }
         if (GEN && stage) {
             const int a0 = W1G ? PA.b1 : PA.W1, c0 = W1G ? PC.b1 : PC.W1;
-            small_copy<NW * 64>(lds + F.small[0], a.act, a0, PA.W2, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b2, a.act, PA.b2, PA.W3, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b3, a.act, PA.b3, PA.total, tid);
-            small_copy<NW * 64>(lds + F.small[1], a.cri, c0, PC.W2, tid);
-            small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
-            small_copy<NW * 64>(lds + F.small[2], a.cri_target, c0, PC.W2, tid);
-            small_copy<NW * 64>(lds + F.small[2] + SC.b2, a.cri_target, PC.b2, PC.total, tid);
+            small_copy_actor<NW * 64>(lds + F.small[0], a.act, a0, PA, SA, tid);
+            small_copy_critic<NW * 64>(lds + F.small[1], a.cri, c0, PC, SC, tid);
+            small_copy_critic<NW * 64>(lds + F.small[2], a.cri_target, c0, PC, SC, tid);
         }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
-        // the online critic's input [s, a, 0 ..]: column q / 4 + q of sample j (this lane's first-layer B operands)
-        float xs[KF];
-#pragma unroll
-        for (int k = 0; k < KF; ++k) xs[k] = 4 * k + q < D ? sx[k] : (4 * k + q == D ? action : 0.f);
-        if (wave == 0) {   // ... as rows [16 samples][XW columns] for its first-layer weight gradient, and for the actor launch
-#pragma unroll
-            for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? xs[k] : 0.f;
-            if (valid) {
-#pragma unroll
-                for (int k = 0; k < KF; ++k) a.xg[(size_t)pos * XG + 4 * k + q] = xs[k];
-            }
-        }
+        gather_publish<KF, XW>(G, D, T, wave, xin, a.xg);
 
         // ------------------------------------------------------------------ next_a = clamp(tanh(act_target(s')) + clamp(noise))
         {
             f32x4_t h[PER];
-            layer_first<PER, KF>(W1G ? a.act + PA.W1 : at + SA.W1, at + SA.b1, D, t0, lane, nx, h);
+            layer_first<PER, KF>(W1G ? a.act + PA.W1 : at + SA.W1, at + SA.b1, D, t0, lane, G.nx, h);
 #pragma unroll
             for (int n = 0; n < PER; ++n) chain_put(B0, lane, t0 + n, relu4(h[n]));
         }
@@ -173,106 +150,15 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_critic_kernel(Td3GradArgs a) {
         }
         // ------------------------------------------------------------------ q_label = r + mask * min(cri_target twin heads)(s', next_a)
         wload(wB, a.cri + PC.W2, t0, lane);
-        float label;
-        {
-            float xt[KF];
-#pragma unroll
-            for (int k = 0; k < KF; ++k) xt[k] = 4 * k + q < D ? nx[k] : (4 * k + q == D ? next_a : 0.f);
-            f32x4_t h[PER];
-            layer_first<PER, KF>(W1G ? a.cri_target + PC.W1 : ct + SC.W1, ct + SC.b1, Dc, t0, lane, xt, h);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) chain_put(B0, lane, t0 + n, relu4(h[n]));
-            bias_get<PER>(ct + SC.b2, t0, lane, h);
-            TD3_BARRIER();
-            chain_get<NT>(B0, lane, in);
-            wlayer(wA, in, h);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) h[n] = relu4(h[n]);
-            red_put(red, 1, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, h));
-            red_put(red, 2, wave, lane, head_partial<PER>(ct + SC.q2w, t0, lane, h));
-            TD3_BARRIER();
-            const float tq1 = red_get<NW>(red, 1, lane) + ct[SC.q1b], tq2 = red_get<NW>(red, 2, lane) + ct[SC.q2b];
-            label = reward + mask * fminf(tq1, tq2);
-        }
-        // ------------------------------------------------------------------ online twin critic on (s, a): forward
-        f32x4_t h1[PER], h2[PER];
-        {
-            layer_first<PER, KF>(W1G ? a.cri + PC.W1 : cr + SC.W1, cr + SC.b1, Dc, t0, lane, xs, h1);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { h1[n] = relu4(h1[n]); chain_put(B1, lane, t0 + n, h1[n]); }
-        }
-        wload_t(wA, a.cri + PC.W2, t0, lane);   // for dH1 = W2^T dZ2
-        bias_get<PER>(cr + SC.b2, t0, lane, h2);
-        TD3_BARRIER();
-        chain_get<NT>(B1, lane, in);
-        wlayer(wB, in, h2);
-#pragma unroll
-        for (int n = 0; n < PER; ++n) h2[n] = relu4(h2[n]);
-        red_put(red, 3, wave, lane, head_partial<PER>(cr + SC.q1w, t0, lane, h2));
-        red_put(red, 4, wave, lane, head_partial<PER>(cr + SC.q2w, t0, lane, h2));
-        TD3_BARRIER();
-        // ------------------------------------------------------------------ SmoothL1 x 2 (beta = 1, mean) and its gradient
-        float g1 = 0.f, g2 = 0.f;
-        {
-            const float d1 = red_get<NW>(red, 3, lane) + cr[SC.q1b] - label, d2 = red_get<NW>(red, 4, lane) + cr[SC.q2b] - label;
-            const float a1 = fabsf(d1), a2 = fabsf(d2);
-            if (valid) {
-                g1 = (a1 < 1.f ? d1 : (d1 > 0.f ? 1.f : -1.f)) * invB;
-                g2 = (a2 < 1.f ? d2 : (d2 > 0.f ? 1.f : -1.f)) * invB;
-                if (wave == 0 && q == 0) loss_acc += (a1 < 1.f ? 0.5f * d1 * d1 : a1 - 0.5f) + (a2 < 1.f ? 0.5f * d2 * d2 : a2 - 0.5f);
-            }
-        }
-        // heads: weight / bias gradients, dZ2 = (g1 wq1 + g2 wq2) [h2 > 0]
-        {
-            f32x4_t v1[PER], v2[PER], dz[PER];
-#pragma unroll
-            for (int n = 0; n < PER; ++n) {
-                const f32x4_t w1 = ld4(cr + SC.q1w + 16 * (t0 + n) + 4 * q), w2 = ld4(cr + SC.q2w + 16 * (t0 + n) + 4 * q);
-                v1[n] = h2[n] * g1;
-                v2[n] = h2[n] * g2;
-                dz[n] = gate4(w1 * g1 + w2 * g2, h2[n]);
-                chain_put(B2, lane, t0 + n, dz[n]);
-            }
-            vec_grad<PER>(sl + SL.seg[4].slab_off, t0, lane, v1, accum);
-            vec_grad<PER>(sl + SL.seg[6].slab_off, t0, lane, v2, accum);
-            vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, dz, accum);   // net_sa.2 bias
-            if (wave == 0) {
-                const float b1 = row_sum16(g1), b2 = row_sum16(g2);
-                if (lane == 0) {
-                    float* p1 = sl + SL.seg[5].slab_off;
-                    float* p2 = sl + SL.seg[7].slab_off;
-                    p1[0] = accum ? p1[0] + b1 : b1;
-                    p2[0] = accum ? p2[0] + b2 : b2;
-                }
-            }
-        }
-        TD3_BARRIER();   // dZ2 published
-        dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[2].slab_off, t0, lane, accum);   // net_sa.2 weight gradient
-        TD3_NO_HOIST();
-        chain_get<NT>(B2, lane, in);
-        {
-            f32x4_t d1[PER];
-            zero4<PER>(d1);
-            wlayer(wA, in, d1);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { d1[n] = gate4(d1[n], h1[n]); chain_put(B0, lane, t0 + n, d1[n]); }
-            vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d1, accum);   // net_sa.0 bias
-        }
-        TD3_BARRIER();   // dZ1 published
-        {
-            f32x4_t acc[PER][CT];
-            dw_first<PER, XW>(B0, xin, t0, lane, acc);
-            float* seg = sl + SL.seg[0].slab_off;
-#pragma unroll
-            for (int n = 0; n < PER; ++n)
-#pragma unroll
-                for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
-        }
+        float xt[KF], tq1, tq2;
+        critic_input<KF>(G.nx, next_a, D, T.q, xt);
+        twin_heads<NT, PER, NW, KF, S>(W1G ? a.cri_target + PC.W1 : ct + SC.W1, ct, SC, Dc, B0, red, 1, wave, t0, lane, xt, wA, in, tq1, tq2);
+        const float label = G.reward + G.mask * fminf(tq1, tq2);
+        // ------------------------------------------------------------------ online twin critic on (s, a): loss, backward, weight gradients
+        online_critic_step<NT, PER, NW, KF, XW, S>(W1G ? a.cri + PC.W1 : cr + SC.W1, cr, SC, a.cri + PC.W2, Dc, B0, B1, B2, xin, red, 3, wave, t0,
+                                                   T, G.xs, label, invB, wA, wB, in, sl, SL, loss_acc);
     }
-    if (wave == 0) {
-        const float t = row_sum16(loss_acc);
-        if (tid == 0) st4(sl + SL.scalar_off, f32x4_t{t, 0.f, 0.f, 0.f});
-    }
+    tile_scalars_put(sl + SL.scalar_off, wave, tid, {loss_acc});
 }
 
 // ======================================================================================================== actor gradients
@@ -285,7 +171,7 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
     constexpr bool S = MD == 256;                     // streamed md x md weights (Wts)
     constexpr bool W1G = MD == 256 && KF == 8;        // first-layer weights read from global memory (td3_w1_global)
     constexpr bool GEN = KF == 8 || MD == 256;        // small tensors staged by small_copy (the round-4 shapes: sv[] below)
-    constexpr int XW = KF == 2 ? 16 : 32, CT = XW / 16, XG = 4 * KF;
+    constexpr int XW = KF == 2 ? 16 : 32;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = DD ? DD : a.D, Dc = D + 1;
     const Td3Lds F = td3_lds(NT, D);
@@ -311,20 +197,14 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
 
 #pragma unroll 1
     for (int group = blockIdx.x; group < a.ngroups; group += gridDim.x) {
-        int lane = tid & 63;
-        asm volatile("" : "+v"(lane));
-        const int j = lane & 15, q = lane >> 4;
-        const bool accum = group != (int)blockIdx.x;
-        const int pos = group * kTd3Tile + j;
-        const bool valid = pos < a.b.B;
-        const int p = valid ? pos : a.b.B - 1;
+        const Td3Tile T = td3_tile(tid, group, a.b.B);
+        const int lane = T.lane, q = T.q;
+        const bool accum = T.accum;
         Wts<NT, PER, S> wA, wB;
         f32x4_t in[NT];
         wload(wA, a.act + PA.W2, t0, lane);
-        // the minibatch's state rows as the critic launch of this step gathered them (one round trip instead of index -> row)
         float sx[KF];
-#pragma unroll
-        for (int k = 0; k < KF; ++k) sx[k] = 4 * k + q < D ? a.xg[(size_t)p * XG + 4 * k + q] : 0.f;
+        gather_read<KF>(a.xg, D, T, sx);
         const bool stage = !accum;   // the small tensors ride along (first group only)
         const int nA0 = (PA.W2 - PA.W1) / 4, nA1 = MD / 4, nA2 = (PA.total - PA.b3) / 4, nC0 = (PC.W2 - PC.W1) / 4, nC1 = (PC.total - PC.b2) / 4;
         f32x4_t sv[6];
@@ -341,18 +221,11 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
             small_store(c + SC.W1 + 1024, nC0 - 256, tid, sv[5]);
         }
         if (GEN && stage) {
-            const int a0 = W1G ? PA.b1 : PA.W1, c0 = W1G ? PC.b1 : PC.W1;
-            small_copy<NW * 64>(lds + F.small[0], a.act, a0, PA.W2, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b2, a.act, PA.b2, PA.W3, tid);
-            small_copy<NW * 64>(lds + F.small[0] + SA.b3, a.act, PA.b3, PA.total, tid);
-            small_copy<NW * 64>(lds + F.small[1], a.cri, c0, PC.W2, tid);
-            small_copy<NW * 64>(lds + F.small[1] + SC.b2, a.cri, PC.b2, PC.total, tid);
+            small_copy_actor<NW * 64>(lds + F.small[0], a.act, W1G ? PA.b1 : PA.W1, PA, SA, tid);
+            small_copy_critic<NW * 64>(lds + F.small[1], a.cri, W1G ? PC.b1 : PC.W1, PC, SC, tid);
         }
         TD3_BARRIER();   // the previous group is done with the LDS images; the small tensors are in
-        if (wave == 0) {   // the actor's input rows [16 samples][XW columns, zero beyond D] for its first-layer weight gradient
-#pragma unroll
-            for (int k = 0; k < XW / 4; ++k) xin[j * XW + 4 * k + q] = k < KF ? sx[k] : 0.f;
-        }
+        if (wave == 0) xin_put<KF, XW>(xin, T, sx);   // the actor's input rows, for its first-layer weight gradient
         f32x4_t a1[PER], a2[PER], a3[PER], c1[PER], c2[PER];
 
         // ------------------------------------------------------------------ action = tanh(act(s))
@@ -377,24 +250,12 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         TD3_BARRIER();
         const float act = tanhf(red_get<NW>(red, 0, lane) + ac[SA.b4]);
         // ------------------------------------------------------------------ q1 = cri_target.q1(s, action)
-        {
-            float xt[KF];
-#pragma unroll
-            for (int k = 0; k < KF; ++k) xt[k] = 4 * k + q < D ? sx[k] : (4 * k + q == D ? act : 0.f);
-            layer_first<PER, KF>(ctW1, ct + SC.b1, Dc, t0, lane, xt, c1);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { c1[n] = relu4(c1[n]); chain_put(B2, lane, t0 + n, c1[n]); }
-        }
-        wload_t(wB, a.cri + PC.W2, t0, lane);   // dC1 = W2^T dZc2
-        bias_get<PER>(ct + SC.b2, t0, lane, c2);
-        TD3_BARRIER();
-        chain_get<NT>(B2, lane, in);
-        wlayer(wA, in, c2);
-#pragma unroll
-        for (int n = 0; n < PER; ++n) c2[n] = relu4(c2[n]);
+        float xt[KF];
+        critic_input<KF>(sx, act, D, q, xt);
+        target_critic_fwd<NT, PER, KF, S>(ctW1, ct, SC, a.cri + PC.W2, Dc, B2, t0, lane, xt, wA, wB, in, c1, c2);
         red_put(red, 1, wave, lane, head_partial<PER>(ct + SC.q1w, t0, lane, c2));   // (the value itself only feeds the logged objective)
-        // ------------------------------------------------------------------ backward through the critic to the action
-        const float g = valid ? -invB : 0.f;   // d(-mean q1) / d q1
+        // ------------------------------------------------------------------ backward through the critic to the action, from the first head
+        const float g = T.valid ? -invB : 0.f;   // d(-mean q1) / d q1
 #pragma unroll
         for (int n = 0; n < PER; ++n) {
             const f32x4_t wq = ld4(ct + SC.q1w + 16 * (t0 + n) + 4 * q);
@@ -402,26 +263,8 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
         }
         wload_t(wA, a.act + PA.W3, t0, lane);   // dA2 = W3^T dZ3
         TD3_BARRIER();
-        if (valid && wave == 0 && q == 0) q_acc += red_get<NW>(red, 1, lane) + ct[SC.q1b];
-        chain_get<NT>(B3, lane, in);
-        float dpre;
-        {
-            f32x4_t d[PER];
-            zero4<PER>(d);
-            wlayer(wB, in, d);
-            float pa = 0.f;   // d obj / d action = sum_f W1[f][D] dZc1[f]
-#pragma unroll
-            for (int n = 0; n < PER; ++n) {
-                d[n] = gate4(d[n], c1[n]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pa = fmaf(d[n][r], ctW1[(16 * (t0 + n) + 4 * q + r) * Dc + D], pa);
-            }
-            pa += __shfl_xor(pa, 16);
-            pa += __shfl_xor(pa, 32);
-            red_put(red, 2, wave, lane, pa);
-            TD3_BARRIER();
-            dpre = red_get<NW>(red, 2, lane) * (1.0f - act * act);   // tanh'
-        }
+        if (T.valid && wave == 0 && q == 0) q_acc += red_get<NW>(red, 1, lane) + ct[SC.q1b];
+        const float dpre = critic_to_action<NT, PER, NW, S>(ctW1, D, B3, red, 2, wave, t0, lane, wB, in, c1) * (1.0f - act * act);   // tanh'
         // ------------------------------------------------------------------ actor backward + weight gradients
         {
             f32x4_t v[PER], dz[PER];
@@ -442,46 +285,9 @@ __global__ __launch_bounds__(NW * 64, 1) void td3_actor_kernel(Td3GradArgs a) {
                 }
             }
         }
-        wload_t(wB, a.act + PA.W2, t0, lane);   // dA1 = W2^T dZ2
-        TD3_BARRIER();   // dZ3 published
-        dw_slab<NT, PER, S>(B2, B1, sl + SL.seg[4].slab_off, t0, lane, accum);   // net.4: dZ3^T A2
-        TD3_NO_HOIST();
-        chain_get<NT>(B2, lane, in);
-        {
-            f32x4_t d[PER];
-            zero4<PER>(d);
-            wlayer(wA, in, d);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { d[n] = gate4(d[n], a2[n]); chain_put(B3, lane, t0 + n, d[n]); }
-            vec_grad<PER>(sl + SL.seg[3].slab_off, t0, lane, d, accum);    // net.2 bias
-        }
-        TD3_BARRIER();   // dZ2 published
-        dw_slab<NT, PER, S>(B3, B0, sl + SL.seg[2].slab_off, t0, lane, accum);   // net.2: dZ2^T A1
-        TD3_NO_HOIST();
-        chain_get<NT>(B3, lane, in);
-        {
-            f32x4_t d[PER];
-            zero4<PER>(d);
-            wlayer(wB, in, d);
-#pragma unroll
-            for (int n = 0; n < PER; ++n) { d[n] = gate4(d[n], a1[n]); chain_put(B1, lane, t0 + n, d[n]); }
-            vec_grad<PER>(sl + SL.seg[1].slab_off, t0, lane, d, accum);    // net.0 bias
-        }
-        TD3_BARRIER();   // dZ1 published
-        {
-            f32x4_t acc[PER][CT];
-            dw_first<PER, XW>(B1, xin, t0, lane, acc);
-            float* seg = sl + SL.seg[0].slab_off;
-#pragma unroll
-            for (int n = 0; n < PER; ++n)
-#pragma unroll
-                for (int c = 0; c < CT; ++c) slab_put(seg + (((t0 + n) * CT + c) * 64 + lane) * 4, acc[n][c], accum);
-        }
+        actor_body_bwd<GateRelu, NT, PER, XW, S>(a.act + PA.W2, B0, B1, B2, B3, xin, t0, T, wA, wB, in, a1, a2, sl, SL);
     }
-    if (wave == 0) {
-        const float t = row_sum16(q_acc);
-        if (tid == 0) st4(sl + SL.scalar_off, f32x4_t{t, 0.f, 0.f, 0.f});
-    }
+    tile_scalars_put(sl + SL.scalar_off, wave, tid, {q_acc});
 }
 
 // ======================================================================================================== slab reduction + Adam + soft update
@@ -633,40 +439,27 @@ int td3_grid(int B) {   // one 16-sample group per workgroup, at most kTd3MaxSla
     const int ngroups = (B + kTd3Tile - 1) / kTd3Tile;
     return ngroups < kTd3MaxSlabs ? ngroups : kTd3MaxSlabs;
 }
-int64_t td3_workspace_floats(int D, int md, int B) {
+int64_t td3_workspace_floats(const Td3SlabLayout& actor, int D, int md, int B) {
     const int64_t g = td3_grid(B);
     // slabs + the gathered rows [B][td3_xg_stride(D)]
-    return g * (td3_actor_slab(D, md).stride + td3_critic_slab(D, md).stride) + (int64_t)B * td3_xg_stride(D);
+    return g * (actor.stride + td3_critic_slab(D, md).stride) + (int64_t)B * td3_xg_stride(D);
 }
+int64_t td3_workspace_floats(int D, int md, int B) { return td3_workspace_floats(td3_actor_slab(D, md), D, md, B); }
 bool td3_supported(int D, int A, int md) { return A == 1 && D >= 1 && D <= kTd3MaxD && (md == 64 || md == 128 || md == 256); }
 
-// Waves per workgroup of the gradient kernels.  Width 64 has four output tiles: four waves, one per SIMD.  Widths 128 and 256: eight
-// waves, two per SIMD, owning one / two of a layer's eight / sixteen output tiles (the non-MFMA instructions of one wave issue behind
-// the other's MFMAs); at width 128 that measured 60.4 us per optimizer step against 63.1 on four waves (profiles/r04_u_td3_waves_ab.txt).
-template <int MD, int DD, int KF>
-static int launch_grad_d(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
-    constexpr int NW = MD == 64 ? 4 : 8;
-    const size_t lds_bytes = sizeof(float) * (size_t)td3_lds(MD / 16, a.D).total;
-    if (critic) hipLaunchKernelGGL((td3_critic_kernel<MD, DD, NW, KF>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
-    else hipLaunchKernelGGL((td3_actor_kernel<MD, DD, NW, KF>), dim3(grid), dim3(NW * 64), lds_bytes, s, a);
-    PIME_HIP_TRY(hipGetLastError());
-    return PIME_OK;
-}
-template <int MD>
-static int launch_grad(bool critic, const Td3GradArgs& a, int grid, hipStream_t s) {
-    if (a.D == 3) return launch_grad_d<MD, 3, 2>(critic, a, grid, s);     // pH observation
-    if (a.D == 4) return launch_grad_d<MD, 4, 2>(critic, a, grid, s);     // water-tank Integrator observation
-    if (a.D == 12) return launch_grad_d<MD, 12, 8>(critic, a, grid, s);   // water-tank Stacking4
-    if (a.D == 30) return launch_grad_d<MD, 30, 8>(critic, a, grid, s);   // water-tank Stacking10
-    if (td3_first_ksteps(a.D) == 2) return launch_grad_d<MD, 0, 2>(critic, a, grid, s);
-    return launch_grad_d<MD, 0, 8>(critic, a, grid, s);
-}
+struct Td3Kernels {   // td3_device.hpp: grad_dispatch
+    using Args = Td3GradArgs;
+    template <int MD, int KF> static constexpr bool serves() { return true; }
+    static int lds_floats(int NT, int D) { return td3_lds(NT, D).total; }
+    template <int MD, int DD, int NW, int KF> static constexpr auto critic() { return td3_critic_kernel<MD, DD, NW, KF>; }
+    template <int MD, int DD, int NW, int KF> static constexpr auto actor() { return td3_actor_kernel<MD, DD, NW, KF>; }
+};
 int launch_td3_grad(bool critic, int md, const Td3GradArgs& a, int grid, hipStream_t s) {
-    if (md == 256) return launch_grad<256>(critic, a, grid, s);
-    if (md == 128) return launch_grad<128>(critic, a, grid, s);
-    if (md == 64) return launch_grad<64>(critic, a, grid, s);
-    set_error("no fused TD3 instantiation for width %d", md);
-    return PIME_ERR_ARG;
+    if (md != 64 && md != 128 && md != 256) {
+        set_error("no fused TD3 instantiation for width %d", md);
+        return PIME_ERR_ARG;
+    }
+    return grad_dispatch<Td3Kernels>(critic, md, a, grid, s);
 }
 int launch_td3_apply(const Td3ApplyArgs& a, hipStream_t s) {
     const int nwords = a.L.stride / 4;

@@ -41,7 +41,7 @@ COMPILED_D = (3, 4, 12, 30)
 
 
 def kernel_class(width, D):
-    """The instantiation `launch_grad` / `launch_td3_grad` of csrc/td3_fused.hip pick for (width, D): the state width compiled in
+    """The instantiation `launch_td3_grad` (csrc/td3_fused.hip; `grad_dispatch` of csrc/td3_device.hpp) picks for (width, D): the state width compiled in
     (D = 3, 4, 12, 30), else run-time D with two first-layer k-steps while the critic's D + 1 inputs fit 8 columns (td3.hpp:
     td3_first_ksteps), else with eight."""
     if D in COMPILED_D:

@@ -13,7 +13,7 @@ GRADIENT_SPECS = T.gradient_specs()
 
 
 def _launch_class(md, D):
-    # csrc/td3_fused.hip launch_grad<MD>: D == 3 | 4 | 12 | 30 compiled in; else run-time D, td3_first_ksteps(D) = (D + 1 <= 8 ? 2 : 8)
+    # csrc/td3_device.hpp grad_dispatch_d<K, MD>: D == 3 | 4 | 12 | 30 compiled in; else run-time D, td3_first_ksteps(D) = (D + 1 <= 8 ? 2 : 8)
     if D in (3, 4, 12, 30):
         return md, f"D{D}"
     return md, "rt2" if D + 1 <= 8 else "rt8"
