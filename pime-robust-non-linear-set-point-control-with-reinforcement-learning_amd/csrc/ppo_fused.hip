@@ -614,24 +614,33 @@ struct Gathered {
     float rsum, action, logprob, adv;
     float x0, x1, x2, x3;   // the first state columns ride along (all of them for the pH / tank envs)
 };
-template <bool WANT_ACTOR, bool WANT_CRITIC>
-__device__ __forceinline__ Gathered fused_gather(const PpoArgs& a, const int tile, const int li) {
-    Gathered g;
+__device__ __forceinline__ long long fused_gather_row(const PpoArgs& a, const int64_t* index_row, const int tile, const int li) {
     const int pos = tile * 32 + li;   // tiles past the batch run on clamped rows with dOut = 0
-    g.valid = pos < a.B;
-    const int64_t* const idx = a.indices + (a.index_row ? (size_t)a.index_row[0] * a.B : 0);
-    const long long row = idx[g.valid ? pos : a.B - 1];
-    g.xrow = a.state + (size_t)row * a.D;
+    const int64_t* const idx = a.indices + (index_row ? (size_t)index_row[0] * a.B : 0);
+    return idx[pos < a.B ? pos : a.B - 1];
+}
+// D: a.D (the pair kernel passes it opaque per group: its column tests are otherwise hoisted out of the group loop as per-lane
+// 0 / 1 registers and spilled)
+template <bool WANT_ACTOR, bool WANT_CRITIC>
+__device__ __forceinline__ Gathered fused_gather(const PpoArgs& a, const int D, const int tile, const int li) {
+    Gathered g;
+    g.valid = tile * 32 + li < a.B;
+    const long long row = fused_gather_row(a, a.index_row, tile, li);
+    g.xrow = a.state + (size_t)row * D;
     g.rsum = WANT_CRITIC ? a.r_sum[row] : 0.f;
     g.action = WANT_ACTOR ? a.action[row] : 0.f;
     g.logprob = WANT_ACTOR ? a.logprob[row] : 0.f;
     g.adv = WANT_ACTOR ? a.adv[row] : 0.f;
     g.x0 = g.x1 = g.x2 = g.x3 = 0.f;
-    if (a.D > 0) g.x0 = g.xrow[0];
-    if (a.D > 1) g.x1 = g.xrow[1];
-    if (a.D > 2) g.x2 = g.xrow[2];
-    if (a.D > 3) g.x3 = g.xrow[3];
+    if (D > 0) g.x0 = g.xrow[0];
+    if (D > 1) g.x1 = g.xrow[1];
+    if (D > 2) g.x2 = g.xrow[2];
+    if (D > 3) g.x3 = g.xrow[3];
     return g;
+}
+template <bool WANT_ACTOR, bool WANT_CRITIC>
+__device__ __forceinline__ Gathered fused_gather(const PpoArgs& a, const int tile, const int li) {
+    return fused_gather<WANT_ACTOR, WANT_CRITIC>(a, a.D, tile, li);
 }
 // the group's states into LDS: xs [wave][sample][D], and the padded rows of first_grad_valu (xsp).  rs: NULL, or the pair kernel's
 // [wave][32] segment that parks the critic's targets while the actor's body runs (a VGPR live across that body would be spilled)
@@ -681,8 +690,8 @@ __device__ __forceinline__ void fused_issue_images(const PpoArgs& a, float* __re
 // One 256-sample group of one net: forward, loss gradient, backward chain and weight gradients (into the workgroup's slab `bid`).
 // On entry the group's states are in LDS and the net's forward images are in flight (fused_issue_images' order).  `lane` comes
 // from the caller made opaque per group: hipcc otherwise hoists ~100 per-lane LDS / global offsets of the whole body out of the
-// (usually single-trip) group loop and spills them.  w_dead(): called once where the actor bodies are done with the W image for
-// good (only on the vector-ALU first-layer path, D <= kFirstValuMaxD; never by the critic's body).
+// (usually single-trip) group loop and spills them.  w_dead(): called once where the body is done with the W image for good
+// (from first_grad_valu, so only on the vector-ALU first-layer path, D <= kFirstValuMaxD; the pair kernel hooks both nets' bodies).
 template <int T, int KIND, class Hook = NoHook>
 __device__ __forceinline__ void fused_group(const PpoArgs& a, float* __restrict__ lds, const FusedLds& F, const int bid,
                                             const int group, const int lane, const int wave, const bool valid,
@@ -1093,11 +1102,16 @@ __global__ __launch_bounds__(kFusedThreads) void ppo_fused_kernel(PpoArgs a) {
 }
 
 // ---- actor and critic of a group in ONE workgroup ---------------------------------------------------------------------------
-// LDS map of the pair kernel: the actor's map, then the critic's small segments and the [wave][32] targets.  The critic uses the
-// actor's W / X / xs / xsp / hacc / wsum (the same 256 samples; the sums are written out and re-zeroed between the bodies).
+// LDS map of the pair kernel: the actor's map, then the critic's small segments, the [wave][32] segment `rsum` and, where 160 KB
+// have room for it, two more such segments (`park`, 0 = no room).  The second net of a group uses the first one's W / X / xs /
+// xsp / hacc / wsum (the same 256 samples; the sums are written out and re-zeroed between the bodies).  rsum / park hold the
+// second net's per-sample inputs while the first body runs (a VGPR live across a body would be spilled): the critic's target
+// (rsum), or the actor's action (rsum), old log-prob and advantage (park).  park is added only where the map still fits with it,
+// so what fits (fused_pair_fits) does not depend on it.
+constexpr size_t kPairLdsBytes = 160 * 1024;
 struct PairLds {
     FusedLds a, c;
-    int rsum, total;
+    int rsum, park, total;
 };
 __host__ __device__ inline PairLds pair_lds(int akind, int D, int Di, int T) {
     PairLds P{};
@@ -1114,22 +1128,41 @@ __host__ __device__ inline PairLds pair_lds(int akind, int D, int Di, int T) {
     seg(P.rsum, kFusedWaves * 32);
     seg(P.c.first0, md * (D + 1));
     P.c.first1 = 0;
+    P.park = 0;
+    if (sizeof(float) * (size_t)(o + 2 * kFusedWaves * 32) <= kPairLdsBytes) seg(P.park, 2 * kFusedWaves * 32);
     P.total = P.c.total = o;
     return P;
 }
 
-// Workgroup `bid` runs, for each of its groups, the actor's body and then the critic's on the same 8 tiles.  Against the dual
-// kernel (an actor workgroup retires, a critic workgroup is dispatched on the compute unit and pays a full preamble with the
-// matrix pipe idle) the group is gathered ONCE, the critic's small segments are loaded once per kernel beside the actor's, and the
-// critic's two forward images are started behind the actor's tail: net.2's when the actor's last dX step has read W (w_dead),
-// net.4's when its first-layer gradient is done with X -- so the critic's first layer starts with no exposed round trip.
-// Slab indices and layout, stash tile indexing and the order of every sum of a group are those of the single bodies; a workgroup
-// with ONE group (every batch up to 256 x 256 samples) produces the same bits as the dual kernel.  With several groups the
-// workgroup totals (head weight / bias, scalars) are added group by group instead of wave by wave.
+// Which workgroups run the critic's body first.  The two gradients are independent, so the order inside a workgroup is free; with
+// every workgroup in the same order the whole chip is in the same phase at the same time and the memory bursts of a body (image
+// DMAs, stash stores and re-reads, slab stores) arrive together.  Workgroup b usually lands on XCD b % 8 (a performance
+// assumption only): shift 3 alternates inside every XCD, shift 0 alternates whole XCDs.
+// Default bench, median of 9 interleaved runs: single order 28.86 ms, shift 3 28.46 ms (every run faster), shift 0 28.60 ms (overlaps).
+constexpr int kPairFlipShift = 3;
+__device__ __forceinline__ bool pair_flip(const int b) { return (b >> kPairFlipShift) & 1; }
+
+// Workgroup `bid` runs, for each of its groups, the two nets' bodies on the same 8 tiles, in two passes: the actor's and then the
+// critic's, or (pair_flip) the critic's and then the actor's.  Against the dual kernel (an actor workgroup retires, a critic
+// workgroup is dispatched on the compute unit and pays a full preamble with the matrix pipe idle) the group is gathered ONCE, both
+// nets' small segments are loaded once per kernel, and the second net's forward images are started behind the first body's tail:
+// the one that lands in W when the first body's last dX step has read W (w_dead), the rest when its first-layer gradient is done
+// with X -- so the second net's first layer starts with no exposed round trip.  (The modular actor's first two images land in X
+// and its counted waits rely on the order X, X, W: as second net all three are started behind the critic's body.)
+// The net of a pass is chosen at run time inside ONE pass loop, so each body exists once in the kernel's code (107 KB of
+// straight-line code behind a 64 KB instruction cache).
+// Slab indices and layout, stash tile indexing and the order of every sum of a group are those of the single bodies and do not
+// depend on the order of the passes; a workgroup with ONE group (every batch up to 256 x 256 samples) produces the same bits as
+// the dual kernel.  With several groups the workgroup totals (head weight / bias, scalars) are added group by group instead of
+// wave by wave.
 template <int T, int AKIND>
 __global__ __launch_bounds__(kFusedThreads) void ppo_fused_pair_kernel(PpoArgs actor, PpoArgs critic) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NI_TT = T * T * 1024 / (kFusedThreads * 4);
+    // the two nets work on the same batch of the same states (launch_ppo_fused_dual requires it): one set of scalars derived from
+    // B and D (1 / B, tile and group counts, stash regions, LDS offsets) for both bodies instead of two
+    critic.B = actor.B;
+    critic.D = actor.D;
     const int bid = (int)blockIdx.x, nb = (int)gridDim.x;
     const int tid0 = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -1138,44 +1171,120 @@ __global__ __launch_bounds__(kFusedThreads) void ppo_fused_pair_kernel(PpoArgs a
     float* const wbuf = lds + P.a.wbuf;
     float* const X = lds + P.a.x;
     float* const rs = lds + P.rsum;
+    float* const pk = lds + P.park;
     const MlpLayout Lc = mlp_layout(MLP_CRITIC, critic.D, critic.Di, T * 32);
+    [[maybe_unused]] const MlpLayout La = mlp_layout(AKIND, actor.D, actor.Di, T * 32);
     const float asl0 = actor.a_std_log[0];
+    [[maybe_unused]] const float clip0 = actor.ratio_clip;
+    const bool flip = pair_flip(bid);
     fused_net_setup<T, AKIND>(actor, lds, P.a, tid0);
     fused_net_setup<T, MLP_CRITIC>(critic, lds, P.c, tid0);
-    const bool early_w = actor.D <= kFirstValuMaxD;   // the actor's body calls w_dead
+    const bool early_w = actor.D <= kFirstValuMaxD;   // the bodies call w_dead
 #pragma unroll 1
     for (int group = bid; group < ngroups; group += nb) {
         const bool accum = group != bid;
-        // loop-variant on purpose (fused_group), the thread index too: everything derived from it (totals' slab addresses, the
-        // zeroing, the DMA offsets) would otherwise be hoisted out of the loop and spilled
-        int tid = tid0;
-        asm volatile("" : "+v"(tid));
-        const int lane = tid & 63;
-        float asl = asl0;
-        asm volatile("" : "+s"(asl));
-        const Gathered g = fused_gather<true, true>(actor, group * kFusedWaves + wave, lane & 31);
-        __syncthreads();  // the previous group's critic is done with W / X, its totals have been read
-        fused_zero_sums<T>(lds, P.a, tid);
-        fused_issue_images<T, AKIND>(actor, wbuf, X, tid);
-        fused_gather_store(actor, g, lds + P.a.xs, lds + P.a.xsp, rs, wave, lane & 31, lane >> 5);
-        PIME_LDS_BARRIER();   // the states are in LDS (the images are still in flight)
-        fused_group<T, AKIND>(actor, lds, P.a, bid, group, lane, wave, g.valid, 0.f, g.action, g.logprob, g.adv, asl,
-                              [&]() { dma_image<NI_TT>(wbuf, critic.img_fwd + Lc.off[1], tid); });
-        PIME_LDS_BARRIER();   // the actor is done with X (and W); its sums are complete
-        // the critic's forward images, in fused_issue_images' order: net.2's (unless it is in flight already), then net.4's
-        if (!early_w) dma_image<NI_TT>(wbuf, critic.img_fwd + Lc.off[1], tid);
-        dma_image<NI_TT>(X, critic.img_fwd + Lc.off[3], tid);
-        fused_totals<T, AKIND>(actor, lds, P.a, bid, tid, accum);
-        PIME_LDS_BARRIER();   // the totals have been read
-        int tid_c = tid0;
-        asm volatile("" : "+v"(tid_c));
-        fused_zero_sums<T>(lds, P.c, tid_c);   // (ordered before the critic's first sum by the barriers of its forward)
-        const int lane_c = tid_c & 63;
-        const bool valid = (group * kFusedWaves + wave) * 32 + (lane_c & 31) < critic.B;
-        const float rsum = rs[wave * 32 + (lane_c & 31)];
-        fused_group<T, MLP_CRITIC>(critic, lds, P.c, bid, group, lane_c, wave, valid, rsum, 0.f, 0.f, 0.f, 0.f);
-        PIME_LDS_BARRIER();   // the critic's sums are complete
-        fused_totals<T, MLP_CRITIC>(critic, lds, P.c, bid, tid_c, accum);
+        // the first net's per-sample inputs: the actor's (action, old log-prob, advantage) or the critic's (target)
+        float in0, in1, in2;
+        {
+            int tid = tid0;
+            asm volatile("" : "+v"(tid));
+            const int lane = tid & 63, s = wave * 32 + (lane & 31);
+            int Dg = actor.D;
+            asm volatile("" : "+s"(Dg));   // (fused_gather)
+            const Gathered g = fused_gather<true, true>(actor, Dg, group * kFusedWaves + wave, lane & 31);
+            __syncthreads();  // the previous group's second body is done with W / X, its totals have been read
+            if (flip) fused_issue_images<T, MLP_CRITIC>(critic, wbuf, X, tid);
+            else fused_issue_images<T, AKIND>(actor, wbuf, X, tid);
+            fused_gather_store(actor, g, lds + P.a.xs, lds + P.a.xsp, flip ? nullptr : rs, wave, lane & 31, lane >> 5);
+            if (flip && P.park && lane < 32) {
+                rs[s] = g.action;
+                pk[s] = g.logprob;
+                pk[kFusedWaves * 32 + s] = g.adv;
+            }
+            in0 = flip ? g.rsum : g.action;
+            in1 = g.logprob;
+            in2 = g.adv;
+            PIME_LDS_BARRIER();   // the states are in LDS (the images are still in flight)
+        }
+#pragma unroll 1
+        for (int pass = 0; pass < 2; ++pass) {
+            // Loop-variant on purpose: the order flag (the loop is neither unswitched on it nor unrolled: either would put a second
+            // copy of both bodies into the kernel) and the thread index (fused_group: everything derived from it -- totals' slab
+            // addresses, the zeroing, the DMA offsets -- would otherwise be hoisted out of the loops and spilled)
+            int fl = flip;
+            asm volatile("" : "+s"(fl));
+            const bool crit = (pass != 0) != (fl != 0);
+            int tid = tid0;
+            asm volatile("" : "+v"(tid));
+            const int lane = tid & 63, li = lane & 31, tile = group * kFusedWaves + wave;
+            const bool valid = tile * 32 + li < actor.B;
+            fused_zero_sums<T>(lds, P.a, tid);   // (ordered before the body's first sum by the barriers of its forward)
+            float n0 = 0.f, n1 = 0.f, n2 = 0.f;   // the second net's inputs
+            if (!crit) {
+                float asl = asl0;
+                asm volatile("" : "+s"(asl));
+                if constexpr (T == 4) {   // (at the 256-VGPR cap: the clip bounds 1 -+ ratio_clip are otherwise formed once per
+                    float clip = clip0;   //  kernel and held in two registers across both bodies, which then spill)
+                    asm volatile("" : "+s"(clip));
+                    actor.ratio_clip = clip;
+                }
+                fused_group<T, AKIND>(actor, lds, P.a, bid, group, lane, wave, valid, 0.f, in0, in1, in2, asl, [&]() {
+                    if (pass == 0) dma_image<NI_TT>(wbuf, critic.img_fwd + Lc.off[1], tid);
+                });
+                PIME_LDS_BARRIER();   // the actor is done with X (and W); its sums are complete
+                if (pass == 0) {
+                    // the critic's forward images, in fused_issue_images' order: net.2's (unless it is in flight already), net.4's
+                    if (!early_w) dma_image<NI_TT>(wbuf, critic.img_fwd + Lc.off[1], tid);
+                    dma_image<NI_TT>(X, critic.img_fwd + Lc.off[3], tid);
+                }
+                fused_totals<T, AKIND>(actor, lds, P.a, bid, tid, accum);
+            } else {
+                fused_group<T, MLP_CRITIC>(critic, lds, P.c, bid, group, lane, wave, valid, in0, 0.f, 0.f, 0.f, 0.f, [&]() {
+                    if constexpr (AKIND != MLP_MODULAR_ACTOR)
+                        if (pass == 0) dma_image<NI_TT>(wbuf, actor.img_fwd + La.off[1], tid);
+                });
+                // No room to park the actor's inputs: they are read again through the index (L2-hot rows).  The index goes out in
+                // front of the barrier, the three values in front of the image DMAs (a dependent load behind them would drain
+                // them); they are not needed before the actor's loss.
+                const bool reread = pass == 0 && !P.park;
+                long long row = 0;
+                if (reread) {
+                    const int64_t* ir = actor.index_row;
+                    asm volatile("" : "+s"(ir));   // (its NULL test shared with the gather's would be kept in a register across the body)
+                    row = fused_gather_row(actor, ir, tile, li);
+                }
+                PIME_LDS_BARRIER();   // the critic is done with X (and W); its sums are complete
+                if (pass == 0) {
+                    if (reread) {
+                        n0 = actor.action[row];
+                        n1 = actor.logprob[row];
+                        n2 = actor.adv[row];
+                    }
+                    if constexpr (AKIND == MLP_MODULAR_ACTOR) {
+                        fused_issue_images<T, AKIND>(actor, wbuf, X, tid);
+                    } else {
+                        if (!early_w) dma_image<NI_TT>(wbuf, actor.img_fwd + La.off[1], tid);
+                        dma_image<NI_TT>(X, actor.img_fwd + La.off[3], tid);
+                    }
+                }
+                fused_totals<T, MLP_CRITIC>(critic, lds, P.c, bid, tid, accum);
+            }
+            if (pass == 0) {
+                PIME_LDS_BARRIER();   // the totals have been read
+                const int s = wave * 32 + li;
+                if (!crit) {
+                    n0 = rs[s];
+                } else if (P.park) {
+                    n0 = rs[s];
+                    n1 = pk[s];
+                    n2 = pk[kFusedWaves * 32 + s];
+                }
+            }
+            // on every path, so that no input stays live across a body (both sit at the 256-VGPR cap)
+            in0 = n0;
+            in1 = n1;
+            in2 = n2;
+        }
     }
 }
 
@@ -1518,7 +1627,7 @@ template <int T, int AKIND>
 static int launch_pair(const PpoArgs& actor, const PpoArgs& critic, hipStream_t s) {
     const size_t lds_bytes = sizeof(float) * (size_t)pair_lds(AKIND, actor.D, actor.Di, T).total;
     static LdsLimit lds_limit;  // per instantiation
-    PIME_RAISE_LDS(lds_limit, (ppo_fused_pair_kernel<T, AKIND>), 160 * 1024);
+    PIME_RAISE_LDS(lds_limit, (ppo_fused_pair_kernel<T, AKIND>), kPairLdsBytes);
     hipLaunchKernelGGL((ppo_fused_pair_kernel<T, AKIND>), dim3(fused_grid(actor.B)), dim3(kFusedThreads), lds_bytes, s, actor, critic);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
@@ -1544,7 +1653,7 @@ int launch_ppo_fused_dual(int actor_kind, int md, const PpoArgs& actor, const Pp
 bool fused_pair_fits(int actor_kind, int D, int Di, int md) {
     const int T = md / 32;
     if (!(T == 2 || T == 4) || !(actor_kind == MLP_MODULAR_ACTOR || actor_kind == MLP_PLAIN_ACTOR)) return false;
-    return sizeof(float) * (size_t)pair_lds(actor_kind, D, Di, T).total <= 160 * 1024;
+    return sizeof(float) * (size_t)pair_lds(actor_kind, D, Di, T).total <= kPairLdsBytes;
 }
 
 // Does the kernel's LDS map fit?  (wide observations, e.g. the stacked water tank, do not: the caller then uses the
