@@ -381,7 +381,8 @@ int pime_rollout_h(pime_env* env, int32_t kind, int32_t md, const float* packed_
  * no auto-reset, no per-step host round trip -- with the env state in registers.  Handles in PIME_STATE_MIXED or PIME_STATE_F64
  * mode (the latter reproduces the reference's float64 protocol records to 1e-11), pH or Integrator water tank, Philox draws.
  *   kind         PIME_MLP_PLAIN_ACTOR | PIME_MLP_MODULAR_ACTOR | PIME_MLP_SAC_ACTOR (ActorSAC.forward = tanh(net_a_avg), net.py:197-199)
- *                with packed_actor = its pime_mlp_pack image (width 64 / 128), or -1:
+ *                | PIME_MLP_CRITIC (the TD3 Actor, net.py:96-110: a_env = tanh(net(s)) + s @ priorK)
+ *                with packed_actor = its pime_mlp_pack image (width 64 / 128; 256 except ActorSAC), or -1:
  *                the prior controller alone (get_linear_action, ph.py:227-231), packed_actor ignored
  *   seg_len      0: plain episode.  > 0: every seg_len steps (from step 0) a protocol segment starts: set-point r =
  *                setpoints[segment], integrated error 0, step counter 0, plant state kept -- what the protocols' `env.reset();
@@ -392,7 +393,8 @@ int pime_rollout_h(pime_env* env, int32_t kind, int32_t md, const float* packed_
  * Leaves every lane n_steps further; the caller resets the env before it rolls out again.
  * pime_rollout_eval_supported: 0 = not served; 1 = served (widths 64 / 128 in either state mode; width 256 -- the streamed rollout
  * kernel's evaluation mode, csrc/mlp16.hip -- in PIME_STATE_MIXED on the pH / Integrator observation, trace and schedule included);
- * 2 = returns and trace, but no set-point schedule (a Stacking observation at width 256: seg_len must be 0). */
+ * 2 = returns and trace, but no set-point schedule (a Stacking1 / 4 / 10 observation at width 256 under PIME_MLP_PLAIN_ACTOR or
+ * PIME_MLP_CRITIC: seg_len must be 0).  Stacking observations at widths 64 / 128 are not served. */
 int pime_rollout_eval_supported(const pime_env* env, int32_t kind, int32_t md);
 int pime_rollout_eval(pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
                       int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret, double* trace,
@@ -404,9 +406,12 @@ int pime_rollout_eval(pime_env* env, int32_t kind, int32_t md, const float* pack
  * (replay.py:290-300) -- as ONE launch for n_steps lock-steps of every lane: deterministic actor forward on the matrix cores,
  * clipped exploration noise (Philox stream 2, counter (lane, noise_epoch, t)), env action a_env = a + s @ priorK (priorK zeros:
  * plain TD3), env step with in-kernel auto-reset, transition written into the device ring.  The running episodes CONTINUE (no
- * reset in front).  Handle in PIME_STATE_MIXED mode, pH or Integrator water tank, Philox draws.
+ * reset in front).  Handle in PIME_STATE_MIXED mode, Philox draws; pH, Integrator water tank, or the water tank's Stacking
+ * observation with num_stack 1 / 4 / 10 (there the handle's frame ring is rewritten when the launch ends, so pime_env_step /
+ * pime_env_observe continue from it).  Widths 64 / 128: the LDS-resident image (csrc/rollout_offpolicy.hip); width 256: the
+ * streamed kernel (csrc/mlp16.hip).  Anything else (another num_stack, PIME_STATE_F64 / MIXED16): PIME_ERR_ARG.
  *   packed_actor  pime_mlp_pack image of kind PIME_MLP_CRITIC built from the TD3 Actor's tensors (net.py:96-110 has CriticAdv's
- *                 shape and ReLUs; the kernel applies the tanh), width md = 64 / 128
+ *                 shape and ReLUs; the kernel applies the tanh), width md = 64 / 128 / 256
  *   obs           [dev] float32[N, obs_dim]: in = the lanes' current observation, out = the observation after the last step
  *   ring_state    [dev] float32[slots, N, obs_dim]; ring_other [dev] float32[slots, N, 3] = (reward * reward_scale, mask = 0 if done
  *                 else gamma, action); slots slot0 .. slot0 + n_steps - 1 (mod slots) are written: the successor of (slot, lane) is
@@ -418,7 +423,7 @@ int pime_rollout_offpolicy(pime_env* env, int32_t md, const float* packed_actor,
 /* The same launch for AgentSAC -- replaces AgentBase.explore_env's body (elegantrl/agent.py:54-70) with AgentSAC.select_action
  * (:425-431) and ActorSAC.get_action (net.py:201-205): a = tanh(avg + exp(clamp(log_std, -20, 2)) * eps), eps the SAME Philox
  * stream-2 draw (counter (lane, noise_epoch, t)); the ring stores the squashed action.  packed_actor: pime_mlp_pack image of kind
- * PIME_MLP_SAC_ACTOR, width 64 / 128; everything else as pime_rollout_offpolicy. */
+ * PIME_MLP_SAC_ACTOR, width 64 / 128, pH or Integrator water tank only; everything else as pime_rollout_offpolicy. */
 int pime_rollout_offpolicy_sac_supported(const pime_env* env, int32_t md);
 int pime_rollout_offpolicy_sac(pime_env* env, int32_t md, const float* packed_actor, const double* priorK, float gamma,
                                float reward_scale, int32_t n_steps, uint64_t noise_seed, uint32_t noise_epoch, float* obs,

@@ -802,12 +802,14 @@ int pime_rollout_h(pime_env* e, int32_t kind, int32_t md, const float* packed_ac
 int pime_rollout_eval_supported(const pime_env* e, int32_t kind, int32_t md) {
     if (e == nullptr) return 0;
     if (e->cfg.state_mode != PIME_STATE_MIXED && e->cfg.state_mode != PIME_STATE_F64) return 0;
-    if (e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0) {   // Stacking: the width-256 kernel only (plain actor, returns only)
+    if (e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0) {   // Stacking: the width-256 kernel only (plain actor or the TD3 Actor, returns only)
         const int S = e->cfg.num_stack;
-        return (md == 256 && kind == PIME_MLP_PLAIN_ACTOR && e->cfg.state_mode == PIME_STATE_MIXED && (S == 1 || S == 4 || S == 10)) ? 2 : 0;
+        return (md == 256 && (kind == PIME_MLP_PLAIN_ACTOR || kind == PIME_MLP_CRITIC) && e->cfg.state_mode == PIME_STATE_MIXED &&
+                (S == 1 || S == 4 || S == 10)) ? 2 : 0;
     }   // (2: returns and trace, no set-point schedule -- the protocols of utils/test.py are written for the Integrator observation)
     if (kind == -1) return 1;                                            // the prior controller alone
-    if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR) return 0;
+    // (PIME_MLP_CRITIC: the TD3 Actor, a_env = tanh(net(s)) + s . priorK)
+    if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR && kind != PIME_MLP_CRITIC) return 0;
     if (md == 256) return e->cfg.state_mode == PIME_STATE_MIXED ? 1 : 0;   // the streamed kernel's evaluation mode (float32 state)
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
@@ -851,7 +853,14 @@ int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {
     if (e == nullptr || e->cfg.state_mode != PIME_STATE_MIXED) return 0;
-    if (e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0) return 0;
+    const bool stacking = e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0;
+    if (kind == PIME_MLP_CRITIC) {   // the TD3 Actor: also Stacking1/4/10, and width 256 (the streamed kernel, mlp16.hip)
+        const int S = e->cfg.num_stack;
+        if (stacking && !(S == 1 || S == 4 || S == 10)) return 0;
+        if (md == 256) return 1;
+    } else if (stacking) {
+        return 0;
+    }
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
 int pime_rollout_offpolicy_supported(const pime_env* e, int32_t md) { return offpolicy_supported(e, PIME_MLP_CRITIC, md); }
@@ -862,13 +871,13 @@ static int rollout_offpolicy_common(pime_env* e, int32_t kind, int32_t md, const
                                     uint32_t noise_epoch, float* obs, float* ring_state, float* ring_other, int32_t slot0, int32_t slots,
                                     pime_stream stream) {
     PIME_REQUIRE(e != nullptr, "NULL env handle");
-    PIME_REQUIRE(offpolicy_supported(e, kind, md), "pime_rollout_offpolicy: not served for this handle / width %d", md);
+    PIME_REQUIRE(offpolicy_supported(e, kind, md), "pime_rollout_offpolicy: not served for this handle (state mode, num_stack) / width %d", md);
     PIME_REQUIRE(packed_actor && priorK && obs && ring_state && ring_other && n_steps >= 1 && slots >= 2 && slot0 >= 0 &&
                  slot0 < slots && n_steps <= slots, "pime_rollout_offpolicy: bad arguments");
     if (!e->was_reset) { set_error("pime_rollout_offpolicy before pime_env_reset"); return PIME_ERR_STATE; }
     if (int rc = use_device(e)) return rc;
     OffPolicyArgs a{};
-    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
+    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : (e->cfg.num_stack == 0 ? 1 : 2);
     a.n = e->cfg.n_envs;
     a.env_offset = e->cfg.env_offset;
     if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 1; a.st = e->ph32; }

@@ -34,6 +34,7 @@
 #include "ppo_device.hpp"
 #include "ppo_train.hpp"
 #include "rollout.hpp"
+#include "rollout_offpolicy.hpp"
 
 namespace pime {
 
@@ -1683,6 +1684,49 @@ __device__ __forceinline__ float pick_col(const float (&obs)[D], int c0, int g) 
     return g == 0 ? v0 : (g == 1 ? v1 : (g == 2 ? v2 : v3));
 }
 
+// The plain net's mean for this lane's sample from the observation registers: first layer from the LDS-resident image, the two
+// md x md layers streamed (QUAD: a quad of every layer's output tiles per wave), head on the vector ALUs.  ACT 1: the PPO actor's
+// Tanh; 0: the TD3 Actor's ReLU (net.py:96-110) -- the same image (pack16_kernel packs weights only).  Shared by the on-policy /
+// evaluation kernel and the off-policy one, so both run literally the same forward.
+template <int T, int D, int ACT, bool QUAD>
+__device__ __forceinline__ float plain_forward16(const float* __restrict__ lds, const Lds16& S, const Layout16& L,
+                                                 const float* __restrict__ img, float* __restrict__ region,
+                                                 [[maybe_unused]] float* __restrict__ xb, int lane, int tid, const float (&obs)[D]) {
+    const int g = lane >> 4;
+    float xr[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) xr[ks] = pick_col<D>(obs, 4 * ks, g);
+    f32x4 h1[T], h2[T];
+    first16<T, ACT>(lds + S.w0, lds + S.b0, L.KS0, lane, xr, h1);
+    PIME_NO_HOIST();
+    if constexpr (QUAD) {
+        layer16q<T, ACT>(img + L.w1, lds + S.b1, region, xb, lane, tid, h1, h2);
+        PIME_NO_HOIST();
+        layer16q<T, ACT>(img + L.w2, lds + S.b2, region, xb, lane, tid, h2, h1);
+    } else {
+        layer16<T, ACT, true>(img + L.w1, lds + S.b1, region, lane, tid, h1, h2);
+        PIME_NO_HOIST();
+        layer16<T, ACT, true>(img + L.w2, lds + S.b2, region, lane, tid, h2, h1);
+    }
+    return head16<T>(lds + S.w3, lds[S.b3], lane, h1);
+}
+
+// Stacking observation = the last STACK frames [h1, h2, r], oldest first; the observation registers ARE the frame deque.
+// After a step: deque(maxlen=S).append (nonlinear_watertank.py:1143-1144), or after a reset every frame = the first one (:1181-1183).
+template <int D>
+__device__ __forceinline__ void frames_advance16(const float (&obs)[D], const WtLane<float>& W, bool rst, float (&nxt)[D]) {
+#pragma unroll
+    for (int j = 0; j < D - 3; ++j) nxt[j] = rst ? (j % 3 == 0 ? W.h1 : (j % 3 == 1 ? W.h2 : W.r)) : obs[j + 3];
+    nxt[D - 3] = W.h1; nxt[D - 2] = W.h2; nxt[D - 1] = W.r;
+}
+// hand-over to the step-per-launch kernels' frame ring: slot j = frame j, oldest at slot 0
+template <int D>
+__device__ __forceinline__ void frames_store16(const WtPtrs<float>& wst, int N, int i, const float (&obs)[D]) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) wst.frames[(size_t)j * N + i] = obs[j];
+    wst.head[i] = 0;
+}
+
 // QUAD (launches of <= 4 096 lanes): the four waves share ONE 16-lane tile, each a quad of every layer's output tiles (layer16q; two
 // tiles of the modular actor's tower layers: layer16rq) -- 256 workgroups instead of 64 for the reference script's 4 096 lanes, a quarter of the MFMA chain per env step.
 template <int T, int KIND, int ENV, int STACK, bool QUAD = false>
@@ -1786,22 +1830,7 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
             else layer16<T, 1, true>(a.img + Lm.wn, lds + Sm.bn, region, lane, tid, cat, n0);
             a_avg = head16<T>(lds + Sm.w3, lds[Sm.b3], lane, n0);
         } else {
-            float xr[8];
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) xr[ks] = pick_col<D>(obs, 4 * ks, g);
-            f32x4 h1[T], h2[T];
-            first16<T, 1>(lds + S.w0, lds + S.b0, L.KS0, lane, xr, h1);
-            PIME_NO_HOIST();
-            if constexpr (QUAD) {
-                layer16q<T, 1>(a.img + L.w1, lds + S.b1, region, xb, lane, tid, h1, h2);
-                PIME_NO_HOIST();
-                layer16q<T, 1>(a.img + L.w2, lds + S.b2, region, xb, lane, tid, h2, h1);
-            } else {
-                layer16<T, 1, true>(a.img + L.w1, lds + S.b1, region, lane, tid, h1, h2);
-                PIME_NO_HOIST();
-                layer16<T, 1, true>(a.img + L.w2, lds + S.b2, region, lane, tid, h2, h1);
-            }
-            a_avg = head16<T>(lds + S.w3, lds[S.b3], lane, h1);
+            a_avg = plain_forward16<T, D, KIND == MLP_CRITIC ? 0 : 1, QUAD>(lds, S, L, a.img, region, xb, lane, tid, obs);
         }
         // from here on: rollout.hip's step, one env lane per (wave, lane & 15)
         float eps = 0.f;
@@ -1832,10 +1861,8 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
             if (rst) wt_lane_reset<float>(a.wp, gid, nullptr, W);
             if constexpr (ENV == 1) {
                 nxt[0] = W.h1; nxt[1] = W.h2; nxt[2] = W.r; nxt[D - 1] = W.I;
-            } else {   // deque(maxlen=S).append (:1143-1144), or after a reset every frame = the first one (:1181-1183)
-#pragma unroll
-                for (int j = 0; j < D - 3; ++j) nxt[j] = rst ? (j % 3 == 0 ? W.h1 : (j % 3 == 1 ? W.h2 : W.r)) : obs[j + 3];
-                nxt[D - 3] = W.h1; nxt[D - 2] = W.h2; nxt[D - 1] = W.r;
+            } else {
+                frames_advance16<D>(obs, W, rst, nxt);
             }
         }
         ret += (double)rew;
@@ -1865,11 +1892,7 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
     if (writer) {
         if constexpr (ENV == 0) ph_lane_store<float>(a.p, a.st, i, E);
         else wt_lane_store<float>(a.wp, a.wst, i, W);
-        if constexpr (ENV == 2) {   // the frame ring of the step-per-launch kernels: slot j = frame j, oldest at slot 0
-#pragma unroll
-            for (int j = 0; j < D; ++j) a.wst.frames[(size_t)j * N + i] = obs[j];
-            a.wst.head[i] = 0;
-        }
+        if constexpr (ENV == 2) frames_store16<D>(a.wst, N, i, obs);
         if (evaluating && a.ret) a.ret[i] += ret;
     }
 }
@@ -1906,8 +1929,125 @@ int launch_rollout16(int kind, const RolloutArgs& a, hipStream_t s) {
         if (a.env == 2 && a.wp.num_stack == 1) return launch_rollout16_t<MLP_PLAIN_ACTOR, 2, 1>(a, s);
         if (a.env == 2 && a.wp.num_stack == 4) return launch_rollout16_t<MLP_PLAIN_ACTOR, 2, 4>(a, s);
         if (a.env == 2 && a.wp.num_stack == 10) return launch_rollout16_t<MLP_PLAIN_ACTOR, 2, 10>(a, s);
+    } else if (kind == MLP_CRITIC && a.eval_mode) {   // the TD3 Actor (ReLU layers, a_env = tanh(net(s)) + s . K): evaluation only
+        if (a.env == 0) return launch_rollout16_t<MLP_CRITIC, 0, 0>(a, s);
+        if (a.env == 1) return launch_rollout16_t<MLP_CRITIC, 1, 0>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 1) return launch_rollout16_t<MLP_CRITIC, 2, 1>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 4) return launch_rollout16_t<MLP_CRITIC, 2, 4>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 10) return launch_rollout16_t<MLP_CRITIC, 2, 10>(a, s);
     }
     set_error("no width-256 fused rollout for env %d kind %d", a.env, kind);
+    return PIME_ERR_ARG;
+}
+
+// ==================================================================================================== fused off-policy exploration, width 256
+// rollout_offpolicy_kernel's step (csrc/rollout_offpolicy.hip: the TD3 Actor's mean, clipped exploration noise, prior term, env step
+// with in-kernel auto-reset, the transition written into the device ring; the running episodes continue) around the streamed
+// forward above, for the width the LDS-resident image cannot hold.  Tiling, LDS map and lane roles are rollout16_kernel's.
+// ENV as there: 0 pH, 1 water tank Integrator observation, 2 water tank Stacking (STACK frames; the observation registers are the
+// frame deque, handed over to the step-per-launch kernels' frame ring when the launch ends).
+template <int T, int ENV, int STACK, bool QUAD>
+__global__ __launch_bounds__(k16Threads, 1) void rollout16_offpolicy_kernel(OffPolicyArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int D = ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sl = lane & 15, g = lane >> 4;
+    const Layout16 L = layout16(D, T * 16);
+    const Lds16 S = lds16<T>(D, false);
+    stage_small16<T>(lds, S, a.img, L, tid);
+    __syncthreads();
+    float* const region = lds + S.region;
+    float* const xb = lds + S.total;   // QUAD: the activation exchange buffer behind the map
+    const int N = a.n;
+    const int m = QUAD ? blockIdx.x * 16 + sl : blockIdx.x * k16Group + wave * 16 + sl;
+    const bool valid = m < N;
+    const int i = valid ? m : N - 1;   // idle lanes shadow the last env (compute, never store)
+    const bool writer = valid && g == 0 && (!QUAD || wave == 0);
+    const uint32_t gid = a.env_offset + (uint32_t)i;
+
+    PhLane<float> E{};
+    WtLane<float> W{};
+    if constexpr (ENV == 0) ph_lane_load<float>(a.p, a.st, i, E);
+    else wt_lane_load<float>(a.wp, a.wst, i, W);
+    float obs[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) obs[j] = a.obs[(size_t)D * i + j];
+    int slot = a.slot0;
+    for (int t = 0; t < a.n_steps; ++t) {
+        PIME_NO_HOIST();
+        const float mean = plain_forward16<T, D, 0, QUAD>(lds, S, L, a.img, region, xb, lane, tid, obs);
+        double ua, ub;
+        philox_pair(a.noise_seed, gid, a.noise_epoch, (uint32_t)t, STREAM_EXPLORE16, ua, ub);
+        const float eps = (float)(sqrt(-2.0 * log(1.0 - ua)) * cos(6.283185307179586476925286766559 * ub));
+        const float act = clip(tanhf(mean) + eps * a.explore_noise, -1.0f, 1.0f);   // agent.py:303-305
+        double a_env = (double)act;
+#pragma unroll
+        for (int j = 0; j < D; ++j) a_env += (double)obs[j] * a.K.k[j];
+        float nxt[D], rew;
+        bool d;
+        if constexpr (ENV == 0) {
+            float o3[3];
+            d = ph_lane_step<float>(a.p, a.st.table, a_env, E, o3, rew);
+            if (d) ph_lane_reset<float>(a.p, a.st.table, gid, nullptr, E, o3);     // in-kernel auto-reset
+            nxt[0] = o3[0]; nxt[1] = o3[1]; nxt[2] = o3[2];
+        } else {
+            double z1n, z2n;
+            wt_lane_noise<float>(a.wp, gid, W, nullptr, z1n, z2n);
+            d = wt_lane_step<float>(a.wp, a_env, z1n, z2n, W, rew);
+            if (d) wt_lane_reset<float>(a.wp, gid, nullptr, W);
+            if constexpr (ENV == 1) {
+                nxt[0] = W.h1; nxt[1] = W.h2; nxt[2] = W.r; nxt[D - 1] = W.I;
+            } else {
+                frames_advance16<D>(obs, W, d, nxt);
+            }
+        }
+        if (writer) {   // replay.py:290-300: the state the action was taken in; (reward * scale, mask, action)
+            float* sp = a.ring_state + ((size_t)slot * N + i) * D;
+#pragma unroll
+            for (int j = 0; j < D; ++j) sp[j] = obs[j];
+            float* o = a.ring_other + ((size_t)slot * N + i) * 3;
+            o[0] = rew * a.reward_scale; o[1] = d ? 0.0f : a.gamma; o[2] = act;
+        }
+        slot = slot + 1 == a.slots ? 0 : slot + 1;
+#pragma unroll
+        for (int j = 0; j < D; ++j) obs[j] = nxt[j];
+    }
+    if (writer) {
+        if constexpr (ENV == 0) ph_lane_store<float>(a.p, a.st, i, E);
+        else wt_lane_store<float>(a.wp, a.wst, i, W);
+        if constexpr (ENV == 2) frames_store16<D>(a.wst, N, i, obs);
+#pragma unroll
+        for (int j = 0; j < D; ++j) a.obs[(size_t)D * i + j] = obs[j];
+    }
+}
+
+template <int ENV, int STACK, bool QUAD>
+static int launch_off16_q(const OffPolicyArgs& a, hipStream_t s) {
+    constexpr int T = 16, D = ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK);
+    const size_t lds_bytes = sizeof(float) * ((size_t)lds16<T>(D, false).total + (QUAD ? T * 64 * 4 : 0));   // as launch_rollout16_q
+    static LdsLimit lds_limit;  // per instantiation
+    PIME_RAISE_LDS(lds_limit, (rollout16_offpolicy_kernel<T, ENV, STACK, QUAD>), 160 * 1024);
+    const int per_wg = QUAD ? 16 : k16Group;
+    hipLaunchKernelGGL((rollout16_offpolicy_kernel<T, ENV, STACK, QUAD>), dim3((a.n + per_wg - 1) / per_wg), dim3(k16Threads), lds_bytes, s, a);
+    PIME_HIP_TRY(hipGetLastError());
+    return PIME_OK;
+}
+template <int ENV, int STACK>
+static int launch_off16_t(const OffPolicyArgs& a, hipStream_t s) {
+    bool quad = a.n <= 4096;   // the rule of launch_rollout16_t
+    if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
+    if (quad) return launch_off16_q<ENV, STACK, true>(a, s);
+    return launch_off16_q<ENV, STACK, false>(a, s);
+}
+
+// width 256 (csrc/rollout_offpolicy.hip dispatches here): the TD3 Actor only
+int launch_rollout16_offpolicy(const OffPolicyArgs& a, hipStream_t s) {
+    PIME_REQUIRE(a.kind == MLP_CRITIC, "the width-256 fused off-policy rollout serves the TD3 Actor (kind %d)", a.kind);
+    if (a.env == 0) return launch_off16_t<0, 0>(a, s);
+    if (a.env == 1) return launch_off16_t<1, 0>(a, s);
+    if (a.env == 2 && a.wp.num_stack == 1) return launch_off16_t<2, 1>(a, s);
+    if (a.env == 2 && a.wp.num_stack == 4) return launch_off16_t<2, 4>(a, s);
+    if (a.env == 2 && a.wp.num_stack == 10) return launch_off16_t<2, 10>(a, s);
+    set_error("no width-256 fused off-policy rollout for env %d", a.env);
     return PIME_ERR_ARG;
 }
 

@@ -204,7 +204,8 @@ static int launch_rollout_t(const RolloutArgs& a, hipStream_t s) {
 int launch_rollout(int kind, int md, const RolloutArgs& a, hipStream_t s) {
     const int D = a.env == 0 ? 3 : (a.env == 1 ? 4 : 3 * a.wp.num_stack);
     if (int rc = mlp_check(kind, D, kind == MLP_MODULAR_ACTOR ? 1 : 0, md)) return rc;
-    PIME_REQUIRE(kind != MLP_CRITIC, "rollout needs an actor image");
+    // (MLP_CRITIC is also the image kind of the TD3 Actor: served by the width-256 kernel's evaluation mode only)
+    PIME_REQUIRE(kind != MLP_CRITIC || (md == 256 && a.eval_mode), "rollout needs an actor image");
     if (md == 256) return launch_rollout16(kind, a, s);
     const int T = md / 32;
 #define PIME_RS(TT, SS) \

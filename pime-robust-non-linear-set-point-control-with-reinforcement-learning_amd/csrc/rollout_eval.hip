@@ -9,6 +9,7 @@
 //     over; :209-349 water tank: r = 3,6,9,4,2; utils/robust_test.py:4-46): a segment boundary does what the protocol's
 //     `env.reset(); set_state(last); set_r(r)` leaves behind -- integrated error 0, step counter 0, new set-point, plant state
 //     kept -- and the trace holds what the protocol appends per step.
+// KIND = MLP_CRITIC: the TD3 Actor (net.py:96-110: CriticAdv's shape and ReLUs, the tanh applied here), a_env = tanh(net(s)) + s @ priorK.
 // KIND = -1: the prior controller alone (get_linear_action, ph.py:227-231 / nonlinear_watertank.py:755-759 without its clip).
 // S = float (PIME_STATE_MIXED) or double (PIME_STATE_F64: the golden-pinned protocol tests run here, 1e-11).
 // The policy forward is rollout_policy.hpp -- the code of the rollout kernel; the env arithmetic is env_device.hpp.
@@ -130,7 +131,6 @@ template <typename S>
 int launch_rollout_eval(int kind, int md, const EvalArgs<S>& a, hipStream_t s) {
     if (kind >= 0) {
         if (int rc = mlp_check(kind, a.env == 0 ? 3 : 4, kind == MLP_MODULAR_ACTOR ? 1 : 0, md)) return rc;
-        PIME_REQUIRE(kind != MLP_CRITIC, "evaluation needs an actor image");
     }
     const int T = kind < 0 ? 0 : md / 32;
 #define PIME_EV(TT, KK, EE) \
@@ -139,6 +139,7 @@ int launch_rollout_eval(int kind, int md, const EvalArgs<S>& a, hipStream_t s) {
     PIME_EV(4, MLP_MODULAR_ACTOR, 0) PIME_EV(2, MLP_MODULAR_ACTOR, 0) PIME_EV(4, MLP_PLAIN_ACTOR, 0) PIME_EV(2, MLP_PLAIN_ACTOR, 0)
     PIME_EV(4, MLP_MODULAR_ACTOR, 1) PIME_EV(2, MLP_MODULAR_ACTOR, 1) PIME_EV(4, MLP_PLAIN_ACTOR, 1) PIME_EV(2, MLP_PLAIN_ACTOR, 1)
     PIME_EV(4, MLP_SAC_ACTOR, 0) PIME_EV(2, MLP_SAC_ACTOR, 0) PIME_EV(4, MLP_SAC_ACTOR, 1) PIME_EV(2, MLP_SAC_ACTOR, 1)   // tanh(net_a_avg): ActorSAC.forward
+    PIME_EV(4, MLP_CRITIC, 0) PIME_EV(2, MLP_CRITIC, 0) PIME_EV(4, MLP_CRITIC, 1) PIME_EV(2, MLP_CRITIC, 1)   // the TD3 Actor: tanh(net(s)), ReLU layers
 #undef PIME_EV
     set_error("no fused evaluation instantiation for env %d kind %d width %d", a.env, kind, md);
     return PIME_ERR_ARG;

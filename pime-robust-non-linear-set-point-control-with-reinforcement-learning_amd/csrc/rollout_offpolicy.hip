@@ -12,6 +12,8 @@
 // = env_device.hpp; exploration noise = the rollout kernel's Philox stream 2.
 // KIND = MLP_SAC_ACTOR: AgentSAC's exploration (agent.py:425-431 with net.py:201-205) -- the stochastic actor's two heads from the
 // same forward, a = tanh(avg + exp(clamp(log_std, -20, 2)) * eps) with eps the same stream-2 draw; everything else is shared.
+// ENV 2 (the TD3 Actor only): the water tank's Stacking1/4/10 observation -- the observation registers are the frame deque, as in
+// csrc/rollout.hip.  Width 256: the streamed sibling rollout16_offpolicy_kernel (csrc/mlp16.hip), the same step around another forward.
 #include <cstdlib>
 #include "env_device.hpp"
 #include "rollout_offpolicy.hpp"
@@ -22,11 +24,17 @@ namespace pime {
 constexpr uint32_t STREAM_EXPLORE_OFFPOLICY = 2;   // = rollout.hip's STREAM_EXPLORE
 constexpr int kOffThreads = 256;   // four waves of 16 lanes: one per SIMD (16-lane tiles, rollout_policy.hpp: policy_forward16)
 
+// ENV 0: pH, obs [y, r, I];  1: water tank, Integrator obs [h1, h2, r, I];  2: water tank, Stacking obs = the last STACK frames
+// [h1, h2, r], oldest first (csrc/rollout.hip)
+template <int ENV, int STACK>
+constexpr int off_obs_dim() { return ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK); }
+
 // QUAD (launches of <= 4 096 lanes): one 16-lane tile per workgroup, split over its four waves (rollout_policy.hpp: policy_forward16q)
-template <int T, int ENV, bool QUAD, int KIND>
+template <int T, int ENV, bool QUAD, int KIND, int STACK = 0>
 __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolicyArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int D = ENV == 0 ? 3 : 4;
+    constexpr int D = off_obs_dim<ENV, STACK>();
+    static_assert(ENV != 2 || KIND == MLP_CRITIC, "the Stacking observation: the TD3 Actor only");
     const MlpLayout L = mlp_layout(KIND, D, 0, T * 32);
     stage_image(lds, a.img, L.total / 4);
     __syncthreads();
@@ -72,7 +80,13 @@ __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolic
             wt_lane_noise<float>(a.wp, gid, W, nullptr, z1n, z2n);
             d = wt_lane_step<float>(a.wp, a_env, z1n, z2n, W, rew);
             if (d) wt_lane_reset<float>(a.wp, gid, nullptr, W);
-            nxt[0] = W.h1; nxt[1] = W.h2; nxt[2] = W.r; nxt[3] = W.I;
+            if constexpr (ENV == 1) {
+                nxt[0] = W.h1; nxt[1] = W.h2; nxt[2] = W.r; nxt[3] = W.I;
+            } else {   // deque(maxlen=S).append, or after a reset every frame = the first one (as rollout_kernel)
+#pragma unroll
+                for (int j = 0; j < D - 3; ++j) nxt[j] = d ? (j % 3 == 0 ? W.h1 : (j % 3 == 1 ? W.h2 : W.r)) : obs[j + 3];
+                nxt[D - 3] = W.h1; nxt[D - 2] = W.h2; nxt[D - 1] = W.r;
+            }
         }
         if (writer) {   // replay.py:290-300: the state the action was taken in; (reward * scale, mask, action)
             float* s = a.ring_state + ((size_t)slot * N + i) * D;
@@ -88,6 +102,11 @@ __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolic
     if (writer) {
         if constexpr (ENV == 0) ph_lane_store<float>(a.p, a.st, i, E);
         else wt_lane_store<float>(a.wp, a.wst, i, W);
+        if constexpr (ENV == 2) {   // the frame ring of the step-per-launch kernels: slot j = frame j, oldest at slot 0
+#pragma unroll
+            for (int j = 0; j < D; ++j) a.wst.frames[(size_t)j * N + i] = obs[j];
+            a.wst.head[i] = 0;
+        }
 #pragma unroll
         for (int j = 0; j < D; ++j) a.obs[(size_t)D * i + j] = obs[j];
     }
@@ -95,35 +114,45 @@ __global__ __launch_bounds__(kOffThreads) void rollout_offpolicy_kernel(OffPolic
 
 int mlp_check(int kind, int D, int Di, int md);
 
-template <int T, int ENV, bool QUAD, int KIND>
+int launch_rollout16_offpolicy(const OffPolicyArgs& a, hipStream_t s);   // width 256: the streamed 16-tile family (mlp16.hip)
+
+template <int T, int ENV, bool QUAD, int KIND, int STACK>
 static int launch_off_q(const OffPolicyArgs& a, hipStream_t s) {
-    const size_t lds_bytes = ((size_t)mlp_layout(KIND, ENV == 0 ? 3 : 4, 0, T * 32).total + (QUAD ? quad_xchg_floats<T>() : 0)) * sizeof(float);
+    const size_t lds_bytes = ((size_t)mlp_layout(KIND, off_obs_dim<ENV, STACK>(), 0, T * 32).total + (QUAD ? quad_xchg_floats<T>() : 0)) * sizeof(float);
     static LdsLimit lds_limit;  // per instantiation
-    PIME_RAISE_LDS(lds_limit, (rollout_offpolicy_kernel<T, ENV, QUAD, KIND>), 160 * 1024);
+    PIME_RAISE_LDS(lds_limit, (rollout_offpolicy_kernel<T, ENV, QUAD, KIND, STACK>), 160 * 1024);
     const int per_wg = QUAD ? 16 : kOffThreads / 64 * 16;
-    hipLaunchKernelGGL((rollout_offpolicy_kernel<T, ENV, QUAD, KIND>), dim3((a.n + per_wg - 1) / per_wg), dim3(kOffThreads), lds_bytes, s, a);
+    hipLaunchKernelGGL((rollout_offpolicy_kernel<T, ENV, QUAD, KIND, STACK>), dim3((a.n + per_wg - 1) / per_wg), dim3(kOffThreads), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
-template <int T, int ENV, int KIND>
+template <int T, int ENV, int KIND, int STACK = 0>
 static int launch_off_t(const OffPolicyArgs& a, hipStream_t s) {
     bool quad = a.n <= 4096;   // at most one tile per compute unit: split it over the workgroup's waves (csrc/rollout.hip: tiling)
     if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
-    return quad ? launch_off_q<T, ENV, true, KIND>(a, s) : launch_off_q<T, ENV, false, KIND>(a, s);
+    // ... when the exchange buffers fit behind the image (they do not with the 30-float Stacking10 observation at width 128)
+    if (((size_t)mlp_layout(KIND, off_obs_dim<ENV, STACK>(), 0, T * 32).total + quad_xchg_floats<T>()) * sizeof(float) > 160 * 1024) quad = false;
+    return quad ? launch_off_q<T, ENV, true, KIND, STACK>(a, s) : launch_off_q<T, ENV, false, KIND, STACK>(a, s);
 }
 
 int launch_rollout_offpolicy(int md, const OffPolicyArgs& a, hipStream_t s) {
-    if (int rc = mlp_check(a.kind, a.env == 0 ? 3 : 4, 0, md)) return rc;
+    const int S = a.env == 2 ? a.wp.num_stack : 0;
+    if (int rc = mlp_check(a.kind, a.env == 0 ? 3 : (a.env == 1 ? 4 : 3 * S), 0, md)) return rc;
     if (a.kind == MLP_SAC_ACTOR) {
         if (md == 128 && a.env == 0) return launch_off_t<4, 0, MLP_SAC_ACTOR>(a, s);
         if (md == 128 && a.env == 1) return launch_off_t<4, 1, MLP_SAC_ACTOR>(a, s);
         if (md == 64 && a.env == 0) return launch_off_t<2, 0, MLP_SAC_ACTOR>(a, s);
         if (md == 64 && a.env == 1) return launch_off_t<2, 1, MLP_SAC_ACTOR>(a, s);
     } else if (a.kind == MLP_CRITIC) {
+        if (md == 256) return launch_rollout16_offpolicy(a, s);
         if (md == 128 && a.env == 0) return launch_off_t<4, 0, MLP_CRITIC>(a, s);
         if (md == 128 && a.env == 1) return launch_off_t<4, 1, MLP_CRITIC>(a, s);
         if (md == 64 && a.env == 0) return launch_off_t<2, 0, MLP_CRITIC>(a, s);
         if (md == 64 && a.env == 1) return launch_off_t<2, 1, MLP_CRITIC>(a, s);
+#define PIME_OS(TT, SS) \
+        if (md == TT * 32 && a.env == 2 && S == SS) return launch_off_t<TT, 2, MLP_CRITIC, SS>(a, s);
+        PIME_OS(4, 1) PIME_OS(4, 4) PIME_OS(4, 10) PIME_OS(2, 1) PIME_OS(2, 4) PIME_OS(2, 10)
+#undef PIME_OS
     }
     set_error("no fused off-policy rollout instantiation for env %d width %d", a.env, md);
     return PIME_ERR_ARG;

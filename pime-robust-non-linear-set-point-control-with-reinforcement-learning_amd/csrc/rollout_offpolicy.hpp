@@ -1,10 +1,10 @@
-// Launch arguments of the fused off-policy (TD3) exploration kernel, shared by rollout_offpolicy.hip and abi.hip.
+// Launch arguments of the fused off-policy (TD3 / SAC) exploration kernels, shared by rollout_offpolicy.hip, mlp16.hip and abi.hip.
 #pragma once
 #include "env_state.hpp"
 
 namespace pime {
 struct OffPolicyArgs {
-    int env;                 // 0: pH; 1: water tank, Integrator observation
+    int env;                 // 0: pH; 1: water tank, Integrator observation; 2: water tank, Stacking observation (wp.num_stack frames)
     int n;                   // lanes
     uint32_t env_offset;
     PhParams p;

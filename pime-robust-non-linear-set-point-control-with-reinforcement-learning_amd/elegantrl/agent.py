@@ -691,7 +691,9 @@ class AgentPPO(AgentBase):
 # ================================================================================================= off-policy
 class AgentOffPolicy(AgentBase):
     """The host path AgentTD3 and AgentSAC share: exploration of a vectorised env into a `VecReplayBuffer` (one fused launch per
-    call, or lock-step by lock-step), and `update_net` on a fused optimizer step (ops.FusedTD3 / ops.FusedSAC): the tables of a
+    call where the library serves the env and the actor -- `env.offpolicy_rollout_supported`: the TD3 Actor at width 64 / 128 / 256
+    on pH, the Integrator tank and Stacking1 / 4 / 10, ActorSAC at width 64 / 128 on pH and the Integrator tank -- or lock-step by
+    lock-step), and `update_net` on a fused optimizer step (ops.FusedTD3 / ops.FusedSAC): the tables of a
     whole update drawn at once, the update captured as ONE HIP graph from the second call on, one host read at the end.
 
     An agent names its fused step (`_fused_name`: the backend's factory and, with a leading underscore, the cache attribute) and
@@ -895,7 +897,10 @@ class AgentTD3(AgentOffPolicy):
     four hand-written launches (`pime_td3_step`, csrc/td3_fused.hip: critic gradients, slab reduction + Adam + delayed soft
     update, actor gradients through the target critic, the same for the actor), a whole update_net one HIP graph
     (AgentOffPolicy); shapes the kernels do not serve (state_dim > 31, widths other than 64 / 128 / 256) and CPU tensors run
-    the same arithmetic as PyTorch modules (`_one_update`)."""
+    the same arithmetic as PyTorch modules (`_one_update`).  Exploration of a vectorised env is ONE launch per call
+    (`pime_rollout_offpolicy`) at width 64 / 128 / 256 on pH, the Integrator tank and the Stacking1 / 4 / 10 tank; an evaluation
+    episode is ONE launch (`fused_eval_policy` -> `pime_rollout_eval`) at width 64 / 128 / 256 on pH and the Integrator tank and
+    at width 256 on Stacking1 / 4 / 10; elsewhere all lanes step in lock-step, one policy forward per step."""
     _fused_name = "fused_td3"
 
     def __init__(self, backend=None, device=None):
@@ -936,6 +941,17 @@ class AgentTD3(AgentOffPolicy):
 
     def _rollout_sigma(self):
         return self.explore_noise
+
+    def fused_eval_policy(self, env):
+        """(packed actor, priorK) if the fused evaluation kernel can run a_env = tanh(net(s)) + s @ priorK on `env` as one launch
+        per episode -- what the evaluator's module path computes (`self.act`, or AgentResidualTD3.eval_policy) -- else None -> the
+        evaluator steps the env launch by launch.  priorK: zeros for plain TD3, the prior gain for the residual agent."""
+        if not hasattr(env, "eval_supported"):
+            return None
+        pk = self._packed_actor()
+        if pk is None or not env.eval_supported(pk):
+            return None
+        return pk.repack(), self._rollout_priorK()
 
     def _explore_actions(self, obs):
         a = self.act(obs)

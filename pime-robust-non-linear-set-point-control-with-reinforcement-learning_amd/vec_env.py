@@ -98,6 +98,11 @@ class CallbackDraws:
 
 
 # ------------------------------------------------------------------------------------------------ base class
+# image kinds the fused evaluation kernels take as a policy ("critic": the TD3 Actor, whose image has CriticAdv's shape and ReLUs)
+_EVAL_KINDS = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR, "sac_actor": native.MLP_SAC_ACTOR,
+               "critic": native.MLP_CRITIC}
+
+
 class VecControlEnv:
     """Common host logic of the two env families.  Tensors returned by reset/step live on `device`."""
     kind = None
@@ -361,7 +366,8 @@ class VecControlEnv:
         # whole episodes with in-kernel auto-reset: every lane is back at step 0 of a new episode
 
     def offpolicy_rollout_supported(self, packed_actor):
-        """Does the fused off-policy exploration kernel serve this env with this packed deterministic actor?"""
+        """Does the fused off-policy exploration kernel serve this env with this packed actor?  (The TD3 Actor: widths 64 / 128 /
+        256 on pH, the Integrator tank and Stacking1 / 4 / 10; ActorSAC: widths 64 / 128 on pH and the Integrator tank.)"""
         if self.cfg.state_mode != native.STATE_MIXED or self.draws.injects or packed_actor.D != self.obs_dim:
             return False
         if packed_actor.kind == "sac_actor":   # ActorSAC: the re-parameterised sample instead of mean + clipped noise
@@ -397,16 +403,15 @@ class VecControlEnv:
     def eval_supported(self, packed_actor=None, trace=False, schedule=False):
         """Does the fused evaluation kernel serve this env (with this packed actor, or the prior controller alone)?
         (pime_rollout_eval_supported: 1 = everything, 2 = returns and trace but no set-point schedule -- a Stacking observation
-        at width 256; float64 or mixed state, in-kernel draws).  `schedule`: the caller wants a set-point schedule."""
+        at width 256; float64 or mixed state, in-kernel draws).  A packed TD3 Actor (kind "critic") evaluates as tanh(net(s)).  `schedule`: the caller wants a set-point schedule."""
         if self.draws.injects:
             return False
         if packed_actor is None:
             level = self._lib.pime_rollout_eval_supported(self._h, -1, 0)
         else:
-            if packed_actor.kind not in ("modular_actor", "plain_actor", "sac_actor") or packed_actor.D != self.obs_dim:
+            if packed_actor.kind not in _EVAL_KINDS or packed_actor.D != self.obs_dim:
                 return False
-            kind = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR,
-                    "sac_actor": native.MLP_SAC_ACTOR}[packed_actor.kind]
+            kind = _EVAL_KINDS[packed_actor.kind]
             level = self._lib.pime_rollout_eval_supported(self._h, kind, int(packed_actor.md))
         return level == 1 or (level == 2 and not schedule)
 
@@ -424,8 +429,7 @@ class VecControlEnv:
         if packed_actor is None:
             kind, md, img = -1, 0, None
         else:
-            kind = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR,
-                    "sac_actor": native.MLP_SAC_ACTOR}[packed_actor.kind]
+            kind = _EVAL_KINDS[packed_actor.kind]
             md, img = int(packed_actor.md), packed_actor.packed
         native.check(self._lib.pime_rollout_eval(self._h, kind, md, native.ptr(img), native.ptr(k), int(n_steps), int(seg_len),
                                                  native.ptr(sp) if sp.size else None, int(sp.size), native.ptr(ret),
