@@ -394,7 +394,8 @@ int pime_rollout_h(pime_env* env, int32_t kind, int32_t md, const float* packed_
  * pime_rollout_eval_supported: 0 = not served; 1 = served (widths 64 / 128 in either state mode; width 256 -- the streamed rollout
  * kernel's evaluation mode, csrc/mlp16.hip -- in PIME_STATE_MIXED on the pH / Integrator observation, trace and schedule included);
  * 2 = returns and trace, but no set-point schedule (a Stacking1 / 4 / 10 observation at width 256 under PIME_MLP_PLAIN_ACTOR or
- * PIME_MLP_CRITIC: seg_len must be 0).  Stacking observations at widths 64 / 128 are not served. */
+ * PIME_MLP_CRITIC: seg_len must be 0).  Stacking observations at widths 64 / 128 are not served; PIME_MLP_SAC_ACTOR is not
+ * served at width 256 (it has no image there). */
 int pime_rollout_eval_supported(const pime_env* env, int32_t kind, int32_t md);
 int pime_rollout_eval(pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
                       int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret, double* trace,

@@ -810,7 +810,8 @@ int pime_rollout_eval_supported(const pime_env* e, int32_t kind, int32_t md) {
     if (kind == -1) return 1;                                            // the prior controller alone
     // (PIME_MLP_CRITIC: the TD3 Actor, a_env = tanh(net(s)) + s . priorK)
     if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR && kind != PIME_MLP_CRITIC) return 0;
-    if (md == 256) return e->cfg.state_mode == PIME_STATE_MIXED ? 1 : 0;   // the streamed kernel's evaluation mode (float32 state)
+    if (md == 256)   // the streamed kernel's evaluation mode (float32 state); ActorSAC has no width-256 image and no instantiation there
+        return e->cfg.state_mode == PIME_STATE_MIXED && kind != PIME_MLP_SAC_ACTOR ? 1 : 0;
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
 
