@@ -12,7 +12,9 @@ row cursor -> ONE captured graph per optimizer step, the path bench.py's timed r
 Tolerance: 6-7 Adam steps at lr 1e-4.  Adam normalises the gradient, so a parameter whose gradient is at rounding-noise level
 can move by up to lr per step in EITHER direction: weights agree to 3e-5 abs (most to 1e-6) on >= 99 % of every tensor's
 elements, and no element is further off than one sign-flipped step (2 lr = 2e-4, + 3e-5); losses to 1e-3 rel.  The gradients
-themselves are pinned to the reference's first-step .grad tensors in test_multi_workgroup_update_against_reference_gradients."""
+themselves are pinned to the reference's first-step .grad tensors in test_multi_workgroup_update_against_reference_gradients.
+The tight check of the update as a chain of steps -- every step against a float64 replay of its own gradient, every launch form of
+update_net bit-equal to a checked step-by-step loop -- is tests/test_gpu_ppo_chain.py."""
 import numpy as np
 import pytest
 import torch
