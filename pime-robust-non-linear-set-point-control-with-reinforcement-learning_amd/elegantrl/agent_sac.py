@@ -20,7 +20,7 @@ Exploration on a vectorised env is ONE launch per call where `pime_rollout_offpo
 water-tank Integrator observation, width 64 / 128), evaluation one launch per episode (`fused_eval_policy`); otherwise all lanes
 step in lock-step, one policy forward per step.
 
-The exploration loop, the packed-actor cache, the table and capture-or-replay stages of the fused update are agent.py's
+The exploration loop, the packed-actor cache, the table and capture-or-replay stages of the fused update are agent_offpolicy.py's
 AgentOffPolicy, shared with AgentTD3; this file holds what is SAC's own."""
 import os
 
@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import logger
-from .agent import AgentOffPolicy
+from .agent_offpolicy import AgentOffPolicy
 from .net import ActorSAC, CriticTwin
 from .replay import VecReplayBuffer
 

@@ -176,6 +176,11 @@ class FusedPPOGrad:
             self.nets.append(net)
         self._structs = None
         self._image_map = None
+        # host state of AgentPPO's update on this object (elegantrl/ppo_update.py): the FusedPPOUpdate of the current (buf_len,
+        # batch_size), and what its probes found -- None: not asked yet
+        self.static = None
+        self.adam_fusable = None   # does pime_ppo_minibatch_step serve these nets (Adam inside the gradient call)?
+        self.dp_union_ok = None    # does the library defer the critic scale for these nets (data parallel)?
         self.repack()
 
     def image_map(self):
@@ -410,6 +415,8 @@ class _FusedOffPolicy:
             raise native.PimeError(f"fused {self.name} step unsupported for state_dim {self.D} width {self.md}: {native.last_error()}")
         self.max_batch = int(max_batch)
         self.lr, self.betas, self.eps = float(lr), betas, float(eps)
+        self.row = 0         # table row of the next step (host side: a launch argument)
+        self.tables = None   # AgentOffPolicy's index / noise tables of an update and the graph captured over them
 
     def _rehome(self, module, names, offs, n):
         """The module's parameters moved into ONE flat float32 tensor of n floats: every nn.Parameter becomes a view at its offset."""
@@ -445,7 +452,6 @@ class _FusedOffPolicy:
         self.ensure_batch(self.max_batch)
         self.loss = torch.zeros(n_loss, **f32)     # first half: sums of the objectives over the update, second half: the last step's
         self.epoch = torch.zeros(1, dtype=torch.int64, device=self.device)   # added to the noise epoch: bumped once per update
-        self.row = 0                                                          # table row of the next step (host side: a launch argument)
         self._actor, self._critic = self._net("act", getattr(self, "act_t_flat", None)), self._net("cri", self.cri_t_flat)
 
     def _net(self, which, target):

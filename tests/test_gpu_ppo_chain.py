@@ -15,7 +15,8 @@ in every launch form -- held bit for bit to a step-by-step loop whose every step
      one agent per kernel family: a twin agent runs the pre-pass through the same methods (each held to float64) and the manual
      loop of a. with recorder and check_chain; the agent under test must end every update with parameters, moments, counter and
      packed images equal to the twin's (loss sums: see below), in each launch form (index table: eager / probe / capture / per-step graph,
-     then the whole-update graph; index hook: two graphs; launch timer: separate Adam; no graphs; no whole-update graph).
+     then the whole-update graph; index hook: two graphs; launch timer: separate Adam; no graphs; no whole-update graph), and
+     when the third update reads a second buffer with the same contents (other data pointers: new graphs, the same end state).
   d. PIME_PPO_CHAIN_REPORT=<path> writes the largest used share of every bound as JSON (a record -- profiles/ppo_chain_gpu.txt --,
      not a threshold).
 
@@ -503,6 +504,59 @@ def test_update_net_equals_the_chain(tag, form):
         (want_a, want_c), (atol_a, atol_c) = want.obj
         assert abs(obj[0] - want_a) <= atol_a and abs(obj[1] - want_c) <= atol_c, f"{what}: (obj_a, obj_c) {obj} against {want.obj}"
     _BIT_EQUAL[f"{tag} update_net[{form}] == chain, 3 updates"] = True
+
+
+def _copy_of(buf):
+    """A second TrajectoryBuffer with `buf`'s contents: the same update at other data pointers."""
+    from pime_amd.elegantrl.replay import TrajectoryBuffer
+    out = TrajectoryBuffer(buf.horizon, buf.num_envs, buf.state_dim, buf.action_dim, DEV)
+    for name in ("state", "reward", "mask", "action", "noise", "done"):
+        getattr(out, name).copy_(getattr(buf, name))
+    out.length = buf.length
+    return out
+
+
+@pytest.mark.parametrize("tag", ["ppo-64-D4", "modular-256-D4"])
+def test_graphs_are_dropped_when_their_key_changes(tag):
+    """Updates 0 and 1 leave the per-step graph and the whole-update graph; update 2 reads a second buffer with the same contents.
+    The captured graphs hold the first buffer's data pointers, so neither may be replayed: a new per-step graph, no (or a new)
+    whole-update graph, and -- with the first buffer's states and actions set to NaN meanwhile -- the end state of the twin's chain
+    all the same."""
+    cfg = AGENTS[tag]
+    buf, table, updates = _twin(cfg)
+    ag, s, _ = _make_agent(cfg)
+    counter = [0]
+    _configure(ag, "index_table", table, counter)
+    for u in range(2):
+        counter[0] = u
+        ag.update_net(buf, T_ * N_, BATCH, 1)
+    torch.cuda.synchronize()
+    st = ag._packed["fused"].static
+    old_full, old_update = st.graph_full, st.graph_update
+    assert old_full is not None and old_update is not None, f"{tag}: graphs after two updates"
+    other = _copy_of(buf)
+    assert other.state.data_ptr() != buf.state.data_ptr() and other.action.data_ptr() != buf.action.data_ptr()
+    counter[0] = 2
+    # NaN where the old graphs read their states and actions: a replay of either would show in the end state (`buf` is the twin's
+    # cached buffer, shared with the other tests: restored below)
+    kept = buf.state.clone(), buf.action.clone()
+    try:
+        buf.state.fill_(float("nan")); buf.action.fill_(float("nan"))
+        obj = ag.update_net(other, T_ * N_, BATCH, 1)
+        torch.cuda.synchronize()
+    finally:
+        buf.state.copy_(kept[0]); buf.action.copy_(kept[1])
+    st = ag._packed["fused"].static
+    assert st.graph_full is not None and st.graph_full is not old_full, f"{tag}: the per-step graph of the first buffer survived"
+    assert st.graph_update is None or st.graph_update is not old_update, f"{tag}: the whole-update graph of the first buffer survived"
+    got, want, what = _end_state(ag), updates[2], f"{tag} update 2 on a second buffer"
+    for key in ("flat_param", "exp_avg", "exp_avg_sq", "step_count"):
+        assert torch.equal(got[key], want.end[key]), f"{what}: {key} differs from the step-by-step chain's"
+    for (gf, gb), (wf, wb) in zip(got["images"], want.end["images"]):
+        assert torch.equal(gf, wf) and torch.equal(gb, wb), f"{what}: packed images"
+    torch.testing.assert_close(got["loss_sums"], want.end["loss_sums"], rtol=1e-5, atol=0)
+    (want_a, want_c), (atol_a, atol_c) = want.obj
+    assert abs(obj[0] - want_a) <= atol_a and abs(obj[1] - want_c) <= atol_c, f"{what}: (obj_a, obj_c) {obj} against {want.obj}"
 
 
 def test_update_net_on_the_split_pipeline():
