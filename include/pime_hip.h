@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 23
+#define PIME_ABI_VERSION 24
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -400,6 +400,40 @@ int pime_rollout_eval_supported(const pime_env* env, int32_t kind, int32_t md);
 int pime_rollout_eval(pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
                       int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret, double* trace,
                       pime_stream stream);
+
+/* -- fused step-response metrics ----------------------------------------------------------------------------------
+ * pime_rollout_eval that also reduces the step response WHILE IT RUNS: per lane and set-point segment the control indices one
+ * reads off a response, accumulated in registers and written once per segment, so a plant grid needs no float64 trace
+ * (48 bytes per lane and step, reduced on the host).  Served exactly where pime_rollout_eval_supported answers 1; where it
+ * answers 2 (Stacking at width 256) seg_len must be 0.  kind / md / packed_actor / priorK / n_steps / seg_len / setpoints / ret /
+ * trace are pime_rollout_eval's, and ret and trace hold exactly what that call leaves; both may be NULL.
+ *   A SEGMENT is the seg_len steps between two set-point boundaries; seg_len == 0: the whole launch is one segment on each
+ *   lane's own set-point; a last segment cut short by n_steps is reported over the steps it had.  Per lane and segment with
+ *   steps k = 0 .. L-1, everything in double, summed in ascending k:
+ *     y_k      the controlled output AFTER step k, widened from the state's precision (pH: the titration-table value at the new
+ *              x -- what the trace's next row holds in column 0; water tank: h2 after the step)
+ *     r        the segment's set-point as the lane state holds it;  e_k = r - y_k
+ *     y_start  the output before the segment's first step;  a_k  the env action as the trace records it
+ *   metrics      [dev] float64[n_segments, PIME_METRIC_ROWS, N], n_segments = ceil(n_steps / seg_len) (1 when seg_len == 0); rows:
+ *     PIME_METRIC_IAE         sum |e_k|
+ *     PIME_METRIC_ISE         sum e_k^2
+ *     PIME_METRIC_ITAE        sum (k + 1) |e_k|
+ *     PIME_METRIC_OVERSHOOT   max(0, max_k d (y_k - r)),  d = +1 if r >= y_start else -1
+ *     PIME_METRIC_SETTLING    1 + the largest k with |e_k| > band; 0 if there is none; L = not inside the band at the last step
+ *     PIME_METRIC_SSE         steady-state error: mean of e_k over the last min(tail, L) steps (summed ascending, divided once)
+ *     PIME_METRIC_RETURN      sum of the float32 rewards widened, as ret accumulates them
+ *     PIME_METRIC_ACTION_VAR  sum over k >= 1 of |a_k - a_{k-1}| inside the segment (no term across a boundary)
+ *   band         settling band, finite and >= 0;   tail: steady-state window in steps, >= 1
+ * PIME_ERR_ARG with a message naming the argument: NULL metrics, negative / NaN / infinite band, tail < 1, and
+ * pime_rollout_eval's own checks.  pime_rollout_eval_metrics_rows() == PIME_METRIC_ROWS. */
+enum pime_metric {
+    PIME_METRIC_IAE = 0, PIME_METRIC_ISE = 1, PIME_METRIC_ITAE = 2, PIME_METRIC_OVERSHOOT = 3, PIME_METRIC_SETTLING = 4,
+    PIME_METRIC_SSE = 5, PIME_METRIC_RETURN = 6, PIME_METRIC_ACTION_VAR = 7, PIME_METRIC_ROWS = 8
+};
+int pime_rollout_eval_metrics_rows(void);
+int pime_rollout_eval_metrics(pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                              int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
+                              double band, int32_t tail, double* ret, double* trace, double* metrics, pime_stream stream);
 
 /* -- fused off-policy exploration -----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with

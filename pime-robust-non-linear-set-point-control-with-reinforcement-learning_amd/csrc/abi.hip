@@ -256,7 +256,7 @@ int h2d_from_double(const FieldRef& f, int n, const double* in, hipStream_t s) {
 template <typename S>
 static int rollout_eval_t(pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, int32_t kind, int32_t md, const float* packed_actor,
                           const double* priorK, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
-                          double* ret, double* trace, pime_stream stream) {
+                          double* ret, double* trace, const EvalMetricsArgs& mx, pime_stream stream) {
     EvalArgs<S> a{};
     a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
     a.n = e->cfg.n_envs;
@@ -268,7 +268,7 @@ static int rollout_eval_t(pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt,
     a.n_steps = n_steps; a.seg_len = seg_len;
     if (seg_len > 0)   // (validated by the caller: setpoints != NULL, 1 <= n_setpoints <= kMaxSetpoints)
         for (int j = 0; j < n_setpoints && j < kMaxSetpoints; ++j) a.setpoint[j] = setpoints[j];
-    a.ret = ret; a.trace = trace;
+    a.ret = ret; a.trace = trace; a.mx = mx;
     return launch_rollout_eval<S>(kind, md, a, static_cast<hipStream_t>(stream));
 }
 
@@ -815,22 +815,23 @@ int pime_rollout_eval_supported(const pime_env* e, int32_t kind, int32_t md) {
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
 
-int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
-                      int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret, double* trace,
-                      pime_stream stream) {
+// pime_rollout_eval and pime_rollout_eval_metrics (mx.out != NULL): one body, `fn` names the entry point in the messages
+static int rollout_eval_common(const char* fn, pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                               int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret,
+                               double* trace, const EvalMetricsArgs& mx, pime_stream stream) {
     PIME_REQUIRE(e != nullptr, "NULL env handle");
-    PIME_REQUIRE(pime_rollout_eval_supported(e, kind, md), "pime_rollout_eval: not served for this handle / actor kind %d width %d "
-                 "(pime_rollout_eval_supported)", kind, md);
-    PIME_REQUIRE(priorK && n_steps >= 1 && (kind == -1 || packed_actor) && (ret || trace), "pime_rollout_eval: bad arguments");
-    PIME_REQUIRE(n_setpoints >= 0 && n_setpoints <= kMaxSetpoints, "pime_rollout_eval: n_setpoints %d (0 .. %d)", n_setpoints, kMaxSetpoints);
+    PIME_REQUIRE(pime_rollout_eval_supported(e, kind, md), "%s: not served for this handle / actor kind %d width %d "
+                 "(pime_rollout_eval_supported)", fn, kind, md);
+    PIME_REQUIRE(priorK && n_steps >= 1 && (kind == -1 || packed_actor) && (ret || trace || mx.out), "%s: bad arguments", fn);
+    PIME_REQUIRE(n_setpoints >= 0 && n_setpoints <= kMaxSetpoints, "%s: n_setpoints %d (0 .. %d)", fn, n_setpoints, kMaxSetpoints);
     PIME_REQUIRE(seg_len >= 0 && (seg_len == 0 || (setpoints && n_setpoints >= 1 && n_setpoints <= kMaxSetpoints &&
                                                    (n_steps + seg_len - 1) / seg_len <= n_setpoints)),
-                 "pime_rollout_eval: the set-point schedule does not cover n_steps (at most %d segments)", kMaxSetpoints);
-    if (!e->was_reset) { set_error("pime_rollout_eval before pime_env_reset"); return PIME_ERR_STATE; }
+                 "%s: the set-point schedule does not cover n_steps (at most %d segments)", fn, kMaxSetpoints);
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
     if (int rc = use_device(e)) return rc;
     if (md == 256 && kind != -1) {   // the streamed 16-tile rollout kernel in evaluation mode (mlp16.hip)
-        PIME_REQUIRE(seg_len == 0 || pime_rollout_eval_supported(e, kind, md) == 1, "pime_rollout_eval: no set-point schedule on a "
-                     "Stacking observation (the protocols are defined on the Integrator observation)");
+        PIME_REQUIRE(seg_len == 0 || pime_rollout_eval_supported(e, kind, md) == 1, "%s: no set-point schedule on a "
+                     "Stacking observation (the protocols are defined on the Integrator observation)", fn);
         RolloutArgs a{};
         a.env = e->cfg.kind == PIME_ENV_PH ? 0 : (e->cfg.num_stack == 0 ? 1 : 2);
         a.n = e->cfg.n_envs;
@@ -840,16 +841,37 @@ int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed
         a.img = packed_actor;
         a.a_std_log = nullptr;                  // not read in evaluation mode (no exploration noise)
         for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
-        a.n_steps = n_steps; a.eval_mode = 1; a.ret = ret; a.trace = trace; a.seg_len = seg_len;
+        a.n_steps = n_steps; a.eval_mode = 1; a.ret = ret; a.trace = trace; a.seg_len = seg_len; a.mx = mx;
         if (seg_len > 0)
             for (int j = 0; j < n_setpoints && j < 16; ++j) a.setpoint[j] = setpoints[j];
         return launch_rollout(kind, md, a, static_cast<hipStream_t>(stream));
     }
     if (e->cfg.state_mode == PIME_STATE_F64)
         return rollout_eval_t<double>(e, e->ph64, e->wt64, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints,
-                                      ret, trace, stream);
+                                      ret, trace, mx, stream);
     return rollout_eval_t<float>(e, e->ph32, e->wt32, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints, ret,
-                                 trace, stream);
+                                 trace, mx, stream);
+}
+
+int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
+                      int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret, double* trace,
+                      pime_stream stream) {
+    return rollout_eval_common("pime_rollout_eval", e, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints, ret,
+                               trace, EvalMetricsArgs{}, stream);
+}
+
+int pime_rollout_eval_metrics_rows(void) { return PIME_METRIC_ROWS; }
+
+int pime_rollout_eval_metrics(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                              int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band,
+                              int32_t tail, double* ret, double* trace, double* metrics, pime_stream stream) {
+    PIME_REQUIRE(metrics != nullptr, "pime_rollout_eval_metrics: metrics is NULL");
+    PIME_REQUIRE(band >= 0.0 && band <= 1.79769313486231570815e308, "pime_rollout_eval_metrics: band %g (finite, >= 0)", band);   // (NaN fails both)
+    PIME_REQUIRE(tail >= 1, "pime_rollout_eval_metrics: tail %d (>= 1)", tail);
+    EvalMetricsArgs mx{};
+    mx.out = metrics; mx.band = band; mx.tail = tail;
+    return rollout_eval_common("pime_rollout_eval_metrics", e, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints,
+                               n_setpoints, ret, trace, mx, stream);
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

@@ -1729,7 +1729,9 @@ __device__ __forceinline__ void frames_store16(const WtPtrs<float>& wst, int N, 
 
 // QUAD (launches of <= 4 096 lanes): the four waves share ONE 16-lane tile, each a quad of every layer's output tiles (layer16q; two
 // tiles of the modular actor's tower layers: layer16rq) -- 256 workgroups instead of 64 for the reference script's 4 096 lanes, a quarter of the MFMA chain per env step.
-template <int T, int KIND, int ENV, int STACK, bool QUAD = false>
+// METRICS (evaluation mode only, pime_rollout_eval_metrics): the per-segment step-response metrics of eval_metrics.hpp, a
+// compile-time variant so that the training instantiations keep their registers and their loop body.
+template <int T, int KIND, int ENV, int STACK, bool QUAD = false, bool METRICS = false>
 __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int D = ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK), Di = ENV == 2 ? 0 : 1, Do = D - Di, H = T / 2;
@@ -1778,6 +1780,8 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
         for (int j = 0; j < D; ++j) obs[j] = a.state[(size_t)D * i + j];
     }
     double ret = 0.0;
+    [[maybe_unused]] SegMetrics M{};
+    [[maybe_unused]] int seg = 0, kseg = 0;   // METRICS: segment and step inside it (wave-uniform)
     for (int t = 0; t < a.n_steps; ++t) {
         PIME_NO_HOIST();
         if (evaluating && a.seg_len > 0 && t % a.seg_len == 0) {   // segment boundary of a step-response protocol (wave-uniform), as
@@ -1791,6 +1795,12 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
 #pragma unroll
                     for (int f = 0; f < STACK; ++f) { obs[3 * f] = W.h1; obs[3 * f + 1] = W.h2; obs[3 * f + 2] = sp; }
                 }
+            }
+        }
+        if constexpr (METRICS) {
+            if (kseg == 0) {   // a segment starts: the output before its first step, the set-point the lane holds
+                if constexpr (ENV == 0) M.begin((double)ph_lookup<float>(a.p, a.st.table, E.C, E.x), (double)E.r, segment_steps(a.n_steps, a.seg_len, seg), a.mx.tail);
+                else M.begin((double)W.h2, (double)W.r, segment_steps(a.n_steps, a.seg_len, seg), a.mx.tail);
             }
         }
         float a_avg;
@@ -1876,6 +1886,14 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
                 q[4 * (size_t)N] = (double)rew; q[5 * (size_t)N] = a_env;
             }
         }
+        if constexpr (METRICS) {
+            if constexpr (ENV == 0) M.step(kseg, (double)nxt[0], a_env, rew, a.mx.band);   // (float state: the observation IS the table value)
+            else M.step(kseg, (double)W.h2, a_env, rew, a.mx.band);
+            if (++kseg == M.len) {
+                if (writer) M.store(a.mx.out, seg, N, i);
+                ++seg; kseg = 0;
+            }
+        }
         const size_t k = (size_t)t * N + i;
         if (writer && !evaluating) {
             a.action[k] = a_pre;
@@ -1897,15 +1915,15 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
     }
 }
 
-template <int KIND, int ENV, int STACK, bool QUAD>
+template <int KIND, int ENV, int STACK, bool QUAD, bool METRICS>
 static int launch_rollout16_q(const RolloutArgs& a, hipStream_t s) {
     constexpr int T = 16, D = ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK);
     const size_t lds_bytes = sizeof(float) * ((size_t)(KIND == MLP_MODULAR_ACTOR ? lds16m<T>(D, 1, false).total : lds16<T>(D, false).total) +
                                               (QUAD ? T * 64 * 4 : 0));
     static LdsLimit lds_limit;  // per instantiation
-    PIME_RAISE_LDS(lds_limit, (rollout16_kernel<T, KIND, ENV, STACK, QUAD>), 160 * 1024);
+    PIME_RAISE_LDS(lds_limit, (rollout16_kernel<T, KIND, ENV, STACK, QUAD, METRICS>), 160 * 1024);
     const int per_wg = QUAD ? 16 : k16Group;
-    hipLaunchKernelGGL((rollout16_kernel<T, KIND, ENV, STACK, QUAD>), dim3((a.n + per_wg - 1) / per_wg), dim3(k16Threads), lds_bytes, s, a);
+    hipLaunchKernelGGL((rollout16_kernel<T, KIND, ENV, STACK, QUAD, METRICS>), dim3((a.n + per_wg - 1) / per_wg), dim3(k16Threads), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
@@ -1913,14 +1931,33 @@ template <int KIND, int ENV, int STACK>
 static int launch_rollout16_t(const RolloutArgs& a, hipStream_t s) {
     bool quad = a.n <= 4096;   // at most one tile per compute unit: split it over the workgroup's waves (as csrc/rollout.hip: tiling)
     if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
-    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true>(a, s);
-    return launch_rollout16_q<KIND, ENV, STACK, false>(a, s);
+    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, false>(a, s);
+    return launch_rollout16_q<KIND, ENV, STACK, false, false>(a, s);
+}
+// evaluation mode: with a.mx.out the METRICS variant
+template <int KIND, int ENV, int STACK>
+static int launch_rollout16_e(const RolloutArgs& a, hipStream_t s) {
+    if (a.mx.out == nullptr) return launch_rollout16_t<KIND, ENV, STACK>(a, s);
+    bool quad = a.n <= 4096;
+    if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
+    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, true>(a, s);
+    return launch_rollout16_q<KIND, ENV, STACK, false, true>(a, s);
 }
 
 // width 256 (csrc/rollout.hip dispatches here); binary16 rows (PIME_STATE_MIXED16) are not served at this width
 int launch_rollout16(int kind, const RolloutArgs& a, hipStream_t s) {
     PIME_REQUIRE(a.I16 == nullptr, "the width-256 fused rollout serves PIME_STATE_MIXED handles");
-    if (kind == MLP_MODULAR_ACTOR) {
+    PIME_REQUIRE(a.mx.out == nullptr || a.eval_mode, "step-response metrics belong to the evaluation mode");
+    if (a.eval_mode && kind == MLP_MODULAR_ACTOR) {
+        if (a.env == 0) return launch_rollout16_e<MLP_MODULAR_ACTOR, 0, 0>(a, s);
+        if (a.env == 1) return launch_rollout16_e<MLP_MODULAR_ACTOR, 1, 0>(a, s);
+    } else if (a.eval_mode && kind == MLP_PLAIN_ACTOR) {
+        if (a.env == 0) return launch_rollout16_e<MLP_PLAIN_ACTOR, 0, 0>(a, s);
+        if (a.env == 1) return launch_rollout16_e<MLP_PLAIN_ACTOR, 1, 0>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 1) return launch_rollout16_e<MLP_PLAIN_ACTOR, 2, 1>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 4) return launch_rollout16_e<MLP_PLAIN_ACTOR, 2, 4>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 10) return launch_rollout16_e<MLP_PLAIN_ACTOR, 2, 10>(a, s);
+    } else if (kind == MLP_MODULAR_ACTOR) {
         if (a.env == 0) return launch_rollout16_t<MLP_MODULAR_ACTOR, 0, 0>(a, s);
         if (a.env == 1) return launch_rollout16_t<MLP_MODULAR_ACTOR, 1, 0>(a, s);
     } else if (kind == MLP_PLAIN_ACTOR) {
@@ -1930,11 +1967,11 @@ int launch_rollout16(int kind, const RolloutArgs& a, hipStream_t s) {
         if (a.env == 2 && a.wp.num_stack == 4) return launch_rollout16_t<MLP_PLAIN_ACTOR, 2, 4>(a, s);
         if (a.env == 2 && a.wp.num_stack == 10) return launch_rollout16_t<MLP_PLAIN_ACTOR, 2, 10>(a, s);
     } else if (kind == MLP_CRITIC && a.eval_mode) {   // the TD3 Actor (ReLU layers, a_env = tanh(net(s)) + s . K): evaluation only
-        if (a.env == 0) return launch_rollout16_t<MLP_CRITIC, 0, 0>(a, s);
-        if (a.env == 1) return launch_rollout16_t<MLP_CRITIC, 1, 0>(a, s);
-        if (a.env == 2 && a.wp.num_stack == 1) return launch_rollout16_t<MLP_CRITIC, 2, 1>(a, s);
-        if (a.env == 2 && a.wp.num_stack == 4) return launch_rollout16_t<MLP_CRITIC, 2, 4>(a, s);
-        if (a.env == 2 && a.wp.num_stack == 10) return launch_rollout16_t<MLP_CRITIC, 2, 10>(a, s);
+        if (a.env == 0) return launch_rollout16_e<MLP_CRITIC, 0, 0>(a, s);
+        if (a.env == 1) return launch_rollout16_e<MLP_CRITIC, 1, 0>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 1) return launch_rollout16_e<MLP_CRITIC, 2, 1>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 4) return launch_rollout16_e<MLP_CRITIC, 2, 4>(a, s);
+        if (a.env == 2 && a.wp.num_stack == 10) return launch_rollout16_e<MLP_CRITIC, 2, 10>(a, s);
     }
     set_error("no width-256 fused rollout for env %d kind %d", a.env, kind);
     return PIME_ERR_ARG;

@@ -1,6 +1,7 @@
 // Launch arguments of the fused rollout kernel, shared by rollout.hip and abi.hip.
 #pragma once
 #include "env_state.hpp"
+#include "eval_metrics.hpp"
 
 namespace pime {
 struct RolloutArgs {
@@ -32,5 +33,8 @@ struct RolloutArgs {
     int seg_len;
     double setpoint[16];
     double* trace;
+    // ... and its per-segment step-response metrics (eval_metrics.hpp).  mx.out != NULL selects the METRICS instantiations of the
+    // evaluation mode; no other instantiation reads these fields
+    EvalMetricsArgs mx;
 };
 }  // namespace pime

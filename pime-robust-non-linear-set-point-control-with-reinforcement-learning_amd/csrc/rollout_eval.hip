@@ -23,7 +23,10 @@ namespace pime {
 constexpr int kEvalThreads = 256;   // four waves of 16 lanes: one per SIMD (16-lane tiles, rollout_policy.hpp: policy_forward16)
 
 // QUAD (launches of <= 4 096 lanes with a policy): one 16-lane tile per workgroup, split over its four waves (policy_forward16q)
-template <int T, int KIND, int ENV, typename S, bool QUAD>
+// METRICS (pime_rollout_eval_metrics): the per-segment step-response metrics of eval_metrics.hpp, accumulated in registers.  A
+// compile-time variant: as a run-time branch the accumulators cost every launch 14 .. 60 VGPRs (and the prior controller's
+// kernels two of their eight waves per SIMD), so the launches without metrics keep the code they had.
+template <int T, int KIND, int ENV, typename S, bool QUAD, bool METRICS>
 __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int D = ENV == 0 ? 3 : 4;
@@ -53,6 +56,8 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
         obs[0] = (float)W.h1; obs[1] = (float)W.h2; obs[2] = (float)W.r; obs[3] = (float)W.I;
     }
     double ret = 0.0;
+    [[maybe_unused]] SegMetrics M{};
+    [[maybe_unused]] int seg = 0, k = 0;        // METRICS: segment and step inside it (wave-uniform)
     for (int t = 0; t < a.n_steps; ++t) {
         PIME_NO_HOIST();
         if (a.seg_len > 0 && t % a.seg_len == 0) {   // segment boundary of a step-response protocol (wave-uniform)
@@ -63,6 +68,12 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
             const int bump = t > 0 ? 1 : 0;
             if constexpr (ENV == 0) { E.r = (S)sp; E.I = S(0); E.t = 0; E.episode += bump; obs[1] = (float)E.r; obs[2] = 0.f; }
             else { W.r = (S)sp; W.I = S(0); W.t = 0; W.episode += bump; obs[2] = (float)W.r; obs[3] = 0.f; }
+        }
+        if constexpr (METRICS) {
+            if (k == 0) {   // a segment starts: the output before its first step, the set-point the lane holds
+                if constexpr (ENV == 0) M.begin((double)ph_lookup<S>(a.p, a.st.table, E.C, E.x), (double)E.r, segment_steps(a.n_steps, a.seg_len, seg), a.mx.tail);
+                else M.begin((double)W.h2, (double)W.r, segment_steps(a.n_steps, a.seg_len, seg), a.mx.tail);
+            }
         }
         double a_env = 0.0;                                                        // agent_residual.py:61 without the noise
 #pragma unroll
@@ -94,6 +105,19 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
             q[0] = tr0; q[(size_t)N] = tr1; q[2 * (size_t)N] = tr2; q[3 * (size_t)N] = tr3; q[4 * (size_t)N] = (double)rew;
             q[5 * (size_t)N] = tr5;
         }
+        if constexpr (METRICS) {
+            if constexpr (ENV == 0) {   // y after the step in the state's precision (float state: the observation is that value)
+                double y;
+                if constexpr (sizeof(S) == sizeof(float)) y = (double)obs[0];
+                else y = (double)ph_lookup<S>(a.p, a.st.table, E.C, E.x);
+                M.step(k, y, a_env, rew, a.mx.band);
+            }
+            else M.step(k, (double)W.h2, a_env, rew, a.mx.band);
+            if (++k == M.len) {
+                if (writer) M.store(a.mx.out, seg, N, i);
+                ++seg; k = 0;
+            }
+        }
     }
     if (writer) {
         if constexpr (ENV == 0) ph_lane_store<S>(a.p, a.st, i, E);
@@ -104,18 +128,23 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
 
 int mlp_check(int kind, int D, int Di, int md);
 
-template <int T, int KIND, int ENV, typename S, bool QUAD>
-static int launch_eval_q(const EvalArgs<S>& a, hipStream_t s) {
+template <int T, int KIND, int ENV, typename S, bool QUAD, bool METRICS>
+static int launch_eval_m(const EvalArgs<S>& a, hipStream_t s) {
     size_t lds_bytes = 0;
     if constexpr (KIND >= 0) {
         lds_bytes = ((size_t)mlp_layout(KIND, ENV == 0 ? 3 : 4, 1, T * 32).total + (QUAD ? quad_xchg_floats<T>() : 0)) * sizeof(float);
         static LdsLimit lds_limit;  // per instantiation
-        PIME_RAISE_LDS(lds_limit, (rollout_eval_kernel<T, KIND, ENV, S, QUAD>), 160 * 1024);
+        PIME_RAISE_LDS(lds_limit, (rollout_eval_kernel<T, KIND, ENV, S, QUAD, METRICS>), 160 * 1024);
     }
     const int per_wg = QUAD ? 16 : kEvalThreads / 64 * 16;
-    hipLaunchKernelGGL((rollout_eval_kernel<T, KIND, ENV, S, QUAD>), dim3((a.n + per_wg - 1) / per_wg), dim3(kEvalThreads), lds_bytes, s, a);
+    hipLaunchKernelGGL((rollout_eval_kernel<T, KIND, ENV, S, QUAD, METRICS>), dim3((a.n + per_wg - 1) / per_wg), dim3(kEvalThreads), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
+}
+template <int T, int KIND, int ENV, typename S, bool QUAD>
+static int launch_eval_q(const EvalArgs<S>& a, hipStream_t s) {
+    if (a.mx.out != nullptr) return launch_eval_m<T, KIND, ENV, S, QUAD, true>(a, s);
+    return launch_eval_m<T, KIND, ENV, S, QUAD, false>(a, s);
 }
 template <int T, int KIND, int ENV, typename S>
 static int launch_eval_t(const EvalArgs<S>& a, hipStream_t s) {

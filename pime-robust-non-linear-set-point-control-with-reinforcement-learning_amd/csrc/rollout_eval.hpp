@@ -1,6 +1,7 @@
 // Launch arguments of the fused evaluation kernel, shared by rollout_eval.hip and abi.hip.
 #pragma once
 #include "env_state.hpp"
+#include "eval_metrics.hpp"
 
 namespace pime {
 constexpr int kMaxSetpoints = 16;
@@ -20,6 +21,7 @@ struct EvalArgs {
     double setpoint[kMaxSetpoints];
     double* ret;             // [N] += sum of the launch's rewards, or NULL
     double* trace;           // [n_steps][6][N] or NULL
+    EvalMetricsArgs mx;      // per-segment step-response metrics (eval_metrics.hpp); mx.out NULL: none
 };
 template <typename S>
 int launch_rollout_eval(int kind, int md, const EvalArgs<S>& a, hipStream_t s);

@@ -13,9 +13,18 @@ replaces (protocols only, not the matplotlib plotting around them):
 With `policy=None` (prior controller) or `agent=<a residual PPO agent>` the whole protocol is ONE launch of the fused evaluation
 kernel (csrc/rollout_eval.hip, `pime_rollout_eval` with a set-point schedule: no per-step launches, no per-step device-to-host
 reads; round 2 read four state fields back per step); an arbitrary `policy` callable keeps the step-per-launch loop.
+
+`step_response_metrics` / `robust_grid` return the QUALITY of the responses instead of the responses: per plant and set-point
+segment the eight control indices of `METRIC_NAMES` (error integrals, overshoot, settling step, steady-state error, return, action
+variation; definitions in include/pime_hip.h), reduced on the device while the protocol runs (`pime_rollout_eval_metrics`: one
+launch, no trace) -- a dense robustness map costs 64 bytes per plant and segment instead of 48 bytes per plant and STEP.
 """
+from collections import OrderedDict
+
 import numpy as np
 import torch
+
+from .native import ENV_PH, METRIC_NAMES
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -106,3 +115,103 @@ def wt_step_response(env, policy=None, setpoints=WT_SETPOINTS, steps=None, plant
             obs = nxt.clone()
         h1, h2 = env.get_field("h1"), env.get_field("h2")
     return {k: np.stack(v) for k, v in out.items()}
+
+
+def metrics_from_records(y_after, r, action, reward, y_start, seg_len=0, band=0.05, tail=10):
+    """The eight rows of `pime_rollout_eval_metrics` from step-by-step records, in numpy -- for the paths the fused kernel does not
+    serve (an arbitrary `policy` callable, draw injection).  y_after [T, N]: the controlled output AFTER each step (pH: y, tank:
+    h2); r [T, N] or [T]: the set-point of each step; action, reward [T, N]; y_start [n_segments, N]: the output before each
+    segment's first step; seg_len 0: one segment.  Returns dict name -> float64 [n_segments, N].  Sums run in ascending step order
+    (np.cumsum adds sequentially), rewards are rounded to float32 before they are widened, as the kernel's are."""
+    y = np.asarray(y_after, dtype=np.float64)
+    T, N = y.shape
+    r = np.broadcast_to(np.asarray(r, dtype=np.float64).reshape(T, -1), (T, N))
+    a = np.asarray(action, dtype=np.float64).reshape(T, N)
+    rew = np.asarray(reward).reshape(T, N).astype(np.float32).astype(np.float64)
+    y_start = np.asarray(y_start, dtype=np.float64).reshape(-1, N)
+    L0 = int(seg_len) if seg_len > 0 else T
+    n_seg = -(-T // L0)
+    assert y_start.shape[0] == n_seg and band >= 0 and tail >= 1
+    out = {name: np.zeros((n_seg, N)) for name in METRIC_NAMES}
+    last = lambda terms: np.cumsum(terms, axis=0)[-1]
+    for s in range(n_seg):
+        sl = slice(s * L0, min((s + 1) * L0, T))
+        ys, rs, as_ = y[sl], r[sl][0], a[sl]
+        L = ys.shape[0]
+        e = rs - ys
+        k1 = np.arange(1, L + 1, dtype=np.float64)[:, None]
+        out["iae"][s] = last(np.abs(e))
+        out["ise"][s] = last(e * e)
+        out["itae"][s] = last(k1 * np.abs(e))
+        d = np.where(rs >= y_start[s], 1.0, -1.0)
+        out["overshoot"][s] = np.maximum(0.0, (d * (ys - rs)).max(axis=0))
+        outside = np.abs(e) > band
+        out["settling_step"][s] = np.where(outside.any(axis=0), L - np.argmax(outside[::-1], axis=0), 0)
+        w = min(int(tail), L)
+        out["steady_state_error"][s] = last(e[L - w:]) / w
+        out["return"][s] = last(rew[sl])
+        out["action_variation"][s] = last(np.abs(np.diff(as_, axis=0))) if L > 1 else 0.0
+    return out
+
+
+def step_response_metrics(env, agent=None, policy=None, setpoints=None, steps=None, plants=None, band=None, tail=10):
+    """The step-response protocol of `env` (pH: `ph_step_response`, r = 10,6,3,8,5 x 50 steps; Integrator tank:
+    `wt_step_response`, r = 3,6,9,4,2 x max_step) reduced to its control indices: dict of metric name (`METRIC_NAMES`) ->
+    float64 [len(setpoints), N].  band: the settling band on |r - y| (default 0.05 for pH -- the reference's sparse-reward
+    threshold -- and 0.05 for the tank); tail: the steady-state window in steps.  With the prior controller (agent and policy None)
+    or an agent the fused evaluation kernel serves this is ONE launch and no trace; otherwise the step-per-launch protocol runs and
+    `metrics_from_records` reduces its records."""
+    is_ph = env.kind == ENV_PH
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    fused = _fused_policy(env, policy, agent)
+    if fused is not None and len(setpoints) <= 16 and (is_ph or env.num_stack == 0):
+        env.set_reset_all(False)
+        if is_ph:
+            env.set_max_step(2 ** 30)
+            if plants is not None:
+                plants = np.asarray(plants, dtype=np.float64)
+                env.set_params(plants[:, 0], plants[:, 1])
+            env.reset()
+            env.set_field("x", np.zeros(env.num_envs))
+        else:
+            env.set_max_step(max(steps, env.max_step))
+            if plants is not None:
+                plants = np.asarray(plants, dtype=np.float64)
+                env.reset_changable_parameters(plants[:, 0], plants[:, 1], plants[:, 2])
+            env.reset()
+            env.set_field("h1", np.zeros(env.num_envs)); env.set_field("h2", np.zeros(env.num_envs))
+        _, m, _ = env.rollout_eval_metrics(fused[0], fused[1], len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band,
+                                           tail=tail)
+        m = m.cpu().numpy()
+        return {name: np.ascontiguousarray(m[:, j]) for j, name in enumerate(METRIC_NAMES)}
+    if is_ph:
+        res = ph_step_response(env, policy=policy, setpoints=setpoints, steps=steps, plants=plants, agent=agent)
+        y_before = res["y"]                                              # y BEFORE each step; the plant state is carried over
+        y_after = np.concatenate([y_before[1:], env.get_field("y")[None]])
+        r, action = res["r"], res["action"]
+    else:
+        res = wt_step_response(env, policy=policy, setpoints=setpoints, steps=steps, plants=plants, agent=agent)
+        y_after = res["obs"][:, :, 1]
+        y_before = np.concatenate([np.zeros((1, env.num_envs)), y_after[:-1]])   # the protocol starts from empty tanks
+        r, action = res["obs"][:, :, 2], res["action"]
+    return metrics_from_records(y_after, r, action, res["reward"], y_before[::steps], seg_len=steps, band=band, tail=tail)
+
+
+def robust_grid(env, axes, agent=None, policy=None, setpoints=None, steps=None, band=None, tail=10):
+    """A dense robustness map: the step-response metrics over the Cartesian product of plant parameters.  axes: ordered mapping
+    of plant parameter -> 1-D values (pH: qww_V, qc_V; tank: a1, a2, Kp -- all of them, in any order); env.num_envs must equal the
+    product of their lengths; lane = the C-order index into the grid.  Returns (dict of metric name -> float64 [n_segments, *axis
+    lengths], axes as an OrderedDict of float64 arrays)."""
+    names = ("qww_V", "qc_V") if env.kind == ENV_PH else ("a1", "a2", "Kp")
+    axes = OrderedDict((k, np.asarray(v, dtype=np.float64).reshape(-1)) for k, v in axes.items())
+    if sorted(axes) != sorted(names):
+        raise ValueError(f"robust_grid: axes {list(axes)} must name exactly {names}")
+    shape = tuple(len(v) for v in axes.values())
+    if int(np.prod(shape)) != env.num_envs:
+        raise ValueError(f"robust_grid: the grid has {int(np.prod(shape))} plants, the env {env.num_envs} lanes")
+    mesh = dict(zip(axes, np.meshgrid(*axes.values(), indexing="ij")))
+    plants = np.stack([mesh[k].reshape(-1) for k in names], axis=1)
+    m = step_response_metrics(env, agent=agent, policy=policy, setpoints=setpoints, steps=steps, plants=plants, band=band, tail=tail)
+    return {k: v.reshape(v.shape[0], *shape) for k, v in m.items()}, axes

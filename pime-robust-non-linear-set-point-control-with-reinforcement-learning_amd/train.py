@@ -129,6 +129,43 @@ def prepare_train(args, env):
     return kargs, tb
 
 
+def robust_test(args, agent, cwd):
+    """--robust_test (reference train.py:198-200 -> utils/robust_test.py:4-46, without its plots): the environment's step-response
+    protocol under the final deterministic policy on the reference's plant set, one env lane per plant -- the tank's three robust
+    plants at max_step 500, the pH plant grid of utils/test.py:1225-1236 -- reduced to the per-segment control indices of
+    protocols.step_response_metrics (one launch where the fused evaluation kernel serves the agent).  Writes
+    <cwd>/robust_metrics.npz: metrics [n_plants, n_segments, 8] in the row order `metric_names`, plants, setpoints, band, tail."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("robust test skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+    policy = None
+    if protocols._fused_policy(env, None, agent) is None:   # e.g. a width the fused kernel has no instantiation for
+        act = getattr(agent, "eval_policy", None) or agent.act
+
+        def policy(obs):
+            with torch.no_grad():
+                return act(obs)
+    m = protocols.step_response_metrics(env, agent=agent, policy=policy, setpoints=setpoints, steps=steps, plants=plants, band=band,
+                                        tail=tail)
+    env.close()
+    metrics = np.stack([m[name] for name in protocols.METRIC_NAMES], axis=-1).transpose(1, 0, 2)   # [plant, segment, row]
+    path = os.path.join(cwd, "robust_metrics.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, metrics=metrics, metric_names=np.asarray(protocols.METRIC_NAMES), plants=plants,
+             setpoints=np.asarray(setpoints, dtype=np.float64), band=band, tail=tail, steps=steps)
+    print(f"robust test: {len(plants)} plants x {len(setpoints)} set-points -> {path}")
+    return path
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     assert args.test_render_times % args.target_step == 0 or args.num_envs > 1, "Must be an integer multiple"
@@ -153,6 +190,8 @@ def main(argv=None):
         with open(os.path.join(kargs.cwd, "args.txt"), "w") as f:
             f.write(str(args))
         print(f"Finish Training and Saved in {kargs.cwd}")
+        if args.robust_test:
+            robust_test(args, agent, kargs.cwd)
     return agent
 
 

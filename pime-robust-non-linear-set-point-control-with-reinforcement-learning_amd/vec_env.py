@@ -441,6 +441,37 @@ class VecControlEnv:
             self._t_lanes += n_steps
         return ret, trace
 
+    def rollout_eval_metrics(self, packed_actor, priorK, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_trace=False,
+                             ret=None):
+        """`rollout_eval` that also reduces the step response on the device (pime_rollout_eval_metrics): returns (ret, metrics,
+        trace) with metrics float64 [n_segments, 8, N] -- per set-point segment and lane the rows native.METRIC_NAMES (IAE, ISE,
+        ITAE, overshoot, settling step for `band`, steady-state error over the last `tail` steps, return, action variation;
+        definitions in include/pime_hip.h).  n_segments = ceil(n_steps / seg_len), 1 without a schedule.  ret and trace (None
+        unless `want_trace`) are what `rollout_eval` returns for the same launch."""
+        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
+        assert k.size == self.obs_dim
+        if ret is None:
+            ret = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
+        n_seg = -(-int(n_steps) // int(seg_len)) if seg_len > 0 else 1
+        metrics = torch.empty((max(n_seg, 1), native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
+        trace = torch.empty((n_steps, 6, self.num_envs), dtype=torch.float64, device=self.device) if want_trace else None
+        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        if packed_actor is None:
+            kind, md, img = -1, 0, None
+        else:
+            kind = _EVAL_KINDS[packed_actor.kind]
+            md, img = int(packed_actor.md), packed_actor.packed
+        native.check(self._lib.pime_rollout_eval_metrics(
+            self._h, kind, md, native.ptr(img), native.ptr(k), int(n_steps), int(seg_len), native.ptr(sp) if sp.size else None,
+            int(sp.size), float(band), int(tail), native.ptr(ret), native.ptr(trace), native.ptr(metrics), self._stream()),
+            "pime_rollout_eval_metrics")
+        self._was_reset = False   # as rollout_eval: the lanes sit somewhere inside an episode
+        if self._t_lanes is None:
+            self._t_all += n_steps
+        else:
+            self._t_lanes += n_steps
+        return ret, metrics, trace
+
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
         out = np.empty(self.num_envs, dtype=np.float64)

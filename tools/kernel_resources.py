@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/kernel_resources.py [out.txt]
+"""usage: tools/kernel_resources.py [out.txt [file.hip ...]]   (no file names: every .hip under csrc/)
 Compiler-reported resources of every kernel in libpime_hip.so (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
 VGPRs, AGPRs, scratch (spill) bytes per lane, static LDS, SGPRs, occupancy in waves per SIMD -- and, from the ISA of the same
 compile (-S), how many scratch / private-memory INSTRUCTIONS and SGPR-spill lane moves the kernel actually contains: a frame can
@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pime-robust-non-linear-set-point-control-with-reinforcement-learning_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
          f"-I{ROOT}/include", "-DPIME_BUILD", "-Rpass-analysis=kernel-resource-usage"]
+EXTRA = {"mlp16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}   # per-file flags of csrc/Makefile
 
 
 def demangle(name):
@@ -22,13 +23,14 @@ def demangle(name):
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "kernel_resources.txt")
     lines = []
+    only = set(sys.argv[2:])
     for f in sorted(os.listdir(CSRC)):
-        if not f.endswith(".hip"):
+        if not f.endswith(".hip") or (only and f not in only):
             continue
-        p = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-c", os.path.join(CSRC, f), "-o", "/dev/null"],
+        p = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *EXTRA.get(f, []), "-c", os.path.join(CSRC, f), "-o", "/dev/null"],
                            capture_output=True, text=True)
         tmp = f"/tmp/kres_{os.getpid()}_{f}.s"
-        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS[:-1], "--cuda-device-only", "-S", os.path.join(CSRC, f), "-o", tmp],
+        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS[:-1], *EXTRA.get(f, []), "--cuda-device-only", "-S", os.path.join(CSRC, f), "-o", tmp],
                        capture_output=True, text=True)
         asm = open(tmp).read() if os.path.exists(tmp) else ""
         if os.path.exists(tmp):
@@ -51,7 +53,7 @@ def main():
                 cur[m.group(1).strip()] = m.group(2)
         for r in rows:
             g = r.get
-            lines.append(f"{f}: {demangle(r['name'])[:84]:84s} VGPR {g('VGPRs', '?'):>4} AGPR {g('AGPRs', '?'):>4} "
+            lines.append(f"{f}: {demangle(r['name'])[:100]:100s} VGPR {g('VGPRs', '?'):>4} AGPR {g('AGPRs', '?'):>4} "
                          f"scratch {g('ScratchSize [bytes/lane]', '?'):>5} B/lane  static LDS {g('LDS Size [bytes/block]', '?'):>6} B  "
                          f"SGPR {g('TotalSGPRs', '?'):>4}  spilled VGPRs {g('VGPRs Spill', '?'):>3}  waves/SIMD {g('Occupancy [waves/SIMD]', '?')}"
                          f"  ISA: scratch instrs {isa.get(r['name'], ('?', '?'))[0]}, SGPR-spill lane moves {isa.get(r['name'], ('?', '?'))[1]}")
