@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 24
+#define PIME_ABI_VERSION 25
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -434,6 +434,42 @@ int pime_rollout_eval_metrics_rows(void);
 int pime_rollout_eval_metrics(pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
                               int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
                               double band, int32_t tail, double* ret, double* trace, double* metrics, pime_stream stream);
+
+/* -- fused response band ------------------------------------------------------------------------------------------
+ * pime_rollout_eval_metrics that also reduces every step ACROSS lanes: the step response of a whole plant ensemble as a band --
+ * per step and lane group the sum, sum of squares, minimum and maximum of four signals, and a histogram of the controlled output
+ * -- without the float64 trace.  Served exactly where pime_rollout_eval_supported answers 1 or 2 (2: seg_len must be 0).  Every
+ * argument up to `metrics` is pime_rollout_eval_metrics'; ret, trace and metrics hold exactly what that call leaves for the same
+ * launch.  ret, trace and hist may be NULL; metrics, stats and workspace may not.
+ *   SIGNALS of lane i at launch step t, the values the metrics of that step are built from:
+ *     PIME_BAND_Y   y_k, the controlled output after the step        PIME_BAND_E   r - y_k, with the set-point the lane holds
+ *     PIME_BAND_A   the env action as the trace records it           PIME_BAND_R   the float32 reward widened to double
+ *   GROUPS: lane i of the handle (the local index 0 .. N-1, not the global lane id) belongs to group i / group_lanes;
+ *     G = ceil(N / group_lanes).  group_lanes is a positive multiple of 16, or >= N (one group).  The last group may be short.
+ *   stats        [dev] float64[n_steps, PIME_BAND_ROWS, G], row = 4 * signal + stat, over the lanes of the group, in double:
+ *     PIME_BAND_SUM    sum x          PIME_BAND_SUMSQ  sum x * x (each product rounded before it is added)
+ *     PIME_BAND_MIN    min x          PIME_BAND_MAX    max x
+ *     Every lane counts once.  The order of the additions is fixed (per 16-lane tile four mirrored folds, then the group's tiles in
+ *     ascending order within sixteen interleaved chunks, then the chunks in ascending order): two launches from equal state
+ *     give bit-equal stats.  No floating-point atomics.
+ *   hist         [dev] uint32[n_steps, G, bins] or NULL: counts of Y.  1 <= bins <= 256, finite lo < hi;
+ *     scale = (double)bins / (hi - lo);  bin = 0 if !(y >= lo); bins - 1 if y >= hi; else min((int)floor((y - lo) * scale), bins - 1).
+ *     The call zeroes hist on the stream (capture-safe) and counts with integer atomics: exact, order-free.
+ *     bins, lo and hi are ignored when hist is NULL.
+ *   workspace    [dev] pime_rollout_eval_band_workspace_bytes(env, kind, md, n_steps, group_lanes) bytes (-1: bad arguments), any
+ *     content; the layout is private (one 128-byte partial per 16-lane tile and step: at most 8 bytes per lane and step plus one
+ *     tile).  Every byte the call reads from it was written by the same call.
+ * PIME_ERR_ARG with a message naming the argument: NULL metrics / stats / workspace, group_lanes that is neither a positive
+ * multiple of 16 nor >= N, bins outside 1 .. 256, lo >= hi or not finite, and pime_rollout_eval_metrics' own checks.
+ * pime_rollout_eval_band_rows() == PIME_BAND_ROWS. */
+enum pime_band_signal { PIME_BAND_Y = 0, PIME_BAND_E = 1, PIME_BAND_A = 2, PIME_BAND_R = 3, PIME_BAND_SIGNALS = 4 };
+enum pime_band_stat { PIME_BAND_SUM = 0, PIME_BAND_SUMSQ = 1, PIME_BAND_MIN = 2, PIME_BAND_MAX = 3, PIME_BAND_STATS = 4, PIME_BAND_ROWS = 16 };
+int pime_rollout_eval_band_rows(void);
+int64_t pime_rollout_eval_band_workspace_bytes(const pime_env* env, int32_t kind, int32_t md, int32_t n_steps, int32_t group_lanes);
+int pime_rollout_eval_band(pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                           int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail,
+                           double* ret, double* trace, double* metrics, int32_t group_lanes, double* stats, uint32_t* hist,
+                           int32_t bins, double lo, double hi, void* workspace, pime_stream stream);
 
 /* -- fused off-policy exploration -----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with

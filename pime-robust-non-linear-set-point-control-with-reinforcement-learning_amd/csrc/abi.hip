@@ -256,7 +256,7 @@ int h2d_from_double(const FieldRef& f, int n, const double* in, hipStream_t s) {
 template <typename S>
 static int rollout_eval_t(pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, int32_t kind, int32_t md, const float* packed_actor,
                           const double* priorK, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
-                          double* ret, double* trace, const EvalMetricsArgs& mx, pime_stream stream) {
+                          double* ret, double* trace, const EvalMetricsArgs& mx, const EvalBandArgs& bd, pime_stream stream) {
     EvalArgs<S> a{};
     a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
     a.n = e->cfg.n_envs;
@@ -268,7 +268,7 @@ static int rollout_eval_t(pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt,
     a.n_steps = n_steps; a.seg_len = seg_len;
     if (seg_len > 0)   // (validated by the caller: setpoints != NULL, 1 <= n_setpoints <= kMaxSetpoints)
         for (int j = 0; j < n_setpoints && j < kMaxSetpoints; ++j) a.setpoint[j] = setpoints[j];
-    a.ret = ret; a.trace = trace; a.mx = mx;
+    a.ret = ret; a.trace = trace; a.mx = mx; a.bd = bd;
     return launch_rollout_eval<S>(kind, md, a, static_cast<hipStream_t>(stream));
 }
 
@@ -815,10 +815,11 @@ int pime_rollout_eval_supported(const pime_env* e, int32_t kind, int32_t md) {
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;
 }
 
-// pime_rollout_eval and pime_rollout_eval_metrics (mx.out != NULL): one body, `fn` names the entry point in the messages
+// pime_rollout_eval, pime_rollout_eval_metrics (mx.out != NULL) and pime_rollout_eval_band (bd.partial != NULL): one body, `fn`
+// names the entry point in the messages
 static int rollout_eval_common(const char* fn, pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
                                int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret,
-                               double* trace, const EvalMetricsArgs& mx, pime_stream stream) {
+                               double* trace, const EvalMetricsArgs& mx, const EvalBandArgs& bd, pime_stream stream) {
     PIME_REQUIRE(e != nullptr, "NULL env handle");
     PIME_REQUIRE(pime_rollout_eval_supported(e, kind, md), "%s: not served for this handle / actor kind %d width %d "
                  "(pime_rollout_eval_supported)", fn, kind, md);
@@ -829,6 +830,8 @@ static int rollout_eval_common(const char* fn, pime_env* e, int32_t kind, int32_
                  "%s: the set-point schedule does not cover n_steps (at most %d segments)", fn, kMaxSetpoints);
     if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
     if (int rc = use_device(e)) return rc;
+    if (bd.hist != nullptr)   // the band's counts start from zero, on the stream (a memset node under capture)
+        PIME_HIP_TRY(hipMemsetAsync(bd.hist, 0, sizeof(uint32_t) * (size_t)n_steps * bd.groups * bd.bins, static_cast<hipStream_t>(stream)));
     if (md == 256 && kind != -1) {   // the streamed 16-tile rollout kernel in evaluation mode (mlp16.hip)
         PIME_REQUIRE(seg_len == 0 || pime_rollout_eval_supported(e, kind, md) == 1, "%s: no set-point schedule on a "
                      "Stacking observation (the protocols are defined on the Integrator observation)", fn);
@@ -841,23 +844,23 @@ static int rollout_eval_common(const char* fn, pime_env* e, int32_t kind, int32_
         a.img = packed_actor;
         a.a_std_log = nullptr;                  // not read in evaluation mode (no exploration noise)
         for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
-        a.n_steps = n_steps; a.eval_mode = 1; a.ret = ret; a.trace = trace; a.seg_len = seg_len; a.mx = mx;
+        a.n_steps = n_steps; a.eval_mode = 1; a.ret = ret; a.trace = trace; a.seg_len = seg_len; a.mx = mx; a.bd = bd;
         if (seg_len > 0)
             for (int j = 0; j < n_setpoints && j < 16; ++j) a.setpoint[j] = setpoints[j];
         return launch_rollout(kind, md, a, static_cast<hipStream_t>(stream));
     }
     if (e->cfg.state_mode == PIME_STATE_F64)
         return rollout_eval_t<double>(e, e->ph64, e->wt64, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints,
-                                      ret, trace, mx, stream);
+                                      ret, trace, mx, bd, stream);
     return rollout_eval_t<float>(e, e->ph32, e->wt32, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints, ret,
-                                 trace, mx, stream);
+                                 trace, mx, bd, stream);
 }
 
 int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
                       int32_t seg_len, const double* setpoints, int32_t n_setpoints, double* ret, double* trace,
                       pime_stream stream) {
     return rollout_eval_common("pime_rollout_eval", e, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints, ret,
-                               trace, EvalMetricsArgs{}, stream);
+                               trace, EvalMetricsArgs{}, EvalBandArgs{}, stream);
 }
 
 int pime_rollout_eval_metrics_rows(void) { return PIME_METRIC_ROWS; }
@@ -871,7 +874,62 @@ int pime_rollout_eval_metrics(pime_env* e, int32_t kind, int32_t md, const float
     EvalMetricsArgs mx{};
     mx.out = metrics; mx.band = band; mx.tail = tail;
     return rollout_eval_common("pime_rollout_eval_metrics", e, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints,
-                               n_setpoints, ret, trace, mx, stream);
+                               n_setpoints, ret, trace, mx, EvalBandArgs{}, stream);
+}
+
+int pime_rollout_eval_band_rows(void) { return PIME_BAND_ROWS; }
+
+// groups and tiles per group of a handle's lanes; 0 groups: group_lanes is neither a positive multiple of 16 nor >= N
+static int band_groups(const pime_env* e, int32_t group_lanes, int* tiles_per_group) {
+    const int N = e->cfg.n_envs, n_tiles = (N + 15) / 16;
+    if (group_lanes >= N) { *tiles_per_group = n_tiles; return 1; }
+    if (group_lanes <= 0 || group_lanes % 16 != 0) return 0;
+    *tiles_per_group = group_lanes / 16;
+    return (N + group_lanes - 1) / group_lanes;
+}
+
+int64_t pime_rollout_eval_band_workspace_bytes(const pime_env* e, int32_t kind, int32_t md, int32_t n_steps, int32_t group_lanes) {
+    int tpg = 0;
+    if (e == nullptr || !pime_rollout_eval_supported(e, kind, md) || n_steps < 1 || band_groups(e, group_lanes, &tpg) == 0) {
+        set_error("pime_rollout_eval_band_workspace_bytes: not served, n_steps %d < 1, or group_lanes %d (a positive multiple of 16, or >= N)",
+                  n_steps, group_lanes);
+        return -1;
+    }
+    return (int64_t)n_steps * ((e->cfg.n_envs + 15) / 16) * PIME_BAND_ROWS * (int64_t)sizeof(double);
+}
+
+int pime_rollout_eval_band(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
+                           int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* ret,
+                           double* trace, double* metrics, int32_t group_lanes, double* stats, uint32_t* hist, int32_t bins, double lo,
+                           double hi, void* workspace, pime_stream stream) {
+    PIME_REQUIRE(metrics != nullptr, "pime_rollout_eval_band: metrics is NULL");
+    PIME_REQUIRE(stats != nullptr, "pime_rollout_eval_band: stats is NULL");
+    PIME_REQUIRE(workspace != nullptr, "pime_rollout_eval_band: workspace is NULL");
+    PIME_REQUIRE(band >= 0.0 && band <= 1.79769313486231570815e308, "pime_rollout_eval_band: band %g (finite, >= 0)", band);
+    PIME_REQUIRE(tail >= 1, "pime_rollout_eval_band: tail %d (>= 1)", tail);
+    EvalBandArgs bd{};
+    if (hist != nullptr) {
+        PIME_REQUIRE(bins >= 1 && bins <= 256, "pime_rollout_eval_band: bins %d (1 .. 256)", bins);
+        const double big = 1.79769313486231570815e308;
+        PIME_REQUIRE(lo >= -big && lo <= big && hi >= -big && hi <= big && lo < hi, "pime_rollout_eval_band: lo %g, hi %g (finite, lo < hi)", lo, hi);   // (NaN fails)
+        bd.hist = hist; bd.bins = bins; bd.lo = lo; bd.hi = hi; bd.scale = (double)bins / (hi - lo);
+    }
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    bd.groups = band_groups(e, group_lanes, &bd.tiles_per_group);
+    PIME_REQUIRE(bd.groups >= 1, "pime_rollout_eval_band: group_lanes %d (a positive multiple of 16, or >= the %d lanes)", group_lanes,
+                 e->cfg.n_envs);
+    bd.n_tiles = (e->cfg.n_envs + 15) / 16;
+    bd.partial = static_cast<double*>(workspace);
+    EvalMetricsArgs mx{};
+    mx.out = metrics; mx.band = band; mx.tail = tail;
+    if (n_steps >= 1 && (int64_t)n_steps * bd.groups > 2147483647LL) {
+        set_error("pime_rollout_eval_band: n_steps %d x %d groups exceeds the reduction's grid", n_steps, bd.groups);
+        return PIME_ERR_ARG;
+    }
+    if (int rc = rollout_eval_common("pime_rollout_eval_band", e, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints,
+                                     ret, trace, mx, bd, stream))
+        return rc;
+    return launch_eval_band_reduce(bd, n_steps, stats, static_cast<hipStream_t>(stream));
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

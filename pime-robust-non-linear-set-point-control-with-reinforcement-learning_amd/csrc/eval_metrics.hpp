@@ -2,7 +2,7 @@
 // indices one reads off a step response, accumulated in registers while the response runs and written once per segment --
 // metrics [n_segments][PIME_METRIC_ROWS][N] float64 -- instead of a float64 trace of every step reduced on the host.
 // Shared by rollout_eval.hip's rollout_eval_kernel and the evaluation mode of mlp16.hip's rollout16_kernel, in both as a
-// compile-time variant (METRICS): the launches without metrics, and the training rollouts that share rollout16_kernel, carry none
+// compile-time variant (MODE, kEvalNone / kEvalMetrics / kEvalBand): the launches without metrics, and the training rollouts that share rollout16_kernel, carry none
 // of this (profiles/eval_metrics_kernel_resources.txt).
 #pragma once
 #include "pime_common.hpp"
@@ -62,6 +62,64 @@ struct SegMetrics {
         q[(size_t)PIME_METRIC_ACTION_VAR * N] = av;
     }
 };
+
+// ---- response band (pime_rollout_eval_band): every step reduced ACROSS lanes ------------------------------------------------
+// The third value of the kernels' compile-time mode; the band variant also produces the metrics.
+constexpr int kEvalNone = 0, kEvalMetrics = 1, kEvalBand = 2;
+
+struct EvalBandArgs {
+    double* partial;       // workspace [n_steps][n_tiles][PIME_BAND_ROWS]: one 128-byte partial per 16-lane tile and step
+    unsigned* hist;        // [n_steps][groups][bins] counts of Y, or NULL
+    int n_tiles;           // ceil(N / 16)
+    int tiles_per_group;   // group_lanes / 16 (one group: n_tiles)
+    int groups, bins;
+    double lo, hi, scale;  // scale = bins / (hi - lo)
+};
+
+// v of the lane a row-DPP control names (0x140 row_mirror: 15 - i; 0x141 row_half_mirror: 7 - i within the half row; quad_perm
+// 0x1B: 3 - i, 0xB1: i ^ 1 within the quad).  All 64 lanes are active where the band runs (the step loop is wave-uniform).
+template <int CTRL>
+__device__ __forceinline__ double band_dpp(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+
+// One step of one 16-lane tile.  The four lane groups of a wave hold copies of the same 16 lanes (bit-equal: the policy head ends
+// in a butterfly over the lane groups), so lane group q reduces signal q -- Y, E, A, R -- over its 16 lanes, the row of a DPP
+// operation: four mirrored folds (16 -> 8 -> 4 -> 2 -> 1 distinct values; a + b == b + a bit for bit, so both partners of a fold
+// hold the same value and the order is fixed), no LDS crossbar.  Lane 0 of the lane group stores SUM, SUMSQ, MIN, MAX: 32 bytes,
+// 128 per tile.  Idle lanes (shadows of lane N - 1) add 0 and +-inf.  `store`: lane 0 of a lane group of the wave that owns the
+// tile (QUAD: wave 0), the tile has a valid lane; `writer`: the one copy of a valid lane that counts in the histogram.
+__device__ __forceinline__ void band_step(const EvalBandArgs& b, int t, int tile, int q, bool valid, bool store, bool writer, int grp,
+                                          double y, double e, double a, double r) {
+    const double x = q == 0 ? y : (q == 1 ? e : (q == 2 ? a : r));
+    double s = valid ? x : 0.0, ss = valid ? x * x : 0.0;
+    double mn = valid ? x : __builtin_huge_val(), mx = valid ? x : -__builtin_huge_val();
+#define PIME_BAND_FOLD(CTRL)                                                      \
+    {                                                                             \
+        s += band_dpp<CTRL>(s);                                                   \
+        ss += band_dpp<CTRL>(ss);                                                 \
+        const double mo = band_dpp<CTRL>(mn), xo = band_dpp<CTRL>(mx);            \
+        mn = mo < mn ? mo : mn;                                                   \
+        mx = xo > mx ? xo : mx;                                                   \
+    }
+    PIME_BAND_FOLD(0x140) PIME_BAND_FOLD(0x141) PIME_BAND_FOLD(0x1B) PIME_BAND_FOLD(0xB1)
+#undef PIME_BAND_FOLD
+    if (store) {
+        double* p = b.partial + ((size_t)t * b.n_tiles + tile) * PIME_BAND_ROWS + 4 * q;
+        p[PIME_BAND_SUM] = s; p[PIME_BAND_SUMSQ] = ss; p[PIME_BAND_MIN] = mn; p[PIME_BAND_MAX] = mx;
+    }
+    if (b.hist != nullptr && writer) {
+        int bin = 0;
+        if (y >= b.hi) bin = b.bins - 1;
+        else if (y >= b.lo) {
+            bin = (int)floor((y - b.lo) * b.scale);
+            bin = bin > b.bins - 1 ? b.bins - 1 : bin;
+        }
+        atomicAdd(b.hist + ((size_t)t * b.groups + grp) * b.bins + bin, 1u);   // integer counts: exact, order-free
+    }
+}
 
 // the steps segment `seg` has in a launch of n_steps with a boundary every seg_len steps (seg_len 0: one segment)
 __device__ __forceinline__ int segment_steps(int n_steps, int seg_len, int seg) {

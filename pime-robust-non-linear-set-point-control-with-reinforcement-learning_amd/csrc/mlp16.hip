@@ -1731,9 +1731,11 @@ __device__ __forceinline__ void frames_store16(const WtPtrs<float>& wst, int N, 
 // tiles of the modular actor's tower layers: layer16rq) -- 256 workgroups instead of 64 for the reference script's 4 096 lanes, a quarter of the MFMA chain per env step.
 // METRICS (evaluation mode only, pime_rollout_eval_metrics): the per-segment step-response metrics of eval_metrics.hpp, a
 // compile-time variant so that the training instantiations keep their registers and their loop body.
-template <int T, int KIND, int ENV, int STACK, bool QUAD = false, bool METRICS = false>
+// MODE = kEvalBand (pime_rollout_eval_band): the metrics, and every step's signals reduced across the tile's lanes (band_step).
+template <int T, int KIND, int ENV, int STACK, bool QUAD = false, int MODE = kEvalNone>
 __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool METRICS = MODE != kEvalNone, BAND = MODE == kEvalBand;
     constexpr int D = ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK), Di = ENV == 2 ? 0 : 1, Do = D - Di, H = T / 2;
     constexpr bool MODULAR = KIND == MLP_MODULAR_ACTOR;
     static_assert(!MODULAR || ENV != 2, "the Stacking observation has no integrator column: plain actors only");
@@ -1782,6 +1784,9 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
     double ret = 0.0;
     [[maybe_unused]] SegMetrics M{};
     [[maybe_unused]] int seg = 0, kseg = 0;   // METRICS: segment and step inside it (wave-uniform)
+    [[maybe_unused]] const int tile = m >> 4;   // BAND: the 16-lane tile, its group, and the lanes that store the tile's partial
+    [[maybe_unused]] const int grp = BAND ? tile / a.bd.tiles_per_group : 0;
+    [[maybe_unused]] const bool band_store = valid && sl == 0 && (!QUAD || wave == 0);
     for (int t = 0; t < a.n_steps; ++t) {
         PIME_NO_HOIST();
         if (evaluating && a.seg_len > 0 && t % a.seg_len == 0) {   // segment boundary of a step-response protocol (wave-uniform), as
@@ -1889,6 +1894,10 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
         if constexpr (METRICS) {
             if constexpr (ENV == 0) M.step(kseg, (double)nxt[0], a_env, rew, a.mx.band);   // (float state: the observation IS the table value)
             else M.step(kseg, (double)W.h2, a_env, rew, a.mx.band);
+            if constexpr (BAND) {
+                const double y = ENV == 0 ? (double)nxt[0] : (double)W.h2;
+                band_step(a.bd, t, tile, g, valid, band_store, writer, grp, y, M.r - y, a_env, (double)rew);
+            }
             if (++kseg == M.len) {
                 if (writer) M.store(a.mx.out, seg, N, i);
                 ++seg; kseg = 0;
@@ -1915,15 +1924,15 @@ __global__ __launch_bounds__(k16Threads, 1) void rollout16_kernel(RolloutArgs a)
     }
 }
 
-template <int KIND, int ENV, int STACK, bool QUAD, bool METRICS>
+template <int KIND, int ENV, int STACK, bool QUAD, int MODE>
 static int launch_rollout16_q(const RolloutArgs& a, hipStream_t s) {
     constexpr int T = 16, D = ENV == 0 ? 3 : (ENV == 1 ? 4 : 3 * STACK);
     const size_t lds_bytes = sizeof(float) * ((size_t)(KIND == MLP_MODULAR_ACTOR ? lds16m<T>(D, 1, false).total : lds16<T>(D, false).total) +
                                               (QUAD ? T * 64 * 4 : 0));
     static LdsLimit lds_limit;  // per instantiation
-    PIME_RAISE_LDS(lds_limit, (rollout16_kernel<T, KIND, ENV, STACK, QUAD, METRICS>), 160 * 1024);
+    PIME_RAISE_LDS(lds_limit, (rollout16_kernel<T, KIND, ENV, STACK, QUAD, MODE>), 160 * 1024);
     const int per_wg = QUAD ? 16 : k16Group;
-    hipLaunchKernelGGL((rollout16_kernel<T, KIND, ENV, STACK, QUAD, METRICS>), dim3((a.n + per_wg - 1) / per_wg), dim3(k16Threads), lds_bytes, s, a);
+    hipLaunchKernelGGL((rollout16_kernel<T, KIND, ENV, STACK, QUAD, MODE>), dim3((a.n + per_wg - 1) / per_wg), dim3(k16Threads), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
@@ -1931,23 +1940,28 @@ template <int KIND, int ENV, int STACK>
 static int launch_rollout16_t(const RolloutArgs& a, hipStream_t s) {
     bool quad = a.n <= 4096;   // at most one tile per compute unit: split it over the workgroup's waves (as csrc/rollout.hip: tiling)
     if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
-    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, false>(a, s);
-    return launch_rollout16_q<KIND, ENV, STACK, false, false>(a, s);
+    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, kEvalNone>(a, s);
+    return launch_rollout16_q<KIND, ENV, STACK, false, kEvalNone>(a, s);
 }
-// evaluation mode: with a.mx.out the METRICS variant
+// evaluation mode: with a.mx.out the METRICS variant, with a.bd.partial the band variant
 template <int KIND, int ENV, int STACK>
 static int launch_rollout16_e(const RolloutArgs& a, hipStream_t s) {
     if (a.mx.out == nullptr) return launch_rollout16_t<KIND, ENV, STACK>(a, s);
     bool quad = a.n <= 4096;
     if (const char* e = std::getenv("PIME_ROLLOUT_NARROW")) quad = std::atoi(e) == 2;
-    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, true>(a, s);
-    return launch_rollout16_q<KIND, ENV, STACK, false, true>(a, s);
+    if (a.bd.partial != nullptr) {
+        if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, kEvalBand>(a, s);
+        return launch_rollout16_q<KIND, ENV, STACK, false, kEvalBand>(a, s);
+    }
+    if (quad) return launch_rollout16_q<KIND, ENV, STACK, true, kEvalMetrics>(a, s);
+    return launch_rollout16_q<KIND, ENV, STACK, false, kEvalMetrics>(a, s);
 }
 
 // width 256 (csrc/rollout.hip dispatches here); binary16 rows (PIME_STATE_MIXED16) are not served at this width
 int launch_rollout16(int kind, const RolloutArgs& a, hipStream_t s) {
     PIME_REQUIRE(a.I16 == nullptr, "the width-256 fused rollout serves PIME_STATE_MIXED handles");
     PIME_REQUIRE(a.mx.out == nullptr || a.eval_mode, "step-response metrics belong to the evaluation mode");
+    PIME_REQUIRE(a.bd.partial == nullptr || (a.eval_mode && a.mx.out != nullptr), "the response band belongs to the evaluation mode, with its metrics");
     if (a.eval_mode && kind == MLP_MODULAR_ACTOR) {
         if (a.env == 0) return launch_rollout16_e<MLP_MODULAR_ACTOR, 0, 0>(a, s);
         if (a.env == 1) return launch_rollout16_e<MLP_MODULAR_ACTOR, 1, 0>(a, s);

@@ -36,5 +36,7 @@ struct RolloutArgs {
     // ... and its per-segment step-response metrics (eval_metrics.hpp).  mx.out != NULL selects the METRICS instantiations of the
     // evaluation mode; no other instantiation reads these fields
     EvalMetricsArgs mx;
+    // ... and its per-step response band (pime_rollout_eval_band): bd.partial != NULL selects the band instantiations
+    EvalBandArgs bd;
 };
 }  // namespace pime

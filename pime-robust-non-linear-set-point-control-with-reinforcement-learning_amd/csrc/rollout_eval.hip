@@ -26,9 +26,11 @@ constexpr int kEvalThreads = 256;   // four waves of 16 lanes: one per SIMD (16-
 // METRICS (pime_rollout_eval_metrics): the per-segment step-response metrics of eval_metrics.hpp, accumulated in registers.  A
 // compile-time variant: as a run-time branch the accumulators cost every launch 14 .. 60 VGPRs (and the prior controller's
 // kernels two of their eight waves per SIMD), so the launches without metrics keep the code they had.
-template <int T, int KIND, int ENV, typename S, bool QUAD, bool METRICS>
+// MODE = kEvalBand (pime_rollout_eval_band): the metrics, and every step's signals reduced across the tile's lanes (band_step).
+template <int T, int KIND, int ENV, typename S, bool QUAD, int MODE>
 __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool METRICS = MODE != kEvalNone, BAND = MODE == kEvalBand;
     constexpr int D = ENV == 0 ? 3 : 4;
     constexpr bool POLICY = KIND >= 0;
     MlpLayout L{};
@@ -58,6 +60,9 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
     double ret = 0.0;
     [[maybe_unused]] SegMetrics M{};
     [[maybe_unused]] int seg = 0, k = 0;        // METRICS: segment and step inside it (wave-uniform)
+    [[maybe_unused]] const int tile = m >> 4;   // BAND: the 16-lane tile, its group, and the lanes that store the tile's partial
+    [[maybe_unused]] const int grp = BAND ? tile / a.bd.tiles_per_group : 0;
+    [[maybe_unused]] const bool band_store = valid && (lane & 15) == 0 && (!QUAD || wave == 0);
     for (int t = 0; t < a.n_steps; ++t) {
         PIME_NO_HOIST();
         if (a.seg_len > 0 && t % a.seg_len == 0) {   // segment boundary of a step-response protocol (wave-uniform)
@@ -111,8 +116,11 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
                 if constexpr (sizeof(S) == sizeof(float)) y = (double)obs[0];
                 else y = (double)ph_lookup<S>(a.p, a.st.table, E.C, E.x);
                 M.step(k, y, a_env, rew, a.mx.band);
+                if constexpr (BAND) band_step(a.bd, t, tile, lane >> 4, valid, band_store, writer, grp, y, M.r - y, a_env, (double)rew);
+            } else {
+                M.step(k, (double)W.h2, a_env, rew, a.mx.band);
+                if constexpr (BAND) band_step(a.bd, t, tile, lane >> 4, valid, band_store, writer, grp, (double)W.h2, M.r - (double)W.h2, a_env, (double)rew);
             }
-            else M.step(k, (double)W.h2, a_env, rew, a.mx.band);
             if (++k == M.len) {
                 if (writer) M.store(a.mx.out, seg, N, i);
                 ++seg; k = 0;
@@ -128,23 +136,24 @@ __global__ __launch_bounds__(kEvalThreads) void rollout_eval_kernel(EvalArgs<S> 
 
 int mlp_check(int kind, int D, int Di, int md);
 
-template <int T, int KIND, int ENV, typename S, bool QUAD, bool METRICS>
+template <int T, int KIND, int ENV, typename S, bool QUAD, int MODE>
 static int launch_eval_m(const EvalArgs<S>& a, hipStream_t s) {
     size_t lds_bytes = 0;
     if constexpr (KIND >= 0) {
         lds_bytes = ((size_t)mlp_layout(KIND, ENV == 0 ? 3 : 4, 1, T * 32).total + (QUAD ? quad_xchg_floats<T>() : 0)) * sizeof(float);
         static LdsLimit lds_limit;  // per instantiation
-        PIME_RAISE_LDS(lds_limit, (rollout_eval_kernel<T, KIND, ENV, S, QUAD, METRICS>), 160 * 1024);
+        PIME_RAISE_LDS(lds_limit, (rollout_eval_kernel<T, KIND, ENV, S, QUAD, MODE>), 160 * 1024);
     }
     const int per_wg = QUAD ? 16 : kEvalThreads / 64 * 16;
-    hipLaunchKernelGGL((rollout_eval_kernel<T, KIND, ENV, S, QUAD, METRICS>), dim3((a.n + per_wg - 1) / per_wg), dim3(kEvalThreads), lds_bytes, s, a);
+    hipLaunchKernelGGL((rollout_eval_kernel<T, KIND, ENV, S, QUAD, MODE>), dim3((a.n + per_wg - 1) / per_wg), dim3(kEvalThreads), lds_bytes, s, a);
     PIME_HIP_TRY(hipGetLastError());
     return PIME_OK;
 }
 template <int T, int KIND, int ENV, typename S, bool QUAD>
 static int launch_eval_q(const EvalArgs<S>& a, hipStream_t s) {
-    if (a.mx.out != nullptr) return launch_eval_m<T, KIND, ENV, S, QUAD, true>(a, s);
-    return launch_eval_m<T, KIND, ENV, S, QUAD, false>(a, s);
+    if (a.bd.partial != nullptr) return launch_eval_m<T, KIND, ENV, S, QUAD, kEvalBand>(a, s);
+    if (a.mx.out != nullptr) return launch_eval_m<T, KIND, ENV, S, QUAD, kEvalMetrics>(a, s);
+    return launch_eval_m<T, KIND, ENV, S, QUAD, kEvalNone>(a, s);
 }
 template <int T, int KIND, int ENV, typename S>
 static int launch_eval_t(const EvalArgs<S>& a, hipStream_t s) {
@@ -173,6 +182,37 @@ int launch_rollout_eval(int kind, int md, const EvalArgs<S>& a, hipStream_t s) {
     set_error("no fused evaluation instantiation for env %d kind %d width %d", a.env, kind, md);
     return PIME_ERR_ARG;
 }
+// ---- the band's second stage: stats[t][row][g] from the group's tile partials, in a fixed order -----------------------------------
+// One workgroup per (step, group): thread (c, row) combines the tiles first + c, first + c + 16, ... of its row in ascending order,
+// then row's thread of chunk 0 combines the sixteen chunk results in ascending c.  No atomics: two launches give the same bits.
+constexpr int kBandChunks = 16;
+__device__ __forceinline__ double band_combine(int stat, double acc, double v) {
+    if (stat == PIME_BAND_MIN) return v < acc ? v : acc;
+    if (stat == PIME_BAND_MAX) return v > acc ? v : acc;
+    return acc + v;
+}
+__global__ __launch_bounds__(kBandChunks * PIME_BAND_ROWS) void eval_band_reduce_kernel(EvalBandArgs b, double* __restrict__ stats) {
+    __shared__ double sh[kBandChunks][PIME_BAND_ROWS];
+    const int row = threadIdx.x % PIME_BAND_ROWS, c = threadIdx.x / PIME_BAND_ROWS, stat = row & 3;
+    const int t = blockIdx.x / b.groups, g = blockIdx.x % b.groups;
+    const int first = g * b.tiles_per_group;
+    const int end = first + b.tiles_per_group < b.n_tiles ? first + b.tiles_per_group : b.n_tiles;
+    double acc = stat == PIME_BAND_MIN ? __builtin_huge_val() : (stat == PIME_BAND_MAX ? -__builtin_huge_val() : 0.0);
+    const double* p = b.partial + (size_t)t * b.n_tiles * PIME_BAND_ROWS + row;
+    for (int tile = first + c; tile < end; tile += kBandChunks) acc = band_combine(stat, acc, p[(size_t)tile * PIME_BAND_ROWS]);
+    sh[c][row] = acc;
+    __syncthreads();
+    if (c == 0) {
+        for (int j = 1; j < kBandChunks; ++j) acc = band_combine(stat, acc, sh[j][row]);
+        stats[((size_t)t * PIME_BAND_ROWS + row) * b.groups + g] = acc;
+    }
+}
+int launch_eval_band_reduce(const EvalBandArgs& b, int n_steps, double* stats, hipStream_t s) {
+    hipLaunchKernelGGL(eval_band_reduce_kernel, dim3((unsigned)((size_t)n_steps * b.groups)), dim3(kBandChunks * PIME_BAND_ROWS), 0, s, b, stats);
+    PIME_HIP_TRY(hipGetLastError());
+    return PIME_OK;
+}
+
 template int launch_rollout_eval<float>(int, int, const EvalArgs<float>&, hipStream_t);
 template int launch_rollout_eval<double>(int, int, const EvalArgs<double>&, hipStream_t);
 

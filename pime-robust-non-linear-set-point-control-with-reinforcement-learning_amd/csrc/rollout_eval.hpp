@@ -22,7 +22,10 @@ struct EvalArgs {
     double* ret;             // [N] += sum of the launch's rewards, or NULL
     double* trace;           // [n_steps][6][N] or NULL
     EvalMetricsArgs mx;      // per-segment step-response metrics (eval_metrics.hpp); mx.out NULL: none
+    EvalBandArgs bd;         // per-step response band (pime_rollout_eval_band); bd.partial NULL: none
 };
 template <typename S>
 int launch_rollout_eval(int kind, int md, const EvalArgs<S>& a, hipStream_t s);
+// stats [n_steps][PIME_BAND_ROWS][groups] from the partials a band launch left in b.partial (same stream, after that launch)
+int launch_eval_band_reduce(const EvalBandArgs& b, int n_steps, double* stats, hipStream_t s);
 }  // namespace pime

@@ -16,7 +16,7 @@ LIB_PATH = _override or os.path.join(PACKAGE_DIR, "libpime_hip.so")
 CSRC = os.path.join(PACKAGE_DIR, "csrc")
 
 OK = 0
-ABI_VERSION = 24
+ABI_VERSION = 25
 ENV_PH, ENV_WT = 0, 1
 STATE_F64, STATE_MIXED, STATE_MIXED16 = 0, 1, 2
 REWARD = {"distance": 0, "square_distance": 1, "sparse": 2}
@@ -25,6 +25,10 @@ MLP_CRITIC, MLP_PLAIN_ACTOR, MLP_MODULAR_ACTOR, MLP_SAC_ACTOR = 0, 1, 2, 3
 # rows of pime_rollout_eval_metrics' result (enum pime_metric), in order
 METRIC_NAMES = ("iae", "ise", "itae", "overshoot", "settling_step", "steady_state_error", "return", "action_variation")
 METRIC_ROWS = len(METRIC_NAMES)
+# pime_rollout_eval_band: stats row = 4 * signal + stat (enums pime_band_signal / pime_band_stat)
+BAND_SIGNALS = ("y", "e", "action", "reward")
+BAND_STATS = ("sum", "sumsq", "min", "max")
+BAND_ROWS = len(BAND_SIGNALS) * len(BAND_STATS)
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -152,6 +156,10 @@ _SIGNATURES = {
     "pime_rollout_eval": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "pime_rollout_eval_metrics_rows": (C.c_int, []),
     "pime_rollout_eval_metrics": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "pime_rollout_eval_band_rows": (C.c_int, []),
+    "pime_rollout_eval_band_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32, _i32]),
+    "pime_rollout_eval_band": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _i32, _vp, _vp,
+                                         _i32, C.c_double, C.c_double, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy": (C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,
                                          _vp, _i32, _i32, _vp]),

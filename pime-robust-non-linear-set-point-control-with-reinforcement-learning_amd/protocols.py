@@ -18,13 +18,18 @@ reads; round 2 read four state fields back per step); an arbitrary `policy` call
 segment the eight control indices of `METRIC_NAMES` (error integrals, overshoot, settling step, steady-state error, return, action
 variation; definitions in include/pime_hip.h), reduced on the device while the protocol runs (`pime_rollout_eval_metrics`: one
 launch, no trace) -- a dense robustness map costs 64 bytes per plant and segment instead of 48 bytes per plant and STEP.
+
+`step_response_band` returns the response of a whole ENSEMBLE as a band: per step and lane group the mean, standard deviation,
+minimum and maximum of the controlled output, the error, the action and the reward over the group's plants, and a histogram of
+the output (`band_quantiles` turns it into a percentile fan) -- reduced across lanes on the device while the protocol runs
+(`pime_rollout_eval_band`: one launch, no trace; 128 bytes + 4 bytes per bin leave the device per step and group).
 """
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from .native import ENV_PH, METRIC_NAMES
+from .native import BAND_SIGNALS, BAND_STATS, ENV_PH, METRIC_NAMES
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -154,6 +159,40 @@ def metrics_from_records(y_after, r, action, reward, y_start, seg_len=0, band=0.
     return out
 
 
+def _protocol_start(env, is_ph, steps, plants):
+    """What the fused protocols do before their one launch: the plants written, a reset, the plant state at 0."""
+    env.set_reset_all(False)
+    if is_ph:
+        env.set_max_step(2 ** 30)
+        if plants is not None:
+            plants = np.asarray(plants, dtype=np.float64)
+            env.set_params(plants[:, 0], plants[:, 1])
+        env.reset()
+        env.set_field("x", np.zeros(env.num_envs))
+    else:
+        env.set_max_step(max(steps, env.max_step))
+        if plants is not None:
+            plants = np.asarray(plants, dtype=np.float64)
+            env.reset_changable_parameters(plants[:, 0], plants[:, 1], plants[:, 2])
+        env.reset()
+        env.set_field("h1", np.zeros(env.num_envs)); env.set_field("h2", np.zeros(env.num_envs))
+
+
+def _protocol_records(env, is_ph, policy, setpoints, steps, plants, agent):
+    """The step-per-launch protocol as records: (y_after, r, action, reward, y_before), each [T, N]."""
+    if is_ph:
+        res = ph_step_response(env, policy=policy, setpoints=setpoints, steps=steps, plants=plants, agent=agent)
+        y_before = res["y"]                                              # y BEFORE each step; the plant state is carried over
+        y_after = np.concatenate([y_before[1:], env.get_field("y")[None]])
+        r, action = res["r"], res["action"]
+    else:
+        res = wt_step_response(env, policy=policy, setpoints=setpoints, steps=steps, plants=plants, agent=agent)
+        y_after = res["obs"][:, :, 1]
+        y_before = np.concatenate([np.zeros((1, env.num_envs)), y_after[:-1]])   # the protocol starts from empty tanks
+        r, action = res["obs"][:, :, 2], res["action"]
+    return y_after, r, action, res["reward"], y_before
+
+
 def step_response_metrics(env, agent=None, policy=None, setpoints=None, steps=None, plants=None, band=None, tail=10):
     """The step-response protocol of `env` (pH: `ph_step_response`, r = 10,6,3,8,5 x 50 steps; Integrator tank:
     `wt_step_response`, r = 3,6,9,4,2 x max_step) reduced to its control indices: dict of metric name (`METRIC_NAMES`) ->
@@ -167,36 +206,13 @@ def step_response_metrics(env, agent=None, policy=None, setpoints=None, steps=No
     band = 0.05 if band is None else band
     fused = _fused_policy(env, policy, agent)
     if fused is not None and len(setpoints) <= 16 and (is_ph or env.num_stack == 0):
-        env.set_reset_all(False)
-        if is_ph:
-            env.set_max_step(2 ** 30)
-            if plants is not None:
-                plants = np.asarray(plants, dtype=np.float64)
-                env.set_params(plants[:, 0], plants[:, 1])
-            env.reset()
-            env.set_field("x", np.zeros(env.num_envs))
-        else:
-            env.set_max_step(max(steps, env.max_step))
-            if plants is not None:
-                plants = np.asarray(plants, dtype=np.float64)
-                env.reset_changable_parameters(plants[:, 0], plants[:, 1], plants[:, 2])
-            env.reset()
-            env.set_field("h1", np.zeros(env.num_envs)); env.set_field("h2", np.zeros(env.num_envs))
+        _protocol_start(env, is_ph, steps, plants)
         _, m, _ = env.rollout_eval_metrics(fused[0], fused[1], len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band,
                                            tail=tail)
         m = m.cpu().numpy()
         return {name: np.ascontiguousarray(m[:, j]) for j, name in enumerate(METRIC_NAMES)}
-    if is_ph:
-        res = ph_step_response(env, policy=policy, setpoints=setpoints, steps=steps, plants=plants, agent=agent)
-        y_before = res["y"]                                              # y BEFORE each step; the plant state is carried over
-        y_after = np.concatenate([y_before[1:], env.get_field("y")[None]])
-        r, action = res["r"], res["action"]
-    else:
-        res = wt_step_response(env, policy=policy, setpoints=setpoints, steps=steps, plants=plants, agent=agent)
-        y_after = res["obs"][:, :, 1]
-        y_before = np.concatenate([np.zeros((1, env.num_envs)), y_after[:-1]])   # the protocol starts from empty tanks
-        r, action = res["obs"][:, :, 2], res["action"]
-    return metrics_from_records(y_after, r, action, res["reward"], y_before[::steps], seg_len=steps, band=band, tail=tail)
+    y_after, r, action, reward, y_before = _protocol_records(env, is_ph, policy, setpoints, steps, plants, agent)
+    return metrics_from_records(y_after, r, action, reward, y_before[::steps], seg_len=steps, band=band, tail=tail)
 
 
 def robust_grid(env, axes, agent=None, policy=None, setpoints=None, steps=None, band=None, tail=10):
@@ -215,3 +231,112 @@ def robust_grid(env, axes, agent=None, policy=None, setpoints=None, steps=None, 
     plants = np.stack([mesh[k].reshape(-1) for k in names], axis=1)
     m = step_response_metrics(env, agent=agent, policy=policy, setpoints=setpoints, steps=steps, plants=plants, band=band, tail=tail)
     return {k: v.reshape(v.shape[0], *shape) for k, v in m.items()}, axes
+
+
+def band_from_records(y_after, r, action, reward, group_lanes=None, hist=None):
+    """The rows of `pime_rollout_eval_band` from step-by-step records, in numpy -- for the paths the fused kernel does not serve
+    (an arbitrary `policy` callable, draw injection).  y_after [T, N]: the controlled output AFTER each step; r [T, N] or [T]: the
+    set-point of each step; action, reward [T, N] (rewards are rounded to float32 before they are widened, as the kernel's are).
+    Lane i belongs to group i // group_lanes (None or >= N: one group).  hist: None or (bins, lo, hi).  Returns a dict: stats
+    float64 [T, 16, G] with row 4 * signal + stat over BAND_SIGNALS x BAND_STATS, count int64 [G], hist int64 [T, G, bins] or None."""
+    y = np.asarray(y_after, dtype=np.float64)
+    T, N = y.shape
+    r = np.broadcast_to(np.asarray(r, dtype=np.float64).reshape(T, -1), (T, N))
+    a = np.asarray(action, dtype=np.float64).reshape(T, N)
+    rew = np.asarray(reward).reshape(T, N).astype(np.float32).astype(np.float64)
+    gl = N if group_lanes is None or group_lanes >= N else int(group_lanes)
+    if gl <= 0 or (gl < N and gl % 16):
+        raise ValueError(f"band_from_records: group_lanes {group_lanes} (a positive multiple of 16, or >= the {N} lanes)")
+    G = -(-N // gl)
+    stats = np.empty((T, len(BAND_SIGNALS) * len(BAND_STATS), G))
+    count = np.array([min(gl, N - g * gl) for g in range(G)], dtype=np.int64)
+    counts = None
+    if hist is not None:
+        bins, lo, hi = int(hist[0]), float(hist[1]), float(hist[2])
+        if not (1 <= bins <= 256 and np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError(f"band_from_records: hist {hist} (1 <= bins <= 256, finite lo < hi)")
+        scale = float(bins) / (hi - lo)
+        with np.errstate(invalid="ignore"):
+            inside = np.minimum(np.floor((np.clip(y, lo, hi) - lo) * scale), bins - 1).astype(np.int64)
+            b = np.where(~(y >= lo), 0, np.where(y >= hi, bins - 1, inside))
+        counts = np.zeros((T, G, bins), dtype=np.int64)
+    for g in range(G):
+        sl = slice(g * gl, min((g + 1) * gl, N))
+        for j, x in enumerate((y[:, sl], (r - y)[:, sl], a[:, sl], rew[:, sl])):
+            stats[:, 4 * j, g] = x.sum(axis=1)
+            stats[:, 4 * j + 1, g] = (x * x).sum(axis=1)
+            stats[:, 4 * j + 2, g] = x.min(axis=1)
+            stats[:, 4 * j + 3, g] = x.max(axis=1)
+        if counts is not None:
+            for t in range(T):
+                counts[t, g] = np.bincount(b[t, sl], minlength=bins)
+    return {"stats": stats, "count": count, "hist": counts}
+
+
+def _band_result(stats, count, counts, hist, metrics):
+    """stats [T, 16, G] -> the band: mean / std / min / max per signal as [T, G] (std: the population's, from sum and sum of squares)."""
+    n = count.astype(np.float64)[None, :]
+    out = {"mean": {}, "std": {}, "min": {}, "max": {}, "count": count, "hist": counts, "edges": None, "metrics": metrics}
+    for j, name in enumerate(BAND_SIGNALS):
+        mean = stats[:, 4 * j + BAND_STATS.index("sum")] / n
+        out["mean"][name] = mean
+        out["std"][name] = np.sqrt(np.maximum(stats[:, 4 * j + BAND_STATS.index("sumsq")] / n - mean * mean, 0.0))
+        out["min"][name] = np.ascontiguousarray(stats[:, 4 * j + BAND_STATS.index("min")])
+        out["max"][name] = np.ascontiguousarray(stats[:, 4 * j + BAND_STATS.index("max")])
+    if hist is not None:
+        out["edges"] = np.linspace(float(hist[1]), float(hist[2]), int(hist[0]) + 1)
+    return out
+
+
+def step_response_band(env, agent=None, policy=None, setpoints=None, steps=None, plants=None, group_lanes=None, hist=None, band=None,
+                       tail=10):
+    """The step-response protocol of `env` (as `step_response_metrics`) over an ensemble of plants, reduced to a band per step:
+    returns a dict with mean / std / min / max -> {signal in BAND_SIGNALS: float64 [T, G]} over the lanes of each group of
+    `group_lanes` consecutive lanes (None: all lanes are one group), count int64 [G], hist (counts [T, G, bins] of the controlled
+    output, for hist=(bins, lo, hi); values outside [lo, hi) count in the outer bins) with its bin edges [bins + 1], and metrics
+    (the dict of `step_response_metrics`).  plants None: every lane keeps the plant its reset draws from the registered ranges.
+    One launch and no trace where the fused evaluation kernel serves the configuration; otherwise the step-per-launch protocol runs
+    and `band_from_records` / `metrics_from_records` reduce its records."""
+    is_ph = env.kind == ENV_PH
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    fused = _fused_policy(env, policy, agent)
+    if fused is not None and len(setpoints) <= 16 and (is_ph or env.num_stack == 0):
+        _protocol_start(env, is_ph, steps, plants)
+        _, m, stats, counts, _ = env.rollout_eval_band(fused[0], fused[1], len(setpoints) * steps, setpoints=setpoints, seg_len=steps,
+                                                       band=band, tail=tail, group_lanes=group_lanes, hist=hist)
+        m, stats = m.cpu().numpy(), stats.cpu().numpy()
+        gl = env.num_envs if group_lanes is None or group_lanes >= env.num_envs else int(group_lanes)
+        count = np.array([min(gl, env.num_envs - g * gl) for g in range(stats.shape[2])], dtype=np.int64)
+        counts = None if counts is None else counts.cpu().numpy().view(np.uint32).astype(np.int64)
+        metrics = {name: np.ascontiguousarray(m[:, j]) for j, name in enumerate(METRIC_NAMES)}
+        return _band_result(stats, count, counts, hist, metrics)
+    y_after, r, action, reward, y_before = _protocol_records(env, is_ph, policy, setpoints, steps, plants, agent)
+    metrics = metrics_from_records(y_after, r, action, reward, y_before[::steps], seg_len=steps, band=band, tail=tail)
+    b = band_from_records(y_after, r, action, reward, group_lanes=group_lanes, hist=hist)
+    return _band_result(b["stats"], b["count"], b["hist"], hist, metrics)
+
+
+def band_quantiles(hist, edges, q):
+    """Percentiles of the controlled output from a band's histogram: hist [..., bins] counts, edges [bins + 1], q in [0, 1] (scalar
+    or 1-D) -> float64 [..., len(q)], by linear interpolation inside the bin that holds the q-th share of the counts (the counts of
+    a bin are taken as spread evenly over it).  The outer bins also hold what fell outside [edges[0], edges[-1]): a quantile
+    there is only known to lie beyond the edge.  A histogram without counts gives NaN."""
+    h = np.asarray(hist, dtype=np.float64)
+    edges = np.asarray(edges, dtype=np.float64)
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    bins = h.shape[-1]
+    assert edges.shape == (bins + 1,) and ((q >= 0) & (q <= 1)).all()
+    c = np.cumsum(h, axis=-1)
+    total = c[..., -1]
+    out = np.empty(h.shape[:-1] + (q.size,))
+    for j, qj in enumerate(q):
+        target = qj * total
+        b = np.minimum(((c < target[..., None]) | (c == 0)).sum(axis=-1), bins - 1)   # the first non-empty bin whose cumulative count reaches the target
+        before = np.where(b > 0, np.take_along_axis(c, np.maximum(b - 1, 0)[..., None], axis=-1)[..., 0], 0.0)
+        inside = np.take_along_axis(h, b[..., None], axis=-1)[..., 0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            frac = np.where(inside > 0, (target - before) / inside, 0.0)
+        out[..., j] = np.where(total > 0, edges[b] + frac * (edges[b + 1] - edges[b]), np.nan)
+    return out

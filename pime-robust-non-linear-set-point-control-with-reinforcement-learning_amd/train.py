@@ -163,6 +163,31 @@ def robust_test(args, agent, cwd):
     np.savez(path, metrics=metrics, metric_names=np.asarray(protocols.METRIC_NAMES), plants=plants,
              setpoints=np.asarray(setpoints, dtype=np.float64), band=band, tail=tail, steps=steps)
     print(f"robust test: {len(plants)} plants x {len(setpoints)} set-points -> {path}")
+    response_band(args, agent, cwd, policy, setpoints, steps, overrides)
+    return path
+
+
+BAND_LANES, BAND_BINS, BAND_QUANTILES = 1024, 128, (0.05, 0.25, 0.5, 0.75, 0.95)
+
+
+def response_band(args, agent, cwd, policy, setpoints, steps, overrides):
+    """The other half of --robust_test: the same protocol under the same policy on BAND_LANES lanes whose plants the reset draws
+    from the env's registered ensemble ranges, reduced per step across the lanes (protocols.step_response_band: one group, one
+    launch where the fused kernel serves the agent).  Writes <cwd>/response_band.npz: mean / std / min / max [4, T] in the row
+    order `signals`, count, hist [T, BAND_BINS] of the controlled output with its `edges`, `quantiles` [T, 5] at
+    `quantile_levels`, setpoints, steps."""
+    from . import protocols
+    is_ph = "NonLinearWaterTank" not in args.env
+    env = gym_control.make_vec(args.env, BAND_LANES, device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+    b = protocols.step_response_band(env, agent=agent, policy=policy, setpoints=setpoints, steps=steps,
+                                     hist=(BAND_BINS, 0.0, 14.0 if is_ph else 10.0))
+    env.close()
+    path = os.path.join(cwd, "response_band.npz")
+    rows = {k: np.stack([b[k][name][:, 0] for name in protocols.BAND_SIGNALS]) for k in ("mean", "std", "min", "max")}
+    np.savez(path, signals=np.asarray(protocols.BAND_SIGNALS), count=b["count"], hist=b["hist"][:, 0], edges=b["edges"],
+             quantile_levels=np.asarray(BAND_QUANTILES), quantiles=protocols.band_quantiles(b["hist"][:, 0], b["edges"], BAND_QUANTILES),
+             setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, **rows)
+    print(f"response band: {BAND_LANES} plants x {len(setpoints)} set-points -> {path}")
     return path
 
 

@@ -472,6 +472,48 @@ class VecControlEnv:
             self._t_lanes += n_steps
         return ret, metrics, trace
 
+    def rollout_eval_band(self, packed_actor, priorK, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, group_lanes=None,
+                          hist=None, want_trace=False, ret=None):
+        """`rollout_eval_metrics` that also reduces every step across lanes (pime_rollout_eval_band): returns (ret, metrics, stats,
+        hist, trace).  stats float64 [n_steps, 16, G]: row 4 * signal + stat over native.BAND_SIGNALS (controlled output y, error
+        r - y, env action, reward) x native.BAND_STATS (sum, sum of squares, min, max) of the lanes of each group of `group_lanes`
+        consecutive lanes (a positive multiple of 16; None: all lanes as one group), G = ceil(N / group_lanes).  hist: None, or
+        (bins, lo, hi) -> uint32 counts [n_steps, G, bins] of y (stored in an int32 tensor; definitions in include/pime_hip.h).
+        ret, metrics and trace are what `rollout_eval_metrics` returns for the same launch."""
+        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
+        assert k.size == self.obs_dim
+        if ret is None:
+            ret = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
+        n_steps, seg_len = int(n_steps), int(seg_len)
+        n_seg = -(-n_steps // seg_len) if seg_len > 0 else 1
+        group_lanes = self.num_envs if group_lanes is None else int(group_lanes)
+        if packed_actor is None:
+            kind, md, img = -1, 0, None
+        else:
+            kind = _EVAL_KINDS[packed_actor.kind]
+            md, img = int(packed_actor.md), packed_actor.packed
+        ws_bytes = int(self._lib.pime_rollout_eval_band_workspace_bytes(self._h, kind, md, n_steps, group_lanes))
+        if ws_bytes < 0:
+            raise native.PimeError(f"pime_rollout_eval_band_workspace_bytes: {native.last_error()}")
+        groups = -(-self.num_envs // group_lanes) if group_lanes < self.num_envs else 1
+        metrics = torch.empty((max(n_seg, 1), native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
+        stats = torch.empty((n_steps, native.BAND_ROWS, groups), dtype=torch.float64, device=self.device)
+        workspace = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+        trace = torch.empty((n_steps, 6, self.num_envs), dtype=torch.float64, device=self.device) if want_trace else None
+        bins, lo, hi = (0, 0.0, 0.0) if hist is None else (int(hist[0]), float(hist[1]), float(hist[2]))
+        counts = None if hist is None else torch.empty((n_steps, groups, max(bins, 0)), dtype=torch.int32, device=self.device)
+        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        native.check(self._lib.pime_rollout_eval_band(
+            self._h, kind, md, native.ptr(img), native.ptr(k), n_steps, seg_len, native.ptr(sp) if sp.size else None, int(sp.size),
+            float(band), int(tail), native.ptr(ret), native.ptr(trace), native.ptr(metrics), group_lanes, native.ptr(stats),
+            native.ptr(counts), bins, lo, hi, native.ptr(workspace), self._stream()), "pime_rollout_eval_band")
+        self._was_reset = False   # as rollout_eval: the lanes sit somewhere inside an episode
+        if self._t_lanes is None:
+            self._t_all += n_steps
+        else:
+            self._t_lanes += n_steps
+        return ret, metrics, stats, counts, trace
+
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
         out = np.empty(self.num_envs, dtype=np.float64)
