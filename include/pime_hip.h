@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 25
+#define PIME_ABI_VERSION 26
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -470,6 +470,54 @@ int pime_rollout_eval_band(pime_env* env, int32_t kind, int32_t md, const float*
                            int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail,
                            double* ret, double* trace, double* metrics, int32_t group_lanes, double* stats, uint32_t* hist,
                            int32_t bins, double lo, double hi, void* workspace, pime_stream stream);
+
+/* -- fused replay of recorded runs (plant identification) ----------------------------------------------------------------------
+ * Scores PLANTS against measured data: every lane of the handle is a candidate plant, every record a run of T steps with the env
+ * action that was applied and the outputs that were measured.  ONE launch runs every (lane, record) pair through the product's own
+ * lane step (csrc/env_device.hpp: a replayed step is bit for bit the arithmetic of pime_env_step) with the lane in registers and
+ * reduces the output error while the record runs -- instead of one pime_env_step per recorded step and record (and, for one-step
+ * prediction, a synchronous pime_env_write_field per step) on a handle that the run advances.  Process noise is zero whatever
+ * wt_noise_scale says; no reset ever happens and T may exceed max_steps; rewards, r and the integrated error play no part.
+ *   rec (all float64, [dev], shared by all lanes)
+ *     action   [E, T]         the env action exactly as env.step received it (pH clips it to [-1, 1] as the env does; the water
+ *                             tank does not clip)
+ *     output   [E, T + 1, C]  the measured outputs, row 0 before the first step; C = pime_env_replay_channels: pH 1 (y), water
+ *                             tank 2 (h1, h2).  The tank's state at row 0 is output[e][0][:] rounded to the state's precision.
+ *     state0   [E] or NULL    pH only: the reaction-invariant x at row 0.  NULL: x is hidden, and each (plant, record) pair derives
+ *                             x0 = k0 / (C_plant * ph_table_scale), k0 = the smallest table index whose entry is <= output[e][0][0]
+ *                             (binary search; the table is strictly decreasing; compared in the precision the handle holds the
+ *                             table in), clamped to the table
+ *   mode  PIME_REPLAY_SIMULATE  free run from row 0
+ *         PIME_REPLAY_PREDICT   one-step-ahead prediction, water tank only: before step t the state is set to the measured
+ *                               output[e][t][:] rounded to the state's precision (a NaN word keeps the simulated one)
+ *   skip  burn-in: the steps t < skip run but their error is not counted (the transient of a wrong x0 decays as A^t)
+ *   err   [dev] float64[E, PIME_REPLAY_ROWS, N], per record and lane, over t = skip .. T-1 in ascending order and per step channel
+ *         0 before channel 1:  d = (double)sim_c - output[e][t+1][c];  SSE_c += d * d (the product rounded before it is added);
+ *         MAX_c = max(MAX_c, |d|);  COUNT = the number of terms that entered SSE0 + SSE1.  A NaN measurement is a gap: no term,
+ *         not counted.  The channel-1 rows are 0 for pH.
+ *   sim   [dev] float64[E, T, C, N] or NULL: the simulated outputs after each step (every step, the burn-in included)
+ * The call READS the handle and never writes it: per lane pH (A, B, C) / water tank (a1, a2, Kp), from the configuration the plant
+ * constants and the table; state, step and episode counters and frame rings are bit-unchanged.  Asynchronous on the caller's
+ * stream, capturable, no allocation, no synchronisation, no atomics; a pair's result does not depend on N, E or the grid.
+ * Served (pime_env_replay_supported == 1): pH (SIMULATE) and the Integrator water tank (both modes) in PIME_STATE_F64 and
+ * PIME_STATE_MIXED.  PIME_STATE_MIXED16 handles and the tank's Stacking observation are REFUSED (0, and the call returns
+ * PIME_ERR_ARG): the plant is the same there, so identify on a MIXED Integrator handle.
+ * PIME_ERR_ARG before any launch, with a message: E < 1, T < 1, skip < 0 or >= T, NULL action / output / err, state0 on a tank
+ * handle, PREDICT on pH, an unknown mode, a handle that is not served.  pime_env_replay_rows() == PIME_REPLAY_ROWS. */
+enum pime_replay_mode { PIME_REPLAY_SIMULATE = 0, PIME_REPLAY_PREDICT = 1 };
+enum pime_replay_row { PIME_REPLAY_SSE0 = 0, PIME_REPLAY_MAX0 = 1, PIME_REPLAY_SSE1 = 2, PIME_REPLAY_MAX1 = 3, PIME_REPLAY_COUNT = 4,
+                       PIME_REPLAY_ROWS = 5 };
+typedef struct pime_replay_records {
+    const double* action;   /* [dev] float64[E, T] */
+    const double* output;   /* [dev] float64[E, T + 1, C] */
+    const double* state0;   /* [dev] float64[E] (pH) or NULL */
+    int32_t E, T;
+} pime_replay_records;
+int pime_env_replay_channels(const pime_env* env);   /* C: 1 pH, 2 water tank; 0: NULL handle */
+int pime_env_replay_rows(void);
+int pime_env_replay_supported(const pime_env* env, int32_t mode);
+int pime_env_replay_error(pime_env* env, const pime_replay_records* rec, int32_t mode, int32_t skip, double* err, double* sim,
+                          pime_stream stream);
 
 /* -- fused off-policy exploration -----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with

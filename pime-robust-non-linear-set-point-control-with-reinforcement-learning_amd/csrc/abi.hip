@@ -11,6 +11,7 @@
 #include "ppo_train.hpp"
 #include "rollout.hpp"
 #include "rollout_eval.hpp"
+#include "replay_error.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -930,6 +931,44 @@ int pime_rollout_eval_band(pime_env* e, int32_t kind, int32_t md, const float* p
                                      ret, trace, mx, bd, stream))
         return rc;
     return launch_eval_band_reduce(bd, n_steps, stats, static_cast<hipStream_t>(stream));
+}
+
+// ---- fused replay of recorded runs (replay_error.hip) --------------------------------------------------------------------------
+int pime_env_replay_channels(const pime_env* e) { return e ? (e->cfg.kind == PIME_ENV_PH ? 1 : 2) : 0; }
+int pime_env_replay_rows(void) { return PIME_REPLAY_ROWS; }
+
+int pime_env_replay_supported(const pime_env* e, int32_t mode) {
+    if (e == nullptr) return 0;
+    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
+    if (e->cfg.kind == PIME_ENV_PH) return mode == PIME_REPLAY_SIMULATE ? 1 : 0;   // x is not measured: no one-step prediction
+    if (e->cfg.num_stack != 0) return 0;
+    return mode == PIME_REPLAY_SIMULATE || mode == PIME_REPLAY_PREDICT ? 1 : 0;
+}
+
+extern "C++" {
+template <typename S>
+static int replay_error_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, const pime_replay_records* rec, int32_t mode,
+                          int32_t skip, double* err, double* sim, pime_stream stream) {
+    ReplayArgs<S> a{};
+    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
+    a.n = e->cfg.n_envs;
+    if (a.env == 0) { a.p = e->ph; a.table = ph.table; a.A = ph.A; a.B = ph.B; a.C = ph.C; }
+    else { a.wp = e->wt; a.a1 = wt.a1; a.a2 = wt.a2; a.kp = wt.kp; }
+    a.E = rec->E; a.T = rec->T; a.mode = mode; a.skip = skip;
+    return launch_replay_error<S>(a, rec->action, rec->output, rec->state0, err, sim, static_cast<hipStream_t>(stream));
+}
+}
+
+int pime_env_replay_error(pime_env* e, const pime_replay_records* rec, int32_t mode, int32_t skip, double* err, double* sim,
+                          pime_stream stream) {
+    const char* fn = "pime_env_replay_error";
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    if (int rc = check_replay_args(fn, e->cfg.kind == PIME_ENV_PH, rec, mode, skip, err)) return rc;
+    PIME_REQUIRE(pime_env_replay_supported(e, mode), "%s: not served for this handle (PIME_STATE_F64 / PIME_STATE_MIXED, pH or the "
+                 "Integrator water tank: pime_env_replay_supported)", fn);
+    if (int rc = use_device(e)) return rc;
+    if (e->cfg.state_mode == PIME_STATE_F64) return replay_error_t<double>(e, e->ph64, e->wt64, rec, mode, skip, err, sim, stream);
+    return replay_error_t<float>(e, e->ph32, e->wt32, rec, mode, skip, err, sim, stream);
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

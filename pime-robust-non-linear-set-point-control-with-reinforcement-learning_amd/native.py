@@ -16,7 +16,7 @@ LIB_PATH = _override or os.path.join(PACKAGE_DIR, "libpime_hip.so")
 CSRC = os.path.join(PACKAGE_DIR, "csrc")
 
 OK = 0
-ABI_VERSION = 25
+ABI_VERSION = 26
 ENV_PH, ENV_WT = 0, 1
 STATE_F64, STATE_MIXED, STATE_MIXED16 = 0, 1, 2
 REWARD = {"distance": 0, "square_distance": 1, "sparse": 2}
@@ -29,6 +29,10 @@ METRIC_ROWS = len(METRIC_NAMES)
 BAND_SIGNALS = ("y", "e", "action", "reward")
 BAND_STATS = ("sum", "sumsq", "min", "max")
 BAND_ROWS = len(BAND_SIGNALS) * len(BAND_STATS)
+# pime_env_replay_error: modes (enum pime_replay_mode) and the rows of its result (enum pime_replay_row), in order
+REPLAY_MODES = {"simulate": 0, "predict": 1}
+REPLAY_ROW_NAMES = ("sse0", "max0", "sse1", "max1", "count")
+REPLAY_ROWS = len(REPLAY_ROW_NAMES)
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -87,6 +91,10 @@ class SacBatch(C.Structure):
     _fields_ = [("state", C.c_void_p), ("other", C.c_void_p), ("idx", C.c_void_p), ("nxt", C.c_void_p), ("noise_next", C.c_void_p),
                 ("noise_pg", C.c_void_p), ("row", C.c_int64), ("epoch", C.c_void_p), ("B", C.c_int32), ("noise_seed", C.c_uint64),
                 ("noise_epoch", C.c_uint32)]
+
+
+class ReplayRecords(C.Structure):
+    _fields_ = [("action", C.c_void_p), ("output", C.c_void_p), ("state0", C.c_void_p), ("E", C.c_int32), ("T", C.c_int32)]
 
 
 class EnvCfg(C.Structure):
@@ -160,8 +168,12 @@ _SIGNATURES = {
     "pime_rollout_eval_band_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32, _i32]),
     "pime_rollout_eval_band": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _i32, _vp, _vp,
                                          _i32, C.c_double, C.c_double, _vp, _vp]),
+    "pime_env_replay_channels": (C.c_int, [_vp]),
+    "pime_env_replay_rows": (C.c_int, []),
+    "pime_env_replay_supported": (C.c_int, [_vp, _i32]),
+    "pime_env_replay_error": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
-    "pime_rollout_offpolicy": (C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,
+    "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,
                                          _vp, _i32, _i32, _vp]),
     "pime_rollout_offpolicy_sac_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy_sac": (C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _i32,

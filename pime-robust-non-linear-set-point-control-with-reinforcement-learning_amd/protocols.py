@@ -23,13 +23,18 @@ launch, no trace) -- a dense robustness map costs 64 bytes per plant and segment
 minimum and maximum of the controlled output, the error, the action and the reward over the group's plants, and a histogram of
 the output (`band_quantiles` turns it into a percentile fan) -- reduced across lanes on the device while the protocol runs
 (`pime_rollout_eval_band`: one launch, no trace; 128 bytes + 4 bytes per bin leave the device per step and group).
+
+`identify_plants` turns the grid around: instead of scoring a policy on a grid of plants it scores the PLANTS against recorded runs
+(`records_from_physical`: measured data; `records_from_trace`: a fused evaluation's trace, for sim-to-sim studies) -- every (plant,
+record) pair replayed and its output error reduced in one launch (`pime_env_replay_error`) -- and `ensemble_ranges` reads the
+plausible ensemble bounds off the result: the check that the training ensemble brackets the real plant.
 """
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from .native import BAND_SIGNALS, BAND_STATS, ENV_PH, METRIC_NAMES
+from .native import BAND_SIGNALS, BAND_STATS, ENV_PH, METRIC_NAMES, REPLAY_ROW_NAMES
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -215,20 +220,25 @@ def step_response_metrics(env, agent=None, policy=None, setpoints=None, steps=No
     return metrics_from_records(y_after, r, action, reward, y_before[::steps], seg_len=steps, band=band, tail=tail)
 
 
+def _grid(env, axes, who):
+    """(names, axes as an OrderedDict of float64 arrays, shape, plants [n, P] in C order) -- the grid of `robust_grid`."""
+    names = ("qww_V", "qc_V") if env.kind == ENV_PH else ("a1", "a2", "Kp")
+    axes = OrderedDict((k, np.asarray(v, dtype=np.float64).reshape(-1)) for k, v in axes.items())
+    if sorted(axes) != sorted(names):
+        raise ValueError(f"{who}: axes {list(axes)} must name exactly {names}")
+    shape = tuple(len(v) for v in axes.values())
+    if int(np.prod(shape)) != env.num_envs:
+        raise ValueError(f"{who}: the grid has {int(np.prod(shape))} plants, the env {env.num_envs} lanes")
+    mesh = dict(zip(axes, np.meshgrid(*axes.values(), indexing="ij")))
+    return names, axes, shape, np.stack([mesh[k].reshape(-1) for k in names], axis=1)
+
+
 def robust_grid(env, axes, agent=None, policy=None, setpoints=None, steps=None, band=None, tail=10):
     """A dense robustness map: the step-response metrics over the Cartesian product of plant parameters.  axes: ordered mapping
     of plant parameter -> 1-D values (pH: qww_V, qc_V; tank: a1, a2, Kp -- all of them, in any order); env.num_envs must equal the
     product of their lengths; lane = the C-order index into the grid.  Returns (dict of metric name -> float64 [n_segments, *axis
     lengths], axes as an OrderedDict of float64 arrays)."""
-    names = ("qww_V", "qc_V") if env.kind == ENV_PH else ("a1", "a2", "Kp")
-    axes = OrderedDict((k, np.asarray(v, dtype=np.float64).reshape(-1)) for k, v in axes.items())
-    if sorted(axes) != sorted(names):
-        raise ValueError(f"robust_grid: axes {list(axes)} must name exactly {names}")
-    shape = tuple(len(v) for v in axes.values())
-    if int(np.prod(shape)) != env.num_envs:
-        raise ValueError(f"robust_grid: the grid has {int(np.prod(shape))} plants, the env {env.num_envs} lanes")
-    mesh = dict(zip(axes, np.meshgrid(*axes.values(), indexing="ij")))
-    plants = np.stack([mesh[k].reshape(-1) for k in names], axis=1)
+    _, axes, shape, plants = _grid(env, axes, "robust_grid")
     m = step_response_metrics(env, agent=agent, policy=policy, setpoints=setpoints, steps=steps, plants=plants, band=band, tail=tail)
     return {k: v.reshape(v.shape[0], *shape) for k, v in m.items()}, axes
 
@@ -340,3 +350,90 @@ def band_quantiles(hist, edges, q):
             frac = np.where(inside > 0, (target - before) / inside, 0.0)
         out[..., j] = np.where(total > 0, edges[b] + frac * (edges[b + 1] - edges[b]), np.nan)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ plant identification
+def records_from_trace(trace, kind, lanes=None, first=None, y_last=None):
+    """Records for `identify_plants` from the trace of a fused evaluation (`rollout_eval(..., want_trace=True)`, float64
+    [n_steps, 6, N]): every lane in `lanes` (default: all) becomes one record of its env actions and outputs.  kind: ENV_PH / ENV_WT
+    (or "ph" / "wt").  The trace holds the tank's levels AFTER each step and the pH's y BEFORE it, so without more the first step
+    (tank) or the first and last step (pH) only supply the starting row; first -- tank: [2, N] the levels (h1, h2) before step 0 --
+    and y_last -- pH: [N] the output after the last step -- recover them.  pH records carry state0 (x after step 0, from the trace);
+    drop the key to identify with x hidden.  A set-point schedule needs no care: it acts through the recorded action alone."""
+    tr = np.asarray(trace.detach().cpu().numpy() if hasattr(trace, "detach") else trace, dtype=np.float64)
+    lanes = np.arange(tr.shape[2]) if lanes is None else np.asarray(lanes, dtype=np.int64).reshape(-1)
+    if kind in (ENV_PH, "ph"):
+        y = tr[1:, 0][:, lanes]                                  # y before steps 1 .. n-1 = after steps 0 .. n-2
+        action = tr[1:, 3][:, lanes]
+        if y_last is None:
+            action = action[:-1]
+        else:
+            y = np.concatenate([y, np.asarray(y_last, dtype=np.float64).reshape(-1)[lanes][None]])
+        return dict(action=np.ascontiguousarray(action.T), output=np.ascontiguousarray(y.T[:, :, None]),
+                    state0=np.ascontiguousarray(tr[0, 5][lanes]))
+    h = tr[:, 0:2][:, :, lanes]                                  # [n, 2, E]: the levels after each step
+    action = tr[:, 5][:, lanes]
+    if first is None:
+        action = action[1:]
+    else:
+        h = np.concatenate([np.asarray(first, dtype=np.float64).reshape(2, -1)[:, lanes][None], h])
+    return dict(action=np.ascontiguousarray(action.T), output=np.ascontiguousarray(h.transpose(2, 0, 1)))
+
+
+def records_from_physical(u, y, kind):
+    """Records from measured data in physical units.  u [E, T]: the plant input -- the tank's pump signal u = 5 a + 5 (action_P with
+    P_max_action 10), the pH's flow u = 0.75 (a + 1) (the action map onto [0, 1.5]) -- converted back to the env action a; y
+    [E, T + 1, C] (pH: [E, T + 1] will do) the measured outputs, row 0 before the first input, NaN where a sample is missing."""
+    u = np.atleast_2d(np.asarray(u, dtype=np.float64))
+    y = np.asarray(y, dtype=np.float64)
+    if kind in (ENV_PH, "ph"):
+        action = u / 0.75 - 1.0
+        y = y.reshape(u.shape[0], -1, 1)
+    else:
+        action = (u - 5.0) / 5.0
+        y = y.reshape(u.shape[0], -1, 2)
+    if y.shape[1] != u.shape[1] + 1:
+        raise ValueError(f"records_from_physical: {u.shape[1]} inputs need {u.shape[1] + 1} output rows, got {y.shape[1]}")
+    return dict(action=np.ascontiguousarray(action), output=np.ascontiguousarray(y))
+
+
+def identify_plants(env, records, axes, mode="simulate", skip=0, weights=None):
+    """Scores a dense plant grid against recorded runs.  axes: as `robust_grid` (every plant parameter -> 1-D values; env.num_envs =
+    the product of their lengths; lane = the C-order index); records: see `VecControlEnv.replay_error`; mode "simulate" (free run
+    from the first row) or "predict" (tank: every step from the measured state); skip: burn-in steps that are not counted;
+    weights: per output channel the scale its error is divided by (default 1).  The grid is written into the env's lanes and ONE
+    `replay_error` launch replays every (plant, record) pair; the env is not stepped.  Returns a dict:
+      axes, plants [n, P]           the grid
+      cost [*shape]                 sum over records e and channels c of SSE[e, c] / weights[c]^2
+      count [*shape]                the number of measurements that entered it (gaps and the burn-in do not)
+      rmse [*shape]                 sqrt(cost / count)
+      max_error [C, *shape]         per channel the largest |simulated - measured| over all records (unweighted)
+      best_index, best              the C-order lane of the smallest cost and its plant as an OrderedDict name -> value"""
+    names, axes, shape, plants = _grid(env, axes, "identify_plants")
+    if env.kind == ENV_PH:
+        env.set_params(plants[:, 0], plants[:, 1])
+    else:
+        env.reset_changable_parameters(plants[:, 0], plants[:, 1], plants[:, 2])
+    err, _ = env.replay_error(records, mode=mode, skip=skip)
+    err = err.cpu().numpy()
+    row = {name: j for j, name in enumerate(REPLAY_ROW_NAMES)}
+    n_ch = 1 if env.kind == ENV_PH else 2
+    w = np.ones(n_ch) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (n_ch,) or not (w > 0).all():
+        raise ValueError(f"identify_plants: weights must be {n_ch} positive numbers")
+    cost = sum(err[:, row[f"sse{c}"]].sum(axis=0) / w[c] ** 2 for c in range(n_ch))
+    count = err[:, row["count"]].sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rmse = np.sqrt(cost / count)
+    best = int(np.nanargmin(cost))
+    return dict(axes=axes, plants=plants, cost=cost.reshape(shape), count=count.reshape(shape), rmse=rmse.reshape(shape),
+                max_error=np.stack([err[:, row[f"max{c}"]].max(axis=0).reshape(shape) for c in range(n_ch)]),
+                best_index=best, best=OrderedDict((k, float(plants[best, j])) for j, k in enumerate(names)))
+
+
+def ensemble_ranges(result, factor=2.0):
+    """The bounding box, per axis, of the plants of an `identify_plants` result whose rmse is <= factor x the best rmse: the
+    ensemble the records find plausible -- OrderedDict axis name -> (low, high).  The training ranges should contain it."""
+    rmse = np.asarray(result["rmse"], dtype=np.float64)
+    keep = np.argwhere(rmse <= factor * np.nanmin(rmse))
+    return OrderedDict((k, (float(v[keep[:, j]].min()), float(v[keep[:, j]].max()))) for j, (k, v) in enumerate(result["axes"].items()))

@@ -69,6 +69,10 @@ def build_parser():
                    help="vectorised envs: in-kernel Philox or per-env MT19937 streams replayed seed-for-seed")
     p.add_argument("--no_reference_quirks", action="store_true")
     p.add_argument("--log_root", default=None, type=str)
+    p.add_argument("--identify", default=None, type=str, metavar="RECORDS.npz",
+                   help="recorded runs (action [E, T], output [E, T + 1, C], pH: optionally state0 [E]; optionally mode, skip): score a "
+                        "plant grid over the env's ensemble ranges against them and write identified.npz into the run directory")
+    p.add_argument("--identify_points", default=9, type=int, help="--identify: grid points per plant parameter")
     return p
 
 
@@ -167,6 +171,40 @@ def robust_test(args, agent, cwd):
     return path
 
 
+def identify(args, cwd):
+    """--identify RECORDS.npz: the recorded runs of the file replayed over a grid of --identify_points values per plant parameter,
+    spanning the env's registered ensemble ranges, in one launch (protocols.identify_plants).  Writes <cwd>/identified.npz -- the
+    axes, cost / rmse / count / max_error over the grid, the best plant, and the plausible ensemble box at twice the best rmse --
+    and prints the last two.  Training does not read the result: the ranges are passed on by the user as before."""
+    from collections import OrderedDict
+    from . import protocols
+    if "Stacking" in args.env:
+        print("identification skipped: the plant is the Integrator env's; identify there")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    z = np.load(args.identify, allow_pickle=False)
+    records = {k: np.asarray(z[k], dtype=np.float64) for k in ("action", "output", "state0") if k in z.files}
+    mode = str(z["mode"]) if "mode" in z.files else "simulate"
+    skip = int(z["skip"]) if "skip" in z.files else 0
+    n = int(args.identify_points)
+    env = gym_control.make_vec(args.env, n ** (2 if is_ph else 3), device=args.device, state_mode=args.state_dtype, seed=args.seed)
+    ranges = (("qww_V", env.qww_Vrange), ("qc_V", env.qc_Vrange)) if is_ph else \
+        (("a1", env.a1_range), ("a2", env.a2_range), ("Kp", env.Kp_range))
+    axes = OrderedDict((k, np.linspace(lo, hi, n)) for k, (lo, hi) in ranges)
+    res = protocols.identify_plants(env, records, axes, mode=mode, skip=skip)
+    env.close()
+    box = protocols.ensemble_ranges(res, 2.0)
+    path = os.path.join(cwd, "identified.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, axis_names=np.asarray(list(axes)), **{f"axis_{k}": v for k, v in axes.items()}, cost=res["cost"], rmse=res["rmse"],
+             count=res["count"], max_error=res["max_error"], best_index=res["best_index"],
+             best=np.asarray(list(res["best"].values())), ensemble_low=np.asarray([lo for lo, _ in box.values()]),
+             ensemble_high=np.asarray([hi for _, hi in box.values()]), mode=mode, skip=skip)
+    print(f"identified plant: {dict(res['best'])}  rmse {float(np.nanmin(res['rmse'])):.4g}")
+    print(f"plausible ensemble (rmse <= 2 x best): {dict(box)} -> {path}")
+    return path
+
+
 BAND_LANES, BAND_BINS, BAND_QUANTILES = 1024, 128, (0.05, 0.25, 0.5, 0.75, 0.95)
 
 
@@ -217,6 +255,8 @@ def main(argv=None):
         print(f"Finish Training and Saved in {kargs.cwd}")
         if args.robust_test:
             robust_test(args, agent, kargs.cwd)
+        if args.identify:
+            identify(args, kargs.cwd)
     return agent
 
 

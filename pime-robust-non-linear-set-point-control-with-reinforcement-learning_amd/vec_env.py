@@ -514,6 +514,39 @@ class VecControlEnv:
             self._t_lanes += n_steps
         return ret, metrics, stats, counts, trace
 
+    # -- replay of recorded runs (plant identification) ----------------------------------------------------------
+    def replay_supported(self, mode="simulate"):
+        """Does `replay_error` serve this env in this mode?  (pime_env_replay_supported: pH -- simulate only -- and the Integrator
+        tank, float64 or mixed state.)"""
+        return mode in native.REPLAY_MODES and bool(self._lib.pime_env_replay_supported(self._h, native.REPLAY_MODES[mode]))
+
+    def replay_error(self, records, mode="simulate", skip=0, want_sim=False):
+        """Every lane's plant run over every recorded run in ONE launch (pime_env_replay_error, csrc/replay_error.hip), the output
+        error reduced on the device: returns (err float64 [E, 5, N] -- rows native.REPLAY_ROW_NAMES: per output channel the sum of
+        squared errors and the largest absolute error over the steps >= `skip`, and the number of terms -- and sim float64
+        [E, T, C, N], the simulated outputs after each step, or None).  records: dict with "action" [E, T] (the env actions as
+        env.step received them), "output" [E, T + 1, C] (the measured outputs, row 0 before the first step; C = 1 pH, 2 tank; NaN = a
+        gap) and, pH only, optionally "state0" [E] (the hidden x at row 0; without it x0 is derived from the first measurement);
+        host arrays or device tensors.  mode "simulate": free run; "predict" (tank): every step from the measured state.  The env
+        itself is read, never advanced: state, counters and observations are untouched (definitions in include/pime_hip.h)."""
+        if mode not in native.REPLAY_MODES:
+            raise native.PimeError(f"replay_error: unknown mode {mode!r} ({sorted(native.REPLAY_MODES)})")
+        dev = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float64).to(self.device).contiguous()
+        action, output, state0 = dev(records["action"]), dev(records["output"]), dev(records.get("state0"))
+        C_out = int(self._lib.pime_env_replay_channels(self._h))
+        if action.dim() != 2 or output.dim() != 3 or tuple(output.shape) != (action.shape[0], action.shape[1] + 1, C_out):
+            raise native.PimeError(f"replay_error: action {tuple(action.shape)} must be [E, T] and output {tuple(output.shape)} "
+                                   f"[E, T + 1, {C_out}]")
+        E, T = int(action.shape[0]), int(action.shape[1])
+        if state0 is not None and tuple(state0.shape) != (E,):
+            raise native.PimeError(f"replay_error: state0 {tuple(state0.shape)} must be [E]")
+        rec = native.ReplayRecords(action.data_ptr(), output.data_ptr(), None if state0 is None else state0.data_ptr(), E, T)
+        err = torch.empty((E, native.REPLAY_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
+        sim = torch.empty((E, T, C_out, self.num_envs), dtype=torch.float64, device=self.device) if want_sim else None
+        native.check(self._lib.pime_env_replay_error(self._h, C.byref(rec), native.REPLAY_MODES[mode], int(skip), native.ptr(err),
+                                                     native.ptr(sim), self._stream()), "pime_env_replay_error")
+        return err, sim
+
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
         out = np.empty(self.num_envs, dtype=np.float64)
