@@ -28,7 +28,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define PIME_ABI_VERSION 26
+#define PIME_ABI_VERSION 26 /* (still 26 with the prior-gain sweep: pime_prior_sweep* ADD symbols, nothing that was there changes) */
 
 typedef struct pime_env pime_env; /* opaque: SoA env state + titration LUT replica, resident in HBM */
 typedef void* pime_stream;        /* hipStream_t */
@@ -518,6 +518,46 @@ int pime_env_replay_rows(void);
 int pime_env_replay_supported(const pime_env* env, int32_t mode);
 int pime_env_replay_error(pime_env* env, const pime_replay_records* rec, int32_t mode, int32_t skip, double* err, double* sim,
                           pime_stream stream);
+
+/* -- prior-gain sweep (csrc/prior_sweep.hip) ----------------------------------------------------------------------
+ * Which prior gain is best over a whole ensemble of plants, and how bad is it on its worst plant?  ONE call runs every (gain row g,
+ * plant lane i) pair of a [G, D] grid of prior gains over the N lanes of the handle under the prior controller alone, a_env =
+ * sum_j (double)obs[j] * gains[g][j] (ascending j from 0.0), and reduces each pair's step response to the rows of
+ * pime_rollout_eval_metrics and each row ACROSS the plants -- instead of G launches of pime_rollout_eval_metrics(kind = -1), G
+ * metric tables and a host-side reduction.  A pair runs exactly that entry point's loop (set-point boundaries every seg_len steps,
+ * the lane step, the metrics with the same band and tail) on a register copy of lane i as the handle holds it; the process noise
+ * of the water tank is keyed on the plant's global lane (env_offset + i), never on the pair: every gain sees the same disturbance
+ * on a given plant (common random numbers).
+ *   gains    [dev] float64[G, D], D = the observation width (pH 3, tank 4), in the kernels' sign: priorK = -K of the env classes
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   pairs    [dev] float64[n_segments, PIME_METRIC_ROWS, G, N] or NULL: pairs[:, :, g, :] is bit for bit the `metrics` of
+ *            pime_rollout_eval_metrics(kind = -1, priorK = gains[g]) from the same lane state.  NULL is the normal use and does not
+ *            change a bit of summary.
+ *   summary  [dev] float64[G, n_segments, PIME_METRIC_ROWS, PIME_SWEEP_STATS]: each row over the N plants; a value counts if it is
+ *            finite:
+ *     PIME_SWEEP_SUM     the sum of the counted values in this order: plants form blocks of 64 consecutive indices (absent plants
+ *                        and uncounted values contribute +0.0); inside a block the balanced pairwise tree over the index bits (level
+ *                        0 adds elements 2j and 2j + 1, level 1 the results pairwise, .. six levels); the block sums are added
+ *                        sequentially in ascending block order, starting from block 0's sum
+ *     PIME_SWEEP_MIN, PIME_SWEEP_MAX   over the counted values; +inf / -inf if there is none
+ *     PIME_SWEEP_ARGMAX  the plant index of the maximum, as a double; the smallest index on a tie; -1 if no value counts
+ *     PIME_SWEEP_FINITE  the number of counted values
+ *   workspace [dev] pime_prior_sweep_workspace_bytes(env, G, n_steps, seg_len) bytes (-1: bad arguments); private layout, every
+ *            byte read was written by the same call
+ * The handle is READ and never written (state, counters, observations bit-unchanged), but must have been reset.  Asynchronous on
+ * the caller's stream, capturable, no allocation, no synchronisation, no atomics: two calls give the same bits.
+ * Served (pime_prior_sweep_supported == 1): pH and the Integrator water tank in PIME_STATE_F64 and PIME_STATE_MIXED.
+ * PIME_STATE_MIXED16 handles and the tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: G < 1, G * N > 2^31 - 1, NULL gains / summary / workspace,
+ * and the schedule / band / tail cases of pime_rollout_eval_metrics.  pime_prior_sweep_stats() == PIME_SWEEP_STATS. */
+enum pime_sweep_stat { PIME_SWEEP_SUM = 0, PIME_SWEEP_MIN = 1, PIME_SWEEP_MAX = 2, PIME_SWEEP_ARGMAX = 3, PIME_SWEEP_FINITE = 4,
+                       PIME_SWEEP_STATS = 5 };
+int pime_prior_sweep_supported(const pime_env* env);
+int64_t pime_prior_sweep_workspace_bytes(const pime_env* env, int32_t G, int32_t n_steps, int32_t seg_len);
+int pime_prior_sweep_stats(void);
+int pime_prior_sweep(const pime_env* env, const double* gains, int32_t G, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                     int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, void* workspace,
+                     pime_stream stream);
 
 /* -- fused off-policy exploration -----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with

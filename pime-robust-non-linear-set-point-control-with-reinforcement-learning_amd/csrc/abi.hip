@@ -12,6 +12,7 @@
 #include "rollout.hpp"
 #include "rollout_eval.hpp"
 #include "replay_error.hpp"
+#include "prior_sweep.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -969,6 +970,61 @@ int pime_env_replay_error(pime_env* e, const pime_replay_records* rec, int32_t m
     if (int rc = use_device(e)) return rc;
     if (e->cfg.state_mode == PIME_STATE_F64) return replay_error_t<double>(e, e->ph64, e->wt64, rec, mode, skip, err, sim, stream);
     return replay_error_t<float>(e, e->ph32, e->wt32, rec, mode, skip, err, sim, stream);
+}
+
+// ---- prior-gain sweep (prior_sweep.hip) ------------------------------------------------------------------------------------------
+int pime_prior_sweep_stats(void) { return PIME_SWEEP_STATS; }
+
+int pime_prior_sweep_supported(const pime_env* e) {
+    if (e == nullptr) return 0;
+    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
+    return e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0 ? 1 : 0;
+}
+
+int64_t pime_prior_sweep_workspace_bytes(const pime_env* e, int32_t G, int32_t n_steps, int32_t seg_len) {
+    if (!pime_prior_sweep_supported(e) || G < 1 || n_steps < 1 || seg_len < 0 || (long long)G * e->cfg.n_envs > 2147483647LL ||
+        sweep_segments(n_steps, seg_len) > kMaxSetpoints) {
+        set_error("pime_prior_sweep_workspace_bytes: not served, G %d < 1, G x N > 2^31 - 1, n_steps %d < 1, seg_len %d < 0 or more than "
+                  "%d segments", G, n_steps, seg_len, kMaxSetpoints);
+        return -1;
+    }
+    return (int64_t)sweep_workspace_doubles(G, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
+}
+
+extern "C++" {
+template <typename S>
+static int prior_sweep_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, const double* gains, int32_t G, int32_t n_steps,
+                         int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* pairs,
+                         double* summary, void* workspace, pime_stream stream) {
+    SweepArgs<S> a{};
+    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
+    a.n = e->cfg.n_envs; a.G = G;
+    a.n_blocks = (a.n + kSweepBlockPlants - 1) / kSweepBlockPlants;
+    a.n_seg = sweep_segments(n_steps, seg_len);
+    a.env_offset = e->cfg.env_offset;
+    if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
+    else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
+    fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+    return launch_prior_sweep<S>(a, gains, pairs, summary, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
+}
+}
+
+int pime_prior_sweep(const pime_env* e, const double* gains, int32_t G, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                     int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, void* workspace,
+                     pime_stream stream) {
+    const char* fn = "pime_prior_sweep";
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    PIME_REQUIRE(pime_prior_sweep_supported(e), "%s: not served for this handle (PIME_STATE_F64 / PIME_STATE_MIXED, pH or the "
+                 "Integrator water tank: pime_prior_sweep_supported)", fn);
+    if (int rc = check_sweep_args(fn, e->cfg.n_envs, gains, G, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary)) return rc;
+    PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
+    if (int rc = use_device(e)) return rc;
+    if (e->cfg.state_mode == PIME_STATE_F64)
+        return prior_sweep_t<double>(e, e->ph64, e->wt64, gains, G, n_steps, seg_len, setpoints, n_setpoints, band, tail, pairs, summary,
+                                     workspace, stream);
+    return prior_sweep_t<float>(e, e->ph32, e->wt32, gains, G, n_steps, seg_len, setpoints, n_setpoints, band, tail, pairs, summary,
+                                workspace, stream);
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

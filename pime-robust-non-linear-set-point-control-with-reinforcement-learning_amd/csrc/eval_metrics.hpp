@@ -25,7 +25,7 @@ struct SegMetrics {
     int tail_from;   // first step of the steady-state window (wave-uniform)
 
     // y_start: the controlled output before the segment's first step; r: the segment's set-point as the lane state holds it
-    __device__ __forceinline__ void begin(double y_start, double r_, int len_, int tail) {
+    __host__ __device__ __forceinline__ void begin(double y_start, double r_, int len_, int tail) {
         iae = ise = itae = tail_sum = ret = av = 0.0;
         peak = 0.0;                                  // max(0, .): the running maximum starts at the clamp
         r = r_;
@@ -36,7 +36,7 @@ struct SegMetrics {
         tail_from = len_ - (tail < len_ ? tail : len_);
     }
     // step k of the segment: y the controlled output after it, a_env the env action as the trace records it, rew its float32 reward
-    __device__ __forceinline__ void step(int k, double y, double a_env, float rew, double band) {
+    __host__ __device__ __forceinline__ void step(int k, double y, double a_env, float rew, double band) {
         const double e = r - y, ae = fabs(e);
         iae += ae;
         ise += e * e;
@@ -50,7 +50,7 @@ struct SegMetrics {
         a_prev = a_env;
     }
     // one coalesced store per row: lane i of segment seg
-    __device__ __forceinline__ void store(double* out, int seg, int N, int i) const {
+    __host__ __device__ __forceinline__ void store(double* out, int seg, int N, int i) const {
         double* q = out + (size_t)seg * PIME_METRIC_ROWS * N + i;
         q[(size_t)PIME_METRIC_IAE * N] = iae;
         q[(size_t)PIME_METRIC_ISE * N] = ise;

@@ -33,6 +33,8 @@ BAND_ROWS = len(BAND_SIGNALS) * len(BAND_STATS)
 REPLAY_MODES = {"simulate": 0, "predict": 1}
 REPLAY_ROW_NAMES = ("sse0", "max0", "sse1", "max1", "count")
 REPLAY_ROWS = len(REPLAY_ROW_NAMES)
+# pime_prior_sweep: the stats of its summary (enum pime_sweep_stat), in order
+SWEEP_STATS = ("sum", "min", "max", "argmax", "finite")
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -172,6 +174,10 @@ _SIGNATURES = {
     "pime_env_replay_rows": (C.c_int, []),
     "pime_env_replay_supported": (C.c_int, [_vp, _i32]),
     "pime_env_replay_error": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pime_prior_sweep_supported": (C.c_int, [_vp]),
+    "pime_prior_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
+    "pime_prior_sweep_stats": (C.c_int, []),
+    "pime_prior_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,
                                          _vp, _i32, _i32, _vp]),

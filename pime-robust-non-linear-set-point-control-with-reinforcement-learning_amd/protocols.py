@@ -28,13 +28,21 @@ the output (`band_quantiles` turns it into a percentile fan) -- reduced across l
 (`records_from_physical`: measured data; `records_from_trace`: a fused evaluation's trace, for sim-to-sim studies) -- every (plant,
 record) pair replayed and its output error reduced in one launch (`pime_env_replay_error`) -- and `ensemble_ranges` reads the
 plausible ensemble bounds off the result: the check that the training ensemble brackets the real plant.
+
+`tune_prior` asks the question that comes next: which PRIOR GAIN is best over that whole ensemble, and how bad is it on its worst
+plant?  A grid of gains (`gain_box`) x the plants in the env's lanes, every pair's step response reduced to the control indices and
+each index across the plants in one call (`pime_prior_sweep`), a few numbers per gain coming back.
+
+Sign convention.  The env classes hold K with a = -obs @ K (the reference's `get_linear_action`); the kernels take priorK = -env.K
+with a = obs @ priorK.  `tune_prior` and `VecControlEnv.prior_sweep` take and return gains in the KERNELS' sign (priorK);
+`gain_box` scales whatever it is given and keeps its sign; `train.py --prior_K` reads `best_gain` in the ENV's sign (env.K).
 """
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from .native import BAND_SIGNALS, BAND_STATS, ENV_PH, METRIC_NAMES, REPLAY_ROW_NAMES
+from .native import BAND_SIGNALS, BAND_STATS, ENV_PH, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -437,3 +445,58 @@ def ensemble_ranges(result, factor=2.0):
     rmse = np.asarray(result["rmse"], dtype=np.float64)
     keep = np.argwhere(rmse <= factor * np.nanmin(rmse))
     return OrderedDict((k, (float(v[keep[:, j]].min()), float(v[keep[:, j]].max()))) for j, (k, v) in enumerate(result["axes"].items()))
+
+
+# ------------------------------------------------------------------------------------------------ prior-gain sweep
+def gain_box(K, factors):
+    """The Cartesian grid [G, D] of K[j] * factors[j][...] in C order (the last component varies fastest).  K: a gain [D], in either
+    sign -- the grid keeps it: pass -env.K for `tune_prior`.  factors: one list of numbers, applied to every NON-ZERO component of K
+    (a zero component stays zero and adds no axis), or D lists, one per component."""
+    K = np.asarray(K, dtype=np.float64).reshape(-1)
+    scalar = len(factors) > 0 and all(np.ndim(f) == 0 for f in factors)
+    if scalar:
+        f = np.asarray(factors, dtype=np.float64).reshape(-1)
+        per = [f if k != 0.0 else np.ones(1) for k in K]
+    else:
+        per = [np.asarray(f, dtype=np.float64).reshape(-1) for f in factors]
+    if len(per) != K.size or any(f.size < 1 for f in per):
+        raise ValueError(f"gain_box: factors must be one non-empty list of numbers or {K.size} non-empty lists")
+    mesh = np.meshgrid(*[K[j] * per[j] for j in range(K.size)], indexing="ij")
+    return np.ascontiguousarray(np.stack([m.reshape(-1) for m in mesh], axis=1))
+
+
+def tune_prior(env, gains, axes=None, plants=None, setpoints=None, steps=None, band=None, tail=10, cost="itae", robust="worst"):
+    """Robust tuning of the prior controller: the step-response protocol of `env` (as `step_response_metrics`) under a_env = obs @
+    gains[g] for every gain row, over the plants in the env's lanes, in ONE sweep (`VecControlEnv.prior_sweep`).  gains float64
+    [G, D] in the KERNELS' sign (priorK = -env.K; `gain_box(-env.K, factors)`).  axes: a plant grid as `robust_grid` takes it, or
+    plants [N, P]: written into the lanes; neither: every lane keeps the plant its reset draws.  cost: a name of `METRIC_NAMES`;
+    robust "worst": the cost of a gain is the sum over segments of the row's MAXIMUM over the plants, "mean": of its mean over
+    the plants.  A gain with a non-finite value on any plant, segment or row costs +inf.  Returns a dict:
+      gains [G, D], summary [G, n_segments, 8, 5] (stats `SWEEP_STATS`), cost [G]
+      worst_plant int64 [G, n_segments]   the lane with the largest value of the cost row
+      settled_all bool [G]                every plant is inside `band` at the end of every segment
+      best_index, best_gain               the first gain of the smallest cost, in the kernels' sign"""
+    if cost not in METRIC_NAMES or robust not in ("worst", "mean"):
+        raise ValueError(f"tune_prior: cost {cost!r} must be one of {METRIC_NAMES} and robust {robust!r} 'worst' or 'mean'")
+    is_ph = env.kind == ENV_PH
+    if axes is not None:
+        plants = _grid(env, axes, "tune_prior")[3]
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    gains = np.ascontiguousarray(np.asarray(gains, dtype=np.float64).reshape(-1, env.obs_dim))
+    _protocol_start(env, is_ph, steps, plants)
+    summary = env.prior_sweep(gains, len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band, tail=tail).cpu().numpy()
+    st = {name: j for j, name in enumerate(SWEEP_STATS)}
+    row = METRIC_NAMES.index(cost)
+    if robust == "worst":
+        c = summary[:, :, row, st["max"]].sum(axis=1)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = (summary[:, :, row, st["sum"]] / summary[:, :, row, st["finite"]]).sum(axis=1)
+    whole = (summary[:, :, :, st["finite"]] == env.num_envs).all(axis=(1, 2))
+    c = np.where(whole, c, np.inf)
+    settled = whole & (summary[:, :, METRIC_NAMES.index("settling_step"), st["max"]] < steps).all(axis=1)
+    best = int(np.argmin(c))
+    return dict(gains=gains, summary=summary, cost=c, worst_plant=summary[:, :, row, st["argmax"]].astype(np.int64), settled_all=settled,
+                best_index=best, best_gain=gains[best].copy())

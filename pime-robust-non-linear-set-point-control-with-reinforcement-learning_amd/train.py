@@ -73,6 +73,14 @@ def build_parser():
                    help="recorded runs (action [E, T], output [E, T + 1, C], pH: optionally state0 [E]; optionally mode, skip): score a "
                         "plant grid over the env's ensemble ranges against them and write identified.npz into the run directory")
     p.add_argument("--identify_points", default=9, type=int, help="--identify: grid points per plant parameter")
+    p.add_argument("--tune_prior", default=0, type=int, metavar="N",
+                   help="sweep N geometric factors in [0.25, 4] per non-zero component of the env's prior gain K over the plants of "
+                        "--robust_test in one launch and write tuned_prior.npz into the run directory")
+    p.add_argument("--tune_prior_points", default=0, type=int,
+                   help="--tune_prior: instead of the --robust_test plants, a grid of this many points per plant parameter over the "
+                        "env's ensemble ranges")
+    p.add_argument("--prior_K", default=None, type=str, metavar="FILE.npz",
+                   help="train with FILE's best_gain (a tuned_prior.npz of --tune_prior) as the env's prior gain K")
     return p
 
 
@@ -205,6 +213,62 @@ def identify(args, cwd):
     return path
 
 
+def tune_prior(args, cwd):
+    """--tune_prior N: the prior controller alone under every gain of the box K[j] x N geometric factors in [0.25, 4] (per non-zero
+    component of the env's built-in K) on every plant of --robust_test's plant set (or, with --tune_prior_points P, of a P-per-
+    parameter grid over the env's ensemble ranges), the step-response protocol of --robust_test, in one launch
+    (protocols.tune_prior: worst-plant ITAE).  Writes <cwd>/tuned_prior.npz -- gains, cost, worst_plant, settled_all, summary in the
+    kernels' sign (priorK = -K), and best_gain / builtin_K in the ENV's sign (what --prior_K reads) -- and prints the best gain
+    and the cost of the built-in K.  Training does not read the result unless it is passed back with --prior_K."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("prior tuning skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    n = int(args.tune_prior_points)
+    if n > 0:
+        probe = gym_control.make_vec(args.env, 1, device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        ranges = (probe.qww_Vrange, probe.qc_Vrange) if is_ph else (probe.a1_range, probe.a2_range, probe.Kp_range)
+        probe.close()
+        mesh = np.meshgrid(*[np.linspace(lo, hi, n) for lo, hi in ranges], indexing="ij")
+        plants = np.stack([m.reshape(-1) for m in mesh], axis=1)
+    env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+    K = np.asarray(env.K, dtype=np.float64).reshape(-1)
+    factors = np.geomspace(0.25, 4.0, int(args.tune_prior))
+    gains = np.concatenate([protocols.gain_box(-K, list(factors)), -K[None]])   # the last row: the built-in gain itself
+    res = protocols.tune_prior(env, gains, plants=plants, setpoints=setpoints, steps=steps, band=band, tail=tail)
+    env.close()
+    path = os.path.join(cwd, "tuned_prior.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, gains_priorK=res["gains"], cost=res["cost"], worst_plant=res["worst_plant"], settled_all=res["settled_all"],
+             summary=res["summary"], best_index=res["best_index"], best_priorK=res["best_gain"], best_gain=-res["best_gain"],
+             builtin_K=K, builtin_cost=res["cost"][-1], factors=factors, plants=plants,
+             setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, band=band, tail=tail, cost_name="itae", robust="worst")
+    print(f"tuned prior: {len(gains)} gains x {len(plants)} plants -> {path}")
+    print(f"best prior gain K = {(-res['best_gain']).tolist()}  worst-plant ITAE {res['cost'][res['best_index']]:.6g}  "
+          f"(built-in K = {K.tolist()}: {res['cost'][-1]:.6g})")
+    return path
+
+
+def apply_prior_K(env, path):
+    """--prior_K FILE.npz: FILE's best_gain (the env's sign: a = -obs @ K) becomes the env's K -- and that of its clones (the
+    evaluation env of an off-policy run) -- before the residual agent reads it."""
+    K = np.asarray(np.load(path, allow_pickle=False)["best_gain"], dtype=np.float64).reshape(-1)
+    old = np.asarray(env.K, dtype=np.float64).reshape(-1)
+    if K.shape != old.shape or not np.isfinite(K).all():
+        raise ValueError(f"--prior_K: best_gain {K.tolist()} must be {old.size} finite numbers")
+    env.K = K.copy()
+    if "P_control_K" in getattr(env, "_ctor", {}):
+        env._ctor["P_control_K"] = K.copy()
+    print(f"prior gain K = {K.tolist()} from {path} (built-in: {old.tolist()})")
+
+
 BAND_LANES, BAND_BINS, BAND_QUANTILES = 1024, 128, (0.05, 0.25, 0.5, 0.75, 0.95)
 
 
@@ -238,6 +302,8 @@ def main(argv=None):
         torch.cuda.set_device(dp.local_rank)
     print(f"Agent: {args.algo}, Env: {args.env}, Seed: {args.seed}, lanes/GPU: {args.num_envs}")
     env = make_env(args, dp)
+    if args.prior_K:
+        apply_prior_K(env, args.prior_K)
     kargs, _ = prepare_train(args, env)
     kargs.agent.dp = dp
     algo = args.algo.lower()
@@ -257,6 +323,8 @@ def main(argv=None):
             robust_test(args, agent, kargs.cwd)
         if args.identify:
             identify(args, kargs.cwd)
+        if args.tune_prior > 0:
+            tune_prior(args, kargs.cwd)
     return agent
 
 

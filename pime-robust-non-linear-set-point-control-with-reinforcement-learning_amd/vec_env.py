@@ -547,6 +547,42 @@ class VecControlEnv:
                                                      native.ptr(sim), self._stream()), "pime_env_replay_error")
         return err, sim
 
+    # -- prior-gain sweep (robust tuning of the prior controller) --------------------------------------------------
+    def prior_sweep_supported(self):
+        """Does `prior_sweep` serve this env?  (pime_prior_sweep_supported: pH and the Integrator tank, float64 or mixed state,
+        in-kernel draws.)"""
+        return not self.draws.injects and bool(self._lib.pime_prior_sweep_supported(self._h))
+
+    def prior_sweep(self, gains, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_pairs=False):
+        """A grid of prior gains over every lane's plant in ONE call (pime_prior_sweep, csrc/prior_sweep.hip): every (gain row,
+        lane) pair runs `n_steps` steps under the prior controller alone, a_env = obs @ gains[g] -- gains float64 [G, D] in the
+        KERNELS' sign, priorK = -env.K -- from the lane state as it stands, and its step response is reduced to the rows of
+        `rollout_eval_metrics` and each row across the lanes.  Returns summary float64 [G, n_segments, 8, 5] -- per gain, segment
+        and metric row (native.METRIC_NAMES) the stats native.SWEEP_STATS over the lanes: sum, min, max, argmax (the lane of the
+        maximum), finite (the number of finite values, the only ones that count) -- and, with `want_pairs`, (summary, pairs) with
+        pairs float64 [n_segments, 8, G, N], the metrics of every pair.  setpoints / seg_len / band / tail: as
+        `rollout_eval_metrics`.  The tank's process noise is keyed on the lane, so every gain meets the same disturbance on a plant.
+        The env itself is read, never advanced (definitions in include/pime_hip.h)."""
+        g = torch.as_tensor(gains, dtype=torch.float64).to(self.device).contiguous()
+        if g.dim() != 2 or g.shape[1] != self.obs_dim or g.shape[0] < 1:
+            raise native.PimeError(f"prior_sweep: gains {tuple(g.shape)} must be [G >= 1, {self.obs_dim}]")
+        G, n_steps, seg_len = int(g.shape[0]), int(n_steps), int(seg_len)
+        n_seg = max(-(-n_steps // seg_len) if seg_len > 0 else 1, 1)
+        ws_bytes = int(self._lib.pime_prior_sweep_workspace_bytes(self._h, G, n_steps, seg_len))
+        if ws_bytes < 0:
+            raise native.PimeError(f"pime_prior_sweep_workspace_bytes: {native.last_error()}")
+        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        summary = torch.empty((G, n_seg, native.METRIC_ROWS, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
+        pairs = torch.empty((n_seg, native.METRIC_ROWS, G, self.num_envs), dtype=torch.float64, device=self.device) if want_pairs else None
+        # the workspace lives for this call only; it comes from torch's allocator, so under a capture (native.capture_guard around
+        # torch.cuda.graph, as for every capture of this package) it is a block of the graph's private pool and dropping it frees nothing
+        workspace = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+        native.check(self._lib.pime_prior_sweep(
+            self._h, native.ptr(g), G, n_steps, seg_len, native.ptr(sp) if sp.size else None, int(sp.size), float(band), int(tail),
+            native.ptr(pairs), native.ptr(summary), native.ptr(workspace), self._stream()), "pime_prior_sweep")
+        del workspace
+        return (summary, pairs) if want_pairs else summary
+
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
         out = np.empty(self.num_envs, dtype=np.float64)
