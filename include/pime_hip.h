@@ -559,6 +559,48 @@ int pime_prior_sweep(const pime_env* env, const double* gains, int32_t G, int32_
                      int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, void* workspace,
                      pime_stream stream);
 
+/* -- receding-horizon benchmark controller (csrc/mpc_eval.hip) -------------------------------------------------------
+ * How good could ANY controller be on each plant of the handle?  ONE launch runs every lane's plant in closed loop with a non-linear
+ * receding-horizon controller on the plant's own model and reduces its step response to the rows of pime_rollout_eval_metrics. All
+ * controller arithmetic is float64; no product is contracted into a sum.  One plant at one control step:
+ *   CANDIDATES  64 per pass, c = 0 .. 63.  step_0 = 2.0 / 63.0, step_p = step_{p-1} / 32.0.
+ *     pass 0       u_c = clip(-1.0 + (double)c * step_0, -1, 1)
+ *     pass p >= 1  u_c = clip(u* + (double)(c - 32) * step_p, -1, 1), u* the winner of pass p - 1 (candidate 32 is u* itself: a pass
+ *                  never makes the cost worse).  clip(v, lo, hi) = min(max(v, lo), hi).  1 <= passes <= 3.
+ *   MODEL ROLLOUT of candidate c: a register copy of the lane as it stands (the tank's h1, h2 are measured: the model state is the
+ *     true state; pH: the lane's x), the tank's (a1, a2, Kp) replaced by model_plants[i][:] rounded to the state's precision where
+ *     given, stepped `horizon` times (1 .. 64) by the lane step of pime_env_step with the constant action u_c and BOTH process-noise
+ *     normals 0.0, under the set-point the lane holds now (no preview across a segment boundary); the TimeLimit flag is ignored and
+ *     the copy's t, I, last action and reward are discarded.
+ *   COST  J_c = (sum_{k = 1 .. horizon} (y_k - r) * (y_k - r)) + rho * ((u_c - u_prev) * (u_c - u_prev)): the sum sequential in
+ *     ascending k from 0.0; y_k the controlled output after model step k widened to double (tank: h2; pH: the looked-up pH in the
+ *     state's precision -- for float32 state the observation's value); r the lane's set-point widened to double; u_prev the action
+ *     applied at the previous step of the launch (0.0 at its first step; it survives a segment boundary).  rho finite, >= 0.
+ *   CHOICE  the smallest J_c; on a tie the smaller c; a non-finite cost loses to any finite one; if none is finite, c = 0.  The
+ *     winner of the last pass, u*, is the applied action.
+ *   TRUE PLANT  the loop of pime_prior_sweep / pime_rollout_eval_metrics(kind = -1) with a_env = u* in place of obs @ K (no prior
+ *     term): the set-point boundaries every seg_len steps (r set, I and t zeroed, a new episode beyond the first), the tank's process
+ *     noise keyed on the plant's global lane env_offset + i, the same lane step and the same metric definitions -- so a plant's rows
+ *     are directly comparable with those entry points' on the same handle.
+ *   model_plants [dev] float64[N, 3] (a1, a2, Kp) or NULL (every plant on its own model); water tank only
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   metrics  [dev] float64[n_segments, PIME_METRIC_ROWS, N], the layout of pime_rollout_eval_metrics
+ *   actions  [dev] float64[n_steps, N] or NULL: the applied u*          outputs  [dev] float64[n_steps, N] or NULL: y after the step
+ *            NULL is the normal use and does not change a bit of metrics.
+ * One wave per plant, the lane index is the candidate index, the argmin is a six-level xor butterfly under the CHOICE rule (a strict
+ * total order: every lane ends with the same winner).  The handle is READ and never written (state, counters, observations
+ * bit-unchanged), but must have been reset.  Asynchronous on the caller's stream, capturable, no allocation, no synchronisation, no
+ * atomics: two calls give the same bits; a plant's rows do not depend on the other lanes or on N.
+ * Served (pime_mpc_eval_supported == 1): pH and the Integrator water tank in PIME_STATE_F64 and PIME_STATE_MIXED.
+ * PIME_STATE_MIXED16 handles and the tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: a handle that is not served, horizon outside 1 .. 64, passes
+ * outside 1 .. 3, rho negative or not finite, NULL metrics, model_plants on a pH handle (its state x is not measured), and the
+ * schedule / band / tail cases of pime_rollout_eval_metrics. */
+int pime_mpc_eval_supported(const pime_env* env);
+int pime_mpc_eval(const pime_env* env, const double* model_plants, int32_t horizon, int32_t passes, double rho, int32_t n_steps,
+                  int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* metrics,
+                  double* actions, double* outputs, pime_stream stream);
+
 /* -- fused off-policy exploration -----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with
  * AgentTD3.select_action (:300-306: a = (act(s) + N(0, explore_noise)).clamp(-1, 1)), env.step, and ReplayBuffer.append_buffer

@@ -13,6 +13,7 @@
 #include "rollout_eval.hpp"
 #include "replay_error.hpp"
 #include "prior_sweep.hpp"
+#include "mpc_eval.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -1025,6 +1026,48 @@ int pime_prior_sweep(const pime_env* e, const double* gains, int32_t G, int32_t 
                                      workspace, stream);
     return prior_sweep_t<float>(e, e->ph32, e->wt32, gains, G, n_steps, seg_len, setpoints, n_setpoints, band, tail, pairs, summary,
                                 workspace, stream);
+}
+
+// ---- receding-horizon benchmark controller (mpc_eval.hip) ------------------------------------------------------------------------
+int pime_mpc_eval_supported(const pime_env* e) {
+    if (e == nullptr) return 0;
+    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
+    return e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0 ? 1 : 0;
+}
+
+extern "C++" {
+template <typename S>
+static int mpc_eval_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, const double* model_plants, int32_t horizon,
+                      int32_t passes, double rho, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
+                      double band, int32_t tail, double* metrics, double* actions, double* outputs, pime_stream stream) {
+    MpcArgs<S> a{};
+    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
+    a.n = e->cfg.n_envs;
+    a.env_offset = e->cfg.env_offset;
+    if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
+    else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
+    fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+    a.m = MpcConfig{horizon, passes, rho};
+    return launch_mpc_eval<S>(a, model_plants, metrics, actions, outputs, static_cast<hipStream_t>(stream));
+}
+}
+
+int pime_mpc_eval(const pime_env* e, const double* model_plants, int32_t horizon, int32_t passes, double rho, int32_t n_steps,
+                  int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* metrics,
+                  double* actions, double* outputs, pime_stream stream) {
+    const char* fn = "pime_mpc_eval";
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    PIME_REQUIRE(pime_mpc_eval_supported(e), "%s: not served for this handle (PIME_STATE_F64 / PIME_STATE_MIXED, pH or the "
+                 "Integrator water tank: pime_mpc_eval_supported)", fn);
+    if (int rc = check_mpc_args(fn, e->cfg.kind == PIME_ENV_PH, model_plants, horizon, passes, rho, n_steps, seg_len, setpoints,
+                                n_setpoints, band, tail, metrics)) return rc;
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
+    if (int rc = use_device(e)) return rc;
+    if (e->cfg.state_mode == PIME_STATE_F64)
+        return mpc_eval_t<double>(e, e->ph64, e->wt64, model_plants, horizon, passes, rho, n_steps, seg_len, setpoints, n_setpoints, band,
+                                  tail, metrics, actions, outputs, stream);
+    return mpc_eval_t<float>(e, e->ph32, e->wt32, model_plants, horizon, passes, rho, n_steps, seg_len, setpoints, n_setpoints, band,
+                             tail, metrics, actions, outputs, stream);
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

@@ -208,9 +208,15 @@ __host__ __device__ __forceinline__ void wt_lane_noise(const WtParams& p, uint32
             // the 20 Euler sub-steps they perturb.  Same Philox uniforms; the normals differ from the float64 ones by ~1e-6
             // relative, i.e. ~1e-8 of a level after the 0.01 noise scale: far inside the mode's 2e-4.
             const float u1 = (float)(1.0 - ua);                      // in [2^-53, 1]: log finite
+#if defined(__HIP_DEVICE_COMPILE__)
             const float rad = __builtin_amdgcn_sqrtf(-2.0f * __logf(u1)), rev = (float)ub;
             z1n = (double)((float)p.noise_scale * (rad * __builtin_amdgcn_cosf(rev)));
             z2n = (double)((float)p.noise_scale * (rad * __builtin_amdgcn_sinf(rev)));
+#else       // a host build with float32 state (mpc_eval_host.hip, test infrastructure): libm's float32 functions, an ulp or so away
+            const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.2831853071795864769f * (float)ub;
+            z1n = (double)((float)p.noise_scale * (rad * cosf(ang)));
+            z2n = (double)((float)p.noise_scale * (rad * sinf(ang)));
+#endif
         } else {
             const double rad = sqrt(-2.0 * log(1.0 - ua)), ang = 6.283185307179586476925286766559 * ub;
             double sn, cs;
@@ -227,8 +233,13 @@ __host__ __device__ __forceinline__ void wt_lane_noise(const WtParams& p, uint32
 // r02_m_env_pmc.json).  One ulp of a root is a 6e-8 relative perturbation of a smooth map, inside the mode's stated 2e-4.
 template <typename S>
 __host__ __device__ __forceinline__ S tank_sqrt(S v) {
+#if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (sizeof(S) == 4) return __builtin_amdgcn_sqrtf(v);
     else return sqrt(v);
+#else   // host builds: the correctly rounded root in both precisions (float32 state on the host: mpc_eval_host.hip only)
+    if constexpr (sizeof(S) == 4) return sqrtf(v);
+    else return sqrt(v);
+#endif
 }
 
 // One env step for env action `a` (NOT clipped, :258-260); returns done (:816-821)

@@ -500,3 +500,40 @@ def tune_prior(env, gains, axes=None, plants=None, setpoints=None, steps=None, b
     best = int(np.argmin(c))
     return dict(gains=gains, summary=summary, cost=c, worst_plant=summary[:, :, row, st["argmax"]].astype(np.int64), settled_all=settled,
                 best_index=best, best_gain=gains[best].copy())
+
+
+# ------------------------------------------------------------------------------------------------ receding-horizon baseline
+def mpc_baseline(env, plants=None, setpoints=None, steps=None, horizon=20, passes=2, rho=0.0, model=None, band=None, tail=10, trace=False):
+    """How good could ANY controller be on each plant?  The step-response protocol of `env` (as `step_response_metrics`: the same
+    start, set-points, steps, band and tail) under a non-linear receding-horizon controller on the plant's own model
+    (`VecControlEnv.mpc_eval`: 64 constant-action candidates per pass over `horizon` noise-free steps, cost sum (y - r)^2 +
+    rho (u - u_prev)^2), every plant in ONE launch.  plants [N, P]: written into the lanes; None: every lane keeps the plant its
+    reset draws.  model (tank only): None -- every plant is controlled on its own model --, one plant row (a1, a2, Kp) broadcast to
+    all lanes, or [N, 3]: certainty-equivalent control on, e.g., the best plant of `identify_plants`.  Returns the dict of
+    `step_response_metrics` (metric name -> float64 [len(setpoints), N]) and, with `trace`, "actions" / "outputs" [T, N]."""
+    is_ph = env.kind == ENV_PH
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    if model is not None:
+        model = np.asarray(model, dtype=np.float64)
+        if model.shape == (3,):
+            model = np.broadcast_to(model, (env.num_envs, 3))
+        model = np.ascontiguousarray(model)
+    _protocol_start(env, is_ph, steps, plants)
+    out = env.mpc_eval(horizon, passes=passes, rho=rho, model_plants=model, n_steps=len(setpoints) * steps, seg_len=steps,
+                       setpoints=setpoints, band=band, tail=tail, trace=trace)
+    m = (out[0] if trace else out).cpu().numpy()
+    res = {name: np.ascontiguousarray(m[:, j]) for j, name in enumerate(METRIC_NAMES)}
+    if trace:
+        res["actions"], res["outputs"] = out[1].cpu().numpy(), out[2].cpu().numpy()
+    return res
+
+
+def regret(metrics, baseline, name="itae"):
+    """A controller's metric against a baseline's (`mpc_baseline`) on the same plants and segments: (difference, ratio) =
+    (metrics[name] - baseline[name], metrics[name] / baseline[name]), element-wise; the ratio is NaN where the baseline is 0."""
+    a, b = np.asarray(metrics[name], dtype=np.float64), np.asarray(baseline[name], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(b == 0.0, np.nan, a / b)
+    return a - b, ratio

@@ -79,6 +79,12 @@ def build_parser():
     p.add_argument("--tune_prior_points", default=0, type=int,
                    help="--tune_prior: instead of the --robust_test plants, a grid of this many points per plant parameter over the "
                         "env's ensemble ranges")
+    p.add_argument("--mpc_baseline", default=0, type=int, metavar="H",
+                   help="after training: the receding-horizon benchmark controller with horizon H on the plants and protocol of "
+                        "--robust_test in one launch; writes mpc_baseline.npz (and the policy's ITAE regret against it when "
+                        "--robust_test ran) into the run directory (0 = off)")
+    p.add_argument("--mpc_model", default=None, type=str, metavar="FILE.npz",
+                   help="--mpc_baseline (tank only): control every plant on FILE's `best` plant (an identified.npz of --identify)")
     p.add_argument("--prior_K", default=None, type=str, metavar="FILE.npz",
                    help="train with FILE's best_gain (a tuned_prior.npz of --tune_prior) as the env's prior gain K")
     return p
@@ -256,6 +262,52 @@ def tune_prior(args, cwd):
     return path
 
 
+def mpc_baseline(args, cwd, robust_path=None):
+    """--mpc_baseline H: the non-linear receding-horizon controller (protocols.mpc_baseline: horizon H, 2 passes, rho 0) on the plant
+    set and protocol of --robust_test, every plant on its own model -- or, with --mpc_model FILE.npz (tank), on FILE's `best` plant
+    -- in one launch.  Writes <cwd>/mpc_baseline.npz: metrics [n_plants, n_segments, 8] in the row order `metric_names` (the layout
+    of robust_metrics.npz), plants, setpoints, horizon, passes, rho, band, tail, steps, and, when robust_metrics.npz was written in
+    the same run, itae_regret / itae_ratio [n_plants, n_segments] of the policy against it."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("mpc baseline skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    horizon, passes, rho = int(args.mpc_baseline), 2, 0.0
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    model = None
+    if args.mpc_model:
+        if is_ph:
+            raise ValueError("--mpc_model: the pH env's state is not measured; a model plant is served for the tank only")
+        model = np.asarray(np.load(args.mpc_model, allow_pickle=False)["best"], dtype=np.float64).reshape(3)
+    env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+    m = protocols.mpc_baseline(env, plants=plants, setpoints=setpoints, steps=steps, horizon=horizon, passes=passes, rho=rho, model=model,
+                               band=band, tail=tail)
+    env.close()
+    metrics = np.stack([m[name] for name in protocols.METRIC_NAMES], axis=-1).transpose(1, 0, 2)   # [plant, segment, row]
+    extra = {}
+    if robust_path is not None:
+        pol = np.load(robust_path, allow_pickle=False)["metrics"]
+        j = protocols.METRIC_NAMES.index("itae")
+        diff, ratio = protocols.regret({"itae": pol[:, :, j]}, {"itae": metrics[:, :, j]})
+        extra = dict(itae_regret=diff, itae_ratio=ratio)
+        print(f"policy ITAE / MPC ITAE per plant (mean over segments): {np.nanmean(ratio, axis=1).round(3).tolist()}")
+    if model is not None:
+        extra["model"] = model
+    path = os.path.join(cwd, "mpc_baseline.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, metrics=metrics, metric_names=np.asarray(protocols.METRIC_NAMES), plants=plants,
+             setpoints=np.asarray(setpoints, dtype=np.float64), horizon=horizon, passes=passes, rho=rho, band=band, tail=tail, steps=steps,
+             **extra)
+    print(f"mpc baseline: horizon {horizon}, {len(plants)} plants x {len(setpoints)} set-points -> {path}")
+    return path
+
+
 def apply_prior_K(env, path):
     """--prior_K FILE.npz: FILE's best_gain (the env's sign: a = -obs @ K) becomes the env's K -- and that of its clones (the
     evaluation env of an off-policy run) -- before the residual agent reads it."""
@@ -319,12 +371,15 @@ def main(argv=None):
         with open(os.path.join(kargs.cwd, "args.txt"), "w") as f:
             f.write(str(args))
         print(f"Finish Training and Saved in {kargs.cwd}")
+        robust_path = None
         if args.robust_test:
-            robust_test(args, agent, kargs.cwd)
+            robust_path = robust_test(args, agent, kargs.cwd)
         if args.identify:
             identify(args, kargs.cwd)
         if args.tune_prior > 0:
             tune_prior(args, kargs.cwd)
+        if args.mpc_baseline > 0:
+            mpc_baseline(args, kargs.cwd, robust_path)
     return agent
 
 

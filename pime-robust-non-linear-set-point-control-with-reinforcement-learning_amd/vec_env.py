@@ -583,6 +583,39 @@ class VecControlEnv:
         del workspace
         return (summary, pairs) if want_pairs else summary
 
+    # -- receding-horizon benchmark controller ---------------------------------------------------------------------
+    def mpc_supported(self):
+        """Does `mpc_eval` serve this env?  (pime_mpc_eval_supported: pH and the Integrator tank, float64 or mixed state, in-kernel
+        draws.)"""
+        return not self.draws.injects and bool(self._lib.pime_mpc_eval_supported(self._h))
+
+    def mpc_eval(self, horizon, passes=2, rho=0.0, model_plants=None, n_steps=1, seg_len=0, setpoints=None, band=0.05, tail=10,
+                 trace=False):
+        """Every lane's plant in closed loop with a non-linear receding-horizon controller on its own model, in ONE launch
+        (pime_mpc_eval, csrc/mpc_eval.hip): per control step 64 constant-action candidates per pass (`passes` 1 .. 3, each pass 32 x
+        finer around the last winner) are rolled `horizon` (1 .. 64) noise-free lane steps forward, the one with the smallest
+        sum (y - r)^2 + rho (u - u_prev)^2 is applied to the true plant.  model_plants: None (the lane's own plant) or float64 [N, 3]
+        (a1, a2, Kp), tank only: the plant the candidates are rolled on.  Returns metrics float64 [n_segments, 8, N] -- the rows of
+        `rollout_eval_metrics`, comparable with it and with `prior_sweep` on the same lane state -- or, with `trace`, (metrics,
+        actions, outputs), float64 [n_steps, N]: the applied action and the controlled output after each step.  setpoints / seg_len /
+        band / tail: as `rollout_eval_metrics`.  The env itself is read, never advanced (definitions in include/pime_hip.h)."""
+        n_steps, seg_len = int(n_steps), int(seg_len)
+        n_seg = max(-(-n_steps // seg_len) if seg_len > 0 else 1, 1)
+        model = None
+        if model_plants is not None:
+            model = torch.as_tensor(model_plants, dtype=torch.float64).to(self.device).contiguous()
+            if tuple(model.shape) != (self.num_envs, 3):
+                raise native.PimeError(f"mpc_eval: model_plants {tuple(model.shape)} must be [{self.num_envs}, 3]")
+        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        metrics = torch.empty((n_seg, native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
+        actions = torch.empty((max(n_steps, 0), self.num_envs), dtype=torch.float64, device=self.device) if trace else None
+        outputs = torch.empty((max(n_steps, 0), self.num_envs), dtype=torch.float64, device=self.device) if trace else None
+        native.check(self._lib.pime_mpc_eval(
+            self._h, native.ptr(model), int(horizon), int(passes), float(rho), n_steps, seg_len, native.ptr(sp) if sp.size else None,
+            int(sp.size), float(band), int(tail), native.ptr(metrics), native.ptr(actions), native.ptr(outputs), self._stream()),
+            "pime_mpc_eval")
+        return (metrics, actions, outputs) if trace else metrics
+
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
         out = np.empty(self.num_envs, dtype=np.float64)
