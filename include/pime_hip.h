@@ -601,7 +601,58 @@ int pime_mpc_eval(const pime_env* env, const double* model_plants, int32_t horiz
                   int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* metrics,
                   double* actions, double* outputs, pime_stream stream);
 
-/* -- fused off-policy exploration -----------------------------------------------------------------------------------
+/* -- loop-perturbation sweep (csrc/margin_sweep.hip) ----------------------------------------------------------------
+ * How much dead time, how much loop-gain error and how much sensor noise does the closed loop tolerate -- under the residual policy
+ * and under the prior controller alone?  The entry points above perturb the PLANT and leave the LOOP ideal; this one perturbs the
+ * loop.  ONE call runs every (perturbation row p, plant lane i) pair of a [P, 3] grid `perturb` -- a row is (g, d, sigma), columns
+ * enum pime_perturb_col -- over the N lanes of the handle.  A pair runs the loop of pime_rollout_eval_metrics (set-point boundaries
+ * every seg_len steps, the lane step, the metrics with the same band and tail) on a register copy of lane i as the handle holds it,
+ * with three things inserted at launch step t:
+ *   MEASUREMENT  obs_m = obs, except for the measured plant outputs -- pH column 0 (y), tank columns 0 and 1 (h1, h2) -- where
+ *     obs_m[j] = obs[j] + (float)sigma * n_j in float32.  (n_0, n_1) is the Box-Muller pair of philox_pair(noise_seed, env_offset + i,
+ *     noise_epoch, t, stream 3): radius sqrt(-2 log(1 - ua)), angle 2 pi ub, the cosine branch for column 0 and the sine branch for
+ *     column 1, computed in double and rounded to float32.  The key is the plant, never the pair: every row meets the same noise
+ *     sequence, scaled (common random numbers, as the tank's process noise in pime_prior_sweep).  sigma == 0: the observation is used
+ *     as it is and nothing is drawn.  The set-point column and the integrator column are the ENV'S OWN: the env integrates the true
+ *     error and the controller reads that integral unperturbed (a controller-side integrator of the measured error is not modelled).
+ *   CONTROLLER  a_c = tanh(mean(obs_m)) + obs_m @ priorK as pime_rollout_eval forms it (the prior term in double, ascending j from
+ *     0.0); kind = -1: the prior controller alone.
+ *   ACTUATOR  a_env(t) = g * a_c(t - d), a_c(s) = 0.0 for s < 0: a delay line of PIME_MARGIN_MAX_DELAY doubles, NOT cleared at a
+ *     segment boundary (the actuator knows nothing of set-points).  d = rint(perturb[p][1]) clamped into 0 .. PIME_MARGIN_MAX_DELAY
+ *     (NaN: 0).  The metrics' action row and `actions` hold the APPLIED a_env.
+ * With (g, d, sigma) = (1, 0, 0) a pair is bit for bit a lane of pime_rollout_eval_metrics from the same lane state.
+ *   kind, md, packed_actor, priorK: as pime_rollout_eval (priorK [host] float64[D])
+ *   perturb  [dev] float64[P, PIME_PERTURB_COLS]
+ *   noise_seed, noise_epoch: the key of the measurement noise
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   pairs    [dev] float64[n_segments, PIME_METRIC_ROWS, P, N] or NULL
+ *   summary  [dev] float64[P, n_segments, PIME_METRIC_ROWS, PIME_SWEEP_STATS]: each row over the N plants, EXACTLY the statistics and
+ *            the addition order of pime_prior_sweep's summary (blocks of 64 plants, the pairwise tree, the blocks in sequence, the
+ *            smaller index on a tie)
+ *   actions  [dev] float64[n_steps, P, N] or NULL: the applied a_env     outputs  [dev] float64[n_steps, P, N] or NULL: y after the step
+ *            NULL pairs / actions / outputs is the normal use and does not change a bit of summary.
+ *   workspace [dev] pime_margin_sweep_workspace_bytes(env, P, n_steps, seg_len) bytes (-1: bad arguments); private layout, every byte
+ *            read was written by the same call
+ * Persistent 256-thread workgroups stage the actor's image into LDS once and walk quads of 16-lane tiles (one tile of ONE row per
+ * wave: g, d and sigma are wave-uniform; the prior alone runs 64 distinct pairs per wave); a finishing launch reduces the rows per
+ * perturbation.  The handle is READ and never written (state, counters, observations bit-unchanged), but must have been reset.
+ * Asynchronous on the caller's stream, capturable, no allocation, no synchronisation, no floating-point atomics: two calls give the
+ * same bits; a pair's result does not depend on P, N or its position in the grid.
+ * Served (pime_margin_sweep_supported == 1): pH and the Integrator water tank in PIME_STATE_F64 and PIME_STATE_MIXED, kind = -1 or one
+ * of the four policy kinds of pime_rollout_eval at width 64 or 128.  Width 256 (the streamed family), PIME_STATE_MIXED16 handles and
+ * the tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: the refused classes, P < 1, P * N > 2^31 - 1, NULL perturb /
+ * summary / workspace / priorK (and packed_actor with a policy), and the schedule / band / tail cases of pime_rollout_eval_metrics. */
+enum pime_perturb_col { PIME_PERTURB_GAIN = 0, PIME_PERTURB_DELAY = 1, PIME_PERTURB_SIGMA = 2, PIME_PERTURB_COLS = 3 };
+enum { PIME_MARGIN_MAX_DELAY = 8 };
+int pime_margin_sweep_supported(const pime_env* env, int32_t kind, int32_t md);
+int64_t pime_margin_sweep_workspace_bytes(const pime_env* env, int32_t P, int32_t n_steps, int32_t seg_len);
+int pime_margin_sweep(const pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                      const double* perturb, int32_t P, uint64_t noise_seed, uint32_t noise_epoch, int32_t n_steps, int32_t seg_len,
+                      const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary,
+                      double* actions, double* outputs, void* workspace, pime_stream stream);
+
+/* -- fused off-policy exploration-----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with
  * AgentTD3.select_action (:300-306: a = (act(s) + N(0, explore_noise)).clamp(-1, 1)), env.step, and ReplayBuffer.append_buffer
  * (replay.py:290-300) -- as ONE launch for n_steps lock-steps of every lane: deterministic actor forward on the matrix cores,

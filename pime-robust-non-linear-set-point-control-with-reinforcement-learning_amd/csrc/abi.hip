@@ -14,6 +14,7 @@
 #include "replay_error.hpp"
 #include "prior_sweep.hpp"
 #include "mpc_eval.hpp"
+#include "margin_sweep.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -1068,6 +1069,75 @@ int pime_mpc_eval(const pime_env* e, const double* model_plants, int32_t horizon
                                   tail, metrics, actions, outputs, stream);
     return mpc_eval_t<float>(e, e->ph32, e->wt32, model_plants, horizon, passes, rho, n_steps, seg_len, setpoints, n_setpoints, band,
                              tail, metrics, actions, outputs, stream);
+}
+
+// ---- loop-perturbation sweep (margin_sweep.hip) ----------------------------------------------------------------------------------
+int pime_margin_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
+    if (e == nullptr) return 0;
+    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
+    if (e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0) return 0;
+    if (kind == -1) return 1;                                            // the prior controller alone
+    if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR && kind != PIME_MLP_CRITIC) return 0;
+    return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;       // (width 256, the streamed family: not served)
+}
+
+int64_t pime_margin_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    if (!pime_margin_sweep_supported(e, -1, 0) || P < 1 || n_steps < 1 || seg_len < 0 || (long long)P * e->cfg.n_envs > 2147483647LL ||
+        sweep_segments(n_steps, seg_len) > kMaxSetpoints) {
+        set_error("pime_margin_sweep_workspace_bytes: not served, P %d < 1, P x N > 2^31 - 1, n_steps %d < 1, seg_len %d < 0 or more than "
+                  "%d segments", P, n_steps, seg_len, kMaxSetpoints);
+        return -1;
+    }
+    return (int64_t)margin_workspace_doubles(P, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
+}
+
+extern "C++" {
+template <typename S>
+static int margin_sweep_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, int32_t kind, int32_t md, const float* packed_actor,
+                          const double* priorK, const double* perturb, int32_t P, uint64_t noise_seed, uint32_t noise_epoch,
+                          int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail,
+                          double* pairs, double* summary, double* actions, double* outputs, void* workspace, pime_stream stream) {
+    MarginArgs<S> a{};
+    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
+    a.n = e->cfg.n_envs; a.P = P;
+    a.n_seg = sweep_segments(n_steps, seg_len);
+    a.env_offset = e->cfg.env_offset;
+    if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
+    else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
+    a.img = packed_actor;
+    for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
+    a.nz = MarginNoise{noise_seed, noise_epoch};
+    fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+    return launch_margin_sweep<S>(kind, md, a, perturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
+                                  static_cast<hipStream_t>(stream));
+}
+}
+
+int pime_margin_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                      const double* perturb, int32_t P, uint64_t noise_seed, uint32_t noise_epoch, int32_t n_steps, int32_t seg_len,
+                      const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary,
+                      double* actions, double* outputs, void* workspace, pime_stream stream) {
+    const char* fn = "pime_margin_sweep";
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    PIME_REQUIRE(e->cfg.state_mode == PIME_STATE_F64 || e->cfg.state_mode == PIME_STATE_MIXED,
+                 "%s: state_mode %d is not served (PIME_STATE_F64 or PIME_STATE_MIXED; PIME_STATE_MIXED16 is refused)", fn,
+                 (int)e->cfg.state_mode);
+    PIME_REQUIRE(e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0,
+                 "%s: the Stacking observation (num_stack %d) is not served (pH or the Integrator water tank)", fn, (int)e->cfg.num_stack);
+    PIME_REQUIRE(kind == -1 || md != 256, "%s: md %d is not served (64 or 128; width 256 is the streamed family)", fn, md);
+    PIME_REQUIRE(pime_margin_sweep_supported(e, kind, md), "%s: not served for actor kind %d width md %d (pime_margin_sweep_supported)",
+                 fn, kind, md);
+    if (int rc = check_margin_args(fn, e->cfg.n_envs, priorK, perturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary))
+        return rc;
+    PIME_REQUIRE(kind == -1 || packed_actor != nullptr, "%s: packed_actor is NULL", fn);
+    PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
+    if (int rc = use_device(e)) return rc;
+    if (e->cfg.state_mode == PIME_STATE_F64)
+        return margin_sweep_t<double>(e, e->ph64, e->wt64, kind, md, packed_actor, priorK, perturb, P, noise_seed, noise_epoch, n_steps,
+                                      seg_len, setpoints, n_setpoints, band, tail, pairs, summary, actions, outputs, workspace, stream);
+    return margin_sweep_t<float>(e, e->ph32, e->wt32, kind, md, packed_actor, priorK, perturb, P, noise_seed, noise_epoch, n_steps,
+                                 seg_len, setpoints, n_setpoints, band, tail, pairs, summary, actions, outputs, workspace, stream);
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

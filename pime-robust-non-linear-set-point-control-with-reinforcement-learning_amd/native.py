@@ -35,6 +35,10 @@ REPLAY_ROW_NAMES = ("sse0", "max0", "sse1", "max1", "count")
 REPLAY_ROWS = len(REPLAY_ROW_NAMES)
 # pime_prior_sweep: the stats of its summary (enum pime_sweep_stat), in order
 SWEEP_STATS = ("sum", "min", "max", "argmax", "finite")
+# pime_margin_sweep: the columns of a perturbation row (enum pime_perturb_col), in order, and the longest dead time it serves
+PERTURB_NAMES = ("gain", "delay", "sigma")
+PERTURB_COLS = len(PERTURB_NAMES)
+MARGIN_MAX_DELAY = 8
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -179,6 +183,10 @@ _SIGNATURES = {
     "pime_prior_sweep_stats": (C.c_int, []),
     "pime_prior_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_mpc_eval_supported": (C.c_int, [_vp]),
+    "pime_margin_sweep_supported": (C.c_int, [_vp, _i32, _i32]),
+    "pime_margin_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
+    "pime_margin_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.c_uint64, C.c_uint32, _i32, _i32, _vp, _i32, C.c_double,
+                                    _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pime_mpc_eval": (C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,

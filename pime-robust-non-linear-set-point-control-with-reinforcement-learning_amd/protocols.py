@@ -537,3 +537,108 @@ def regret(metrics, baseline, name="itae"):
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = np.where(b == 0.0, np.nan, a / b)
     return a - b, ratio
+
+
+# ------------------------------------------------------------------------------------------------ loop margins
+def perturbation_grid(gains=(1.,), delays=(0,), sigmas=(0.,)):
+    """The rows of `loop_sweep` / `VecControlEnv.margin_sweep` for every combination of loop gains, dead times (sample periods) and
+    sensor-noise scales: float64 [P, 3], columns (gain, delay, sigma), in C order -- the gain outermost, sigma innermost."""
+    g, d, s = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (gains, delays, sigmas))
+    if g.size < 1 or d.size < 1 or s.size < 1:
+        raise ValueError("perturbation_grid: every axis needs at least one value")
+    mesh = np.meshgrid(g, d, s, indexing="ij")
+    return np.ascontiguousarray(np.stack([m.reshape(-1) for m in mesh], axis=1))
+
+
+def loop_sweep(env, perturb, agent=None, axes=None, plants=None, setpoints=None, steps=None, band=None, tail=10, seed=0, want_pairs=False):
+    """How much dead time, loop-gain error and sensor noise does the closed loop tolerate?  The step-response protocol of `env` (as
+    `step_response_metrics`: the same start, set-points, steps, band and tail) under every row (gain, delay, sigma) of `perturb`
+    [P, 3] (`perturbation_grid`), over the plants in the env's lanes, in ONE call (`VecControlEnv.margin_sweep`): the plant receives
+    gain x the controller's output of `delay` steps ago, the controller reads the plant outputs plus sigma x a standard normal keyed
+    on the lane (every row meets the same noise sequence; `seed` keys it).  agent None: the prior controller alone, else an agent the
+    fused evaluation serves.  axes: a plant grid as `robust_grid` takes it, or plants [N, P]: written into the lanes; neither: every
+    lane keeps the plant its reset draws.  Returns a dict for `loop_margins`: perturb [P, 3], summary [P, n_segments, 8, 5] (stats
+    `SWEEP_STATS`), pairs [n_segments, 8, P, N] or None, steps, setpoints, band, tail, n (the plants)."""
+    from .vec_env import check_perturb
+    is_ph = env.kind == ENV_PH
+    rows = check_perturb(perturb)
+    if axes is not None:
+        plants = _grid(env, axes, "loop_sweep")[3]
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    fused = _fused_policy(env, None, agent)
+    if fused is None or not hasattr(env, "margin_supported") or not env.margin_supported(fused[0]):
+        raise ValueError("loop_sweep: the loop-perturbation sweep does not serve this env / agent (VecControlEnv.margin_supported)")
+    _protocol_start(env, is_ph, steps, plants)
+    out = env.margin_sweep(fused[0], fused[1], rows, len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band, tail=tail,
+                           noise_seed=seed, want_pairs=want_pairs)
+    summary, pairs = (out["summary"], out["pairs"]) if want_pairs else (out, None)
+    return dict(perturb=rows, summary=summary.cpu().numpy(), pairs=None if pairs is None else pairs.cpu().numpy(), steps=int(steps),
+                setpoints=setpoints, band=band, tail=tail, n=int(env.num_envs))
+
+
+def _last_ok(values, ok):
+    """values ascending away from the nominal one (first): the last value before the first failure; NaN if the nominal row fails."""
+    last = np.nan
+    for v, good in zip(values, ok):
+        if not good:
+            break
+        last = v
+    return float(last)
+
+
+def loop_margins(result, cost="itae", factor=2.0):
+    """Margins from a `loop_sweep` result.  A row is ACCEPTABLE when every plant settles in every segment (the settling step's
+    maximum < the segment's length, every value finite) and the worst-plant `cost` (a name of `METRIC_NAMES`; summed over the
+    segments) stays <= factor x its value on the nominal row (1, 0, 0), which the grid must hold.  Along each perturbation axis, the
+    other two columns nominal, the margin is the LAST value, walking away from the nominal one, up to which every row is acceptable
+    (NaN: the nominal row itself is not).  Returns a dict: nominal (row index), acceptable bool [P], cost [P], delay_margin,
+    gain_margin (upwards from 1), gain_margin_low (downwards), sigma_margin, sigma_slope (the least-squares slope of the plant-mean
+    action variation, summed over the segments, against sigma; NaN with fewer than two sigma rows) and, when the result holds
+    `pairs`, the same per plant: plant_delay_margin, plant_gain_margin, plant_gain_margin_low, plant_sigma_margin, each [N]."""
+    if cost not in METRIC_NAMES:
+        raise ValueError(f"loop_margins: cost {cost!r} must be one of {METRIC_NAMES}")
+    rows, summary = np.asarray(result["perturb"], dtype=np.float64), np.asarray(result["summary"], dtype=np.float64)
+    P, S = summary.shape[0], summary.shape[1]
+    N, steps = int(result["n"]), int(result["steps"])
+    g, d, sg = rows[:, 0], rows[:, 1], rows[:, 2]
+    nominal = np.flatnonzero((g == 1.0) & (d == 0.0) & (sg == 0.0))
+    if nominal.size < 1:
+        raise ValueError("loop_margins: the grid holds no nominal row (gain 1, delay 0, sigma 0)")
+    nom = int(nominal[0])
+    st = {name: j for j, name in enumerate(SWEEP_STATS)}
+    row, settle, av = METRIC_NAMES.index(cost), METRIC_NAMES.index("settling_step"), METRIC_NAMES.index("action_variation")
+    seg_steps = np.full(S, steps, dtype=np.float64)   # (loop_sweep runs whole segments)
+    whole = (summary[:, :, :, st["finite"]] == N).all(axis=(1, 2))
+    settled = (summary[:, :, settle, st["max"]] < seg_steps[None, :]).all(axis=1)
+    c = summary[:, :, row, st["max"]].sum(axis=1)
+    with np.errstate(invalid="ignore"):
+        ok = whole & settled & (c <= factor * c[nom])
+    axes = {"delay": ((g == 1.0) & (sg == 0.0), d, +1), "gain": ((d == 0.0) & (sg == 0.0) & (g >= 1.0), g, +1),
+            "gain_low": ((d == 0.0) & (sg == 0.0) & (g <= 1.0), g, -1), "sigma": ((g == 1.0) & (d == 0.0), sg, +1)}
+    out = dict(nominal=nom, acceptable=ok, cost=c)
+    order = {}
+    for name, (mask, vals, sign) in axes.items():
+        idx = np.flatnonzero(mask)
+        idx = idx[np.argsort(sign * vals[idx], kind="stable")]
+        order[name] = idx
+        out[name + "_margin" if name != "gain_low" else "gain_margin_low"] = _last_ok(vals[idx], ok[idx])
+    idx = order["sigma"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean_av = (summary[:, :, av, st["sum"]] / summary[:, :, av, st["finite"]]).sum(axis=1)
+    fit = np.isfinite(mean_av[idx])
+    out["sigma_slope"] = float(np.polyfit(sg[idx][fit], mean_av[idx][fit], 1)[0]) if np.unique(sg[idx][fit]).size >= 2 else float("nan")
+    pairs = result.get("pairs")
+    if pairs is not None:
+        pairs = np.asarray(pairs, dtype=np.float64)                      # [S, 8, P, N]
+        finite = np.isfinite(pairs).all(axis=(0, 1))                     # [P, N]
+        settled_p = (pairs[:, settle] < seg_steps[:, None, None]).all(axis=0)
+        cp = pairs[:, row].sum(axis=0)
+        with np.errstate(invalid="ignore"):
+            ok_p = finite & settled_p & (cp <= factor * cp[nom][None, :])
+        for name, (mask, vals, sign) in axes.items():
+            idx = order[name]
+            key = "plant_" + (name + "_margin" if name != "gain_low" else "gain_margin_low")
+            out[key] = np.array([_last_ok(vals[idx], ok_p[idx, i]) for i in range(ok_p.shape[1])])
+    return out

@@ -83,6 +83,12 @@ def build_parser():
                    help="after training: the receding-horizon benchmark controller with horizon H on the plants and protocol of "
                         "--robust_test in one launch; writes mpc_baseline.npz (and the policy's ITAE regret against it when "
                         "--robust_test ran) into the run directory (0 = off)")
+    p.add_argument("--margins", action="store_true",
+                   help="after training: sweep dead time, loop gain and sensor noise of the closed loop (trained agent AND prior alone) "
+                        "on the plants of --robust_test, one launch each; writes margins.npz into the run directory")
+    p.add_argument("--margins_points", default=0, type=int,
+                   help="--margins: instead of the --robust_test plants, a grid of this many points per plant parameter over the "
+                        "env's ensemble ranges")
     p.add_argument("--mpc_model", default=None, type=str, metavar="FILE.npz",
                    help="--mpc_baseline (tank only): control every plant on FILE's `best` plant (an identified.npz of --identify)")
     p.add_argument("--prior_K", default=None, type=str, metavar="FILE.npz",
@@ -308,6 +314,66 @@ def mpc_baseline(args, cwd, robust_path=None):
     return path
 
 
+MARGIN_DELAYS = tuple(range(9))
+MARGIN_GAINS = (0.25, 0.35, 0.5, 0.7, 1.4, 2.0, 2.8, 4.0)
+MARGIN_SIGMAS = (0.01, 0.02, 0.05, 0.1)
+
+
+def margins(args, agent, cwd):
+    """--margins: dead time (0 .. 8 sample periods), loop gain (0.25 .. 4) and sensor noise (sigma up to 0.1) swept one axis at a time
+    around the nominal loop, on every plant of --robust_test's plant set (or, with --margins_points P, of a P-per-parameter grid over
+    the env's ensemble ranges), the step-response protocol of --robust_test, one launch for the trained agent and one for the prior
+    controller alone (protocols.loop_sweep / loop_margins: every plant settles and the worst-plant ITAE stays within twice its
+    nominal value).  Writes <cwd>/margins.npz -- perturb, plants, and per controller (prefix agent_ / prior_) summary, acceptable,
+    cost, the four margins, sigma_slope and the per-plant margins -- and prints both delay margins side by side."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("margins skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    n = int(args.margins_points)
+    if n > 0:
+        probe = gym_control.make_vec(args.env, 1, device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        ranges = (probe.qww_Vrange, probe.qc_Vrange) if is_ph else (probe.a1_range, probe.a2_range, probe.Kp_range)
+        probe.close()
+        mesh = np.meshgrid(*[np.linspace(lo, hi, n) for lo, hi in ranges], indexing="ij")
+        plants = np.stack([m.reshape(-1) for m in mesh], axis=1)
+    grid = np.concatenate([protocols.perturbation_grid(delays=MARGIN_DELAYS), protocols.perturbation_grid(gains=MARGIN_GAINS),
+                           protocols.perturbation_grid(sigmas=MARGIN_SIGMAS)])
+    out, found = {}, {}
+    for who, ag in (("agent", agent), ("prior", None)):
+        env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        fused = protocols._fused_policy(env, None, ag)
+        if fused is None or not hasattr(env, "margin_supported") or not env.margin_supported(fused[0]):
+            env.close()
+            print(f"margins skipped for the {who}: the loop-perturbation sweep does not serve this env / actor (margin_supported)")
+            continue
+        res = protocols.loop_sweep(env, grid, agent=ag, plants=plants, setpoints=setpoints, steps=steps, band=band, tail=tail,
+                                   seed=args.seed, want_pairs=True)
+        env.close()
+        m = protocols.loop_margins(res)
+        found[who] = m
+        out[f"{who}_summary"] = res["summary"]
+        for k, v in m.items():
+            out[f"{who}_{k}"] = np.asarray(v)
+    if not found:
+        return None
+    path = os.path.join(cwd, "margins.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, perturb=grid, plants=plants, setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, band=band, tail=tail,
+             cost_name="itae", factor=2.0, metric_names=np.asarray(protocols.METRIC_NAMES), **out)
+    side = "  ".join(f"{who} {found[who]['delay_margin']:g}" for who in ("agent", "prior") if who in found)
+    print(f"margins: {len(grid)} loop perturbations x {len(plants)} plants -> {path}")
+    print(f"delay margin (sample periods, every plant settles and worst-plant ITAE <= 2 x nominal): {side}")
+    return path
+
+
 def apply_prior_K(env, path):
     """--prior_K FILE.npz: FILE's best_gain (the env's sign: a = -obs @ K) becomes the env's K -- and that of its clones (the
     evaluation env of an off-policy run) -- before the residual agent reads it."""
@@ -380,6 +446,8 @@ def main(argv=None):
             tune_prior(args, kargs.cwd)
         if args.mpc_baseline > 0:
             mpc_baseline(args, kargs.cwd, robust_path)
+        if args.margins:
+            margins(args, agent, kargs.cwd)
     return agent
 
 

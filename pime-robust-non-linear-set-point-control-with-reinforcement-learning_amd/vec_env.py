@@ -99,6 +99,22 @@ class CallbackDraws:
 
 # ------------------------------------------------------------------------------------------------ base class
 # image kinds the fused evaluation kernels take as a policy ("critic": the TD3 Actor, whose image has CriticAdv's shape and ReLUs)
+def check_perturb(perturb):
+    """The rows of `VecControlEnv.margin_sweep` as float64 [P, 3], or ValueError: the shape, a non-finite gain, a delay that is not an
+    integer in 0 .. native.MARGIN_MAX_DELAY, a sigma that is negative or not finite."""
+    rows = np.asarray(perturb.detach().cpu().numpy() if torch.is_tensor(perturb) else perturb, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != native.PERTURB_COLS or rows.shape[0] < 1:
+        raise ValueError(f"margin_sweep: perturb {tuple(rows.shape)} must be [P >= 1, {native.PERTURB_COLS}]")
+    g, d, sg = rows[:, 0], rows[:, 1], rows[:, 2]
+    if not np.all(np.isfinite(g)):
+        raise ValueError("margin_sweep: a gain is not finite")
+    if not np.all(np.isfinite(d)) or np.any(d != np.rint(d)) or np.any(d < 0) or np.any(d > native.MARGIN_MAX_DELAY):
+        raise ValueError(f"margin_sweep: a delay is not an integer in 0 .. {native.MARGIN_MAX_DELAY}")
+    if not np.all(np.isfinite(sg)) or np.any(sg < 0):
+        raise ValueError("margin_sweep: a sigma is negative or not finite")
+    return np.ascontiguousarray(rows)
+
+
 _EVAL_KINDS = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR, "sac_actor": native.MLP_SAC_ACTOR,
                "critic": native.MLP_CRITIC}
 
@@ -615,6 +631,70 @@ class VecControlEnv:
             int(sp.size), float(band), int(tail), native.ptr(metrics), native.ptr(actions), native.ptr(outputs), self._stream()),
             "pime_mpc_eval")
         return (metrics, actions, outputs) if trace else metrics
+
+    # -- loop-perturbation sweep (delay, gain and sensor-noise margins) ---------------------------------------------
+    def margin_supported(self, packed_actor=None):
+        """Does `margin_sweep` serve this env (with this packed actor, or the prior controller alone)?
+        (pime_margin_sweep_supported: pH and the Integrator tank, float64 or mixed state, in-kernel draws; actor widths 64 / 128.)"""
+        if self.draws.injects:
+            return False
+        if packed_actor is None:
+            return bool(self._lib.pime_margin_sweep_supported(self._h, -1, 0))
+        if packed_actor.kind not in _EVAL_KINDS or packed_actor.D != self.obs_dim:
+            return False
+        return bool(self._lib.pime_margin_sweep_supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
+
+    def margin_sweep(self, packed_actor, priorK, perturb, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, noise_seed=0,
+                     noise_epoch=0, want_pairs=False, want_trace=False):
+        """A grid of LOOP perturbations over every lane's plant in ONE call (pime_margin_sweep, csrc/margin_sweep.hip): every
+        (perturbation row, lane) pair runs the loop of `rollout_eval_metrics` from the lane state as it stands with the row's
+        (gain g, dead time d in sample periods, sensor-noise scale sigma) -- perturb float64 [P, 3], columns native.PERTURB_NAMES:
+        the controller reads the plant outputs plus sigma x a standard normal keyed on the LANE (every row meets the same noise
+        sequence, scaled), the plant receives g x the controller's output of d steps ago (0 before the first).  packed_actor None =
+        the prior controller alone.  Returns summary float64 [P, n_segments, 8, 5] -- per row, segment and metric row
+        (native.METRIC_NAMES) the stats native.SWEEP_STATS over the lanes, exactly as `prior_sweep` -- or, with `want_pairs` and /
+        or `want_trace`, a dict with "summary", "pairs" float64 [n_segments, 8, P, N] and "actions", "outputs" float64
+        [n_steps, P, N] (the APPLIED action and the controlled output after each step).  ValueError for a row with a non-finite
+        gain, a delay that is not an integer in 0 .. native.MARGIN_MAX_DELAY, or a sigma that is negative or not finite (`check_perturb`;
+        inside a stream capture pass a float64 device tensor validated beforehand).  The env itself is read, never advanced
+        (definitions in include/pime_hip.h)."""
+        if torch.is_tensor(perturb) and perturb.is_cuda and torch.cuda.is_current_stream_capturing():
+            # a capture can neither read the rows back nor upload them: a float64 [P, 3] device tensor the caller validated
+            # (check_perturb) before the capture; the kernel itself rounds and clamps the delay
+            pt = perturb
+            if pt.dtype != torch.float64 or pt.dim() != 2 or pt.shape[1] != native.PERTURB_COLS or pt.shape[0] < 1 or not pt.is_contiguous():
+                raise ValueError(f"margin_sweep: under capture perturb must be a contiguous float64 [P >= 1, {native.PERTURB_COLS}] device tensor")
+        else:
+            pt = torch.as_tensor(check_perturb(perturb), dtype=torch.float64).to(self.device).contiguous()
+        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
+        assert k.size == self.obs_dim
+        P, n_steps, seg_len = int(pt.shape[0]), int(n_steps), int(seg_len)
+        n_seg = max(-(-n_steps // seg_len) if seg_len > 0 else 1, 1)
+        ws_bytes = int(self._lib.pime_margin_sweep_workspace_bytes(self._h, P, n_steps, seg_len))
+        if ws_bytes < 0:
+            raise native.PimeError(f"pime_margin_sweep_workspace_bytes: {native.last_error()}")
+        if packed_actor is None:
+            kind, md, img = -1, 0, None
+        else:
+            kind = _EVAL_KINDS[packed_actor.kind]
+            md, img = int(packed_actor.md), packed_actor.packed
+        N = self.num_envs
+        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        summary = torch.empty((P, n_seg, native.METRIC_ROWS, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
+        pairs = torch.empty((n_seg, native.METRIC_ROWS, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
+        actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
+        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
+        native.check(self._lib.pime_margin_sweep(
+            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(pt), P, C.c_uint64(int(noise_seed)),
+            C.c_uint32(int(noise_epoch)), n_steps, seg_len, native.ptr(sp) if sp.size else None, int(sp.size), float(band), int(tail),
+            native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()),
+            "pime_margin_sweep")
+        del workspace
+        if not (want_pairs or want_trace):
+            return summary
+        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
 
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
