@@ -257,23 +257,31 @@ int h2d_from_double(const FieldRef& f, int n, const double* in, hipStream_t s) {
 
 }  // namespace
 
-template <typename S>
-static int rollout_eval_t(pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, int32_t kind, int32_t md, const float* packed_actor,
-                          const double* priorK, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
-                          double* ret, double* trace, const EvalMetricsArgs& mx, const EvalBandArgs& bd, pime_stream stream) {
-    EvalArgs<S> a{};
+// ---- the plant-grid calls (rollout_eval, prior_sweep, mpc_eval, margin_sweep; replay_error in part): one host path ----------------
+// f(ph, wt) on the handle's state pointers in its state's precision (PIME_STATE_F64: double, else float), so an entry point names its
+// arguments once; inside f the precision is state_scalar_t<decltype(ph)>
+template <typename F>
+static int with_state(const pime_env* e, const F& f) {
+    return e->cfg.state_mode == PIME_STATE_F64 ? f(e->ph64, e->wt64) : f(e->ph32, e->wt32);
+}
+template <typename Ph>
+using state_scalar_t = std::remove_pointer_t<decltype(std::declval<Ph>().r)>;   // (PhPtrs<S>::r is S*)
+
+// what EvalArgs, SweepArgs, MpcArgs and MarginArgs have in common, by member name: the handle's lanes, without auto-reset
+template <typename A, typename Ph, typename Wt>
+static void fill_grid_args(A& a, const pime_env* e, const Ph& ph, const Wt& wt) {
     a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
     a.n = e->cfg.n_envs;
     a.env_offset = e->cfg.env_offset;
     if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
     else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
-    a.img = packed_actor;
-    for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
-    a.n_steps = n_steps; a.seg_len = seg_len;
-    if (seg_len > 0)   // (validated by the caller: setpoints != NULL, 1 <= n_setpoints <= kMaxSetpoints)
-        for (int j = 0; j < n_setpoints && j < kMaxSetpoints; ++j) a.setpoint[j] = setpoints[j];
-    a.ret = ret; a.trace = trace; a.mx = mx; a.bd = bd;
-    return launch_rollout_eval<S>(kind, md, a, static_cast<hipStream_t>(stream));
+}
+
+// float64 or mixed state, pH or the Integrator tank: the handles the plant-grid calls serve
+static bool grid_handle(const pime_env* e) {
+    if (e == nullptr) return false;
+    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return false;
+    return e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0;
 }
 
 
@@ -853,11 +861,18 @@ static int rollout_eval_common(const char* fn, pime_env* e, int32_t kind, int32_
             for (int j = 0; j < n_setpoints && j < 16; ++j) a.setpoint[j] = setpoints[j];
         return launch_rollout(kind, md, a, static_cast<hipStream_t>(stream));
     }
-    if (e->cfg.state_mode == PIME_STATE_F64)
-        return rollout_eval_t<double>(e, e->ph64, e->wt64, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints,
-                                      ret, trace, mx, bd, stream);
-    return rollout_eval_t<float>(e, e->ph32, e->wt32, kind, md, packed_actor, priorK, n_steps, seg_len, setpoints, n_setpoints, ret,
-                                 trace, mx, bd, stream);
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        EvalArgs<S> a{};
+        fill_grid_args(a, e, ph, wt);
+        a.img = packed_actor;
+        for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
+        a.n_steps = n_steps; a.seg_len = seg_len;
+        if (seg_len > 0)   // (validated above: setpoints != NULL, 1 <= n_setpoints <= kMaxSetpoints)
+            for (int j = 0; j < n_setpoints && j < kMaxSetpoints; ++j) a.setpoint[j] = setpoints[j];
+        a.ret = ret; a.trace = trace; a.mx = mx; a.bd = bd;
+        return launch_rollout_eval<S>(kind, md, a, static_cast<hipStream_t>(stream));
+    });
 }
 
 int pime_rollout_eval(pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, int32_t n_steps,
@@ -941,25 +956,9 @@ int pime_env_replay_channels(const pime_env* e) { return e ? (e->cfg.kind == PIM
 int pime_env_replay_rows(void) { return PIME_REPLAY_ROWS; }
 
 int pime_env_replay_supported(const pime_env* e, int32_t mode) {
-    if (e == nullptr) return 0;
-    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
+    if (!grid_handle(e)) return 0;
     if (e->cfg.kind == PIME_ENV_PH) return mode == PIME_REPLAY_SIMULATE ? 1 : 0;   // x is not measured: no one-step prediction
-    if (e->cfg.num_stack != 0) return 0;
     return mode == PIME_REPLAY_SIMULATE || mode == PIME_REPLAY_PREDICT ? 1 : 0;
-}
-
-extern "C++" {
-template <typename S>
-static int replay_error_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, const pime_replay_records* rec, int32_t mode,
-                          int32_t skip, double* err, double* sim, pime_stream stream) {
-    ReplayArgs<S> a{};
-    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
-    a.n = e->cfg.n_envs;
-    if (a.env == 0) { a.p = e->ph; a.table = ph.table; a.A = ph.A; a.B = ph.B; a.C = ph.C; }
-    else { a.wp = e->wt; a.a1 = wt.a1; a.a2 = wt.a2; a.kp = wt.kp; }
-    a.E = rec->E; a.T = rec->T; a.mode = mode; a.skip = skip;
-    return launch_replay_error<S>(a, rec->action, rec->output, rec->state0, err, sim, static_cast<hipStream_t>(stream));
-}
 }
 
 int pime_env_replay_error(pime_env* e, const pime_replay_records* rec, int32_t mode, int32_t skip, double* err, double* sim,
@@ -970,18 +969,22 @@ int pime_env_replay_error(pime_env* e, const pime_replay_records* rec, int32_t m
     PIME_REQUIRE(pime_env_replay_supported(e, mode), "%s: not served for this handle (PIME_STATE_F64 / PIME_STATE_MIXED, pH or the "
                  "Integrator water tank: pime_env_replay_supported)", fn);
     if (int rc = use_device(e)) return rc;
-    if (e->cfg.state_mode == PIME_STATE_F64) return replay_error_t<double>(e, e->ph64, e->wt64, rec, mode, skip, err, sim, stream);
-    return replay_error_t<float>(e, e->ph32, e->wt32, rec, mode, skip, err, sim, stream);
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        ReplayArgs<S> a{};   // (the plants' own arrays, no lane state: not fill_grid_args')
+        a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
+        a.n = e->cfg.n_envs;
+        if (a.env == 0) { a.p = e->ph; a.table = ph.table; a.A = ph.A; a.B = ph.B; a.C = ph.C; }
+        else { a.wp = e->wt; a.a1 = wt.a1; a.a2 = wt.a2; a.kp = wt.kp; }
+        a.E = rec->E; a.T = rec->T; a.mode = mode; a.skip = skip;
+        return launch_replay_error<S>(a, rec->action, rec->output, rec->state0, err, sim, static_cast<hipStream_t>(stream));
+    });
 }
 
 // ---- prior-gain sweep (prior_sweep.hip) ------------------------------------------------------------------------------------------
 int pime_prior_sweep_stats(void) { return PIME_SWEEP_STATS; }
 
-int pime_prior_sweep_supported(const pime_env* e) {
-    if (e == nullptr) return 0;
-    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
-    return e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0 ? 1 : 0;
-}
+int pime_prior_sweep_supported(const pime_env* e) { return grid_handle(e) ? 1 : 0; }
 
 int64_t pime_prior_sweep_workspace_bytes(const pime_env* e, int32_t G, int32_t n_steps, int32_t seg_len) {
     if (!pime_prior_sweep_supported(e) || G < 1 || n_steps < 1 || seg_len < 0 || (long long)G * e->cfg.n_envs > 2147483647LL ||
@@ -991,24 +994,6 @@ int64_t pime_prior_sweep_workspace_bytes(const pime_env* e, int32_t G, int32_t n
         return -1;
     }
     return (int64_t)sweep_workspace_doubles(G, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
-}
-
-extern "C++" {
-template <typename S>
-static int prior_sweep_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, const double* gains, int32_t G, int32_t n_steps,
-                         int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* pairs,
-                         double* summary, void* workspace, pime_stream stream) {
-    SweepArgs<S> a{};
-    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
-    a.n = e->cfg.n_envs; a.G = G;
-    a.n_blocks = (a.n + kSweepBlockPlants - 1) / kSweepBlockPlants;
-    a.n_seg = sweep_segments(n_steps, seg_len);
-    a.env_offset = e->cfg.env_offset;
-    if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
-    else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
-    fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
-    return launch_prior_sweep<S>(a, gains, pairs, summary, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
-}
 }
 
 int pime_prior_sweep(const pime_env* e, const double* gains, int32_t G, int32_t n_steps, int32_t seg_len, const double* setpoints,
@@ -1022,36 +1007,20 @@ int pime_prior_sweep(const pime_env* e, const double* gains, int32_t G, int32_t 
     PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
     if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
     if (int rc = use_device(e)) return rc;
-    if (e->cfg.state_mode == PIME_STATE_F64)
-        return prior_sweep_t<double>(e, e->ph64, e->wt64, gains, G, n_steps, seg_len, setpoints, n_setpoints, band, tail, pairs, summary,
-                                     workspace, stream);
-    return prior_sweep_t<float>(e, e->ph32, e->wt32, gains, G, n_steps, seg_len, setpoints, n_setpoints, band, tail, pairs, summary,
-                                workspace, stream);
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        SweepArgs<S> a{};
+        fill_grid_args(a, e, ph, wt);
+        a.G = G;
+        a.n_blocks = (a.n + kSweepBlockPlants - 1) / kSweepBlockPlants;
+        a.n_seg = sweep_segments(n_steps, seg_len);
+        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+        return launch_prior_sweep<S>(a, gains, pairs, summary, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
+    });
 }
 
 // ---- receding-horizon benchmark controller (mpc_eval.hip) ------------------------------------------------------------------------
-int pime_mpc_eval_supported(const pime_env* e) {
-    if (e == nullptr) return 0;
-    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
-    return e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0 ? 1 : 0;
-}
-
-extern "C++" {
-template <typename S>
-static int mpc_eval_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, const double* model_plants, int32_t horizon,
-                      int32_t passes, double rho, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
-                      double band, int32_t tail, double* metrics, double* actions, double* outputs, pime_stream stream) {
-    MpcArgs<S> a{};
-    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
-    a.n = e->cfg.n_envs;
-    a.env_offset = e->cfg.env_offset;
-    if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
-    else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
-    fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
-    a.m = MpcConfig{horizon, passes, rho};
-    return launch_mpc_eval<S>(a, model_plants, metrics, actions, outputs, static_cast<hipStream_t>(stream));
-}
-}
+int pime_mpc_eval_supported(const pime_env* e) { return grid_handle(e) ? 1 : 0; }
 
 int pime_mpc_eval(const pime_env* e, const double* model_plants, int32_t horizon, int32_t passes, double rho, int32_t n_steps,
                   int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* metrics,
@@ -1064,18 +1033,19 @@ int pime_mpc_eval(const pime_env* e, const double* model_plants, int32_t horizon
                                 n_setpoints, band, tail, metrics)) return rc;
     if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
     if (int rc = use_device(e)) return rc;
-    if (e->cfg.state_mode == PIME_STATE_F64)
-        return mpc_eval_t<double>(e, e->ph64, e->wt64, model_plants, horizon, passes, rho, n_steps, seg_len, setpoints, n_setpoints, band,
-                                  tail, metrics, actions, outputs, stream);
-    return mpc_eval_t<float>(e, e->ph32, e->wt32, model_plants, horizon, passes, rho, n_steps, seg_len, setpoints, n_setpoints, band,
-                             tail, metrics, actions, outputs, stream);
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        MpcArgs<S> a{};
+        fill_grid_args(a, e, ph, wt);
+        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+        a.m = MpcConfig{horizon, passes, rho};
+        return launch_mpc_eval<S>(a, model_plants, metrics, actions, outputs, static_cast<hipStream_t>(stream));
+    });
 }
 
 // ---- loop-perturbation sweep (margin_sweep.hip) ----------------------------------------------------------------------------------
 int pime_margin_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
-    if (e == nullptr) return 0;
-    if (e->cfg.state_mode != PIME_STATE_F64 && e->cfg.state_mode != PIME_STATE_MIXED) return 0;
-    if (e->cfg.kind != PIME_ENV_PH && e->cfg.num_stack != 0) return 0;
+    if (!grid_handle(e)) return 0;
     if (kind == -1) return 1;                                            // the prior controller alone
     if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR && kind != PIME_MLP_CRITIC) return 0;
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;       // (width 256, the streamed family: not served)
@@ -1089,28 +1059,6 @@ int64_t pime_margin_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t 
         return -1;
     }
     return (int64_t)margin_workspace_doubles(P, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
-}
-
-extern "C++" {
-template <typename S>
-static int margin_sweep_t(const pime_env* e, const PhPtrs<S>& ph, const WtPtrs<S>& wt, int32_t kind, int32_t md, const float* packed_actor,
-                          const double* priorK, const double* perturb, int32_t P, uint64_t noise_seed, uint32_t noise_epoch,
-                          int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints, double band, int32_t tail,
-                          double* pairs, double* summary, double* actions, double* outputs, void* workspace, pime_stream stream) {
-    MarginArgs<S> a{};
-    a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
-    a.n = e->cfg.n_envs; a.P = P;
-    a.n_seg = sweep_segments(n_steps, seg_len);
-    a.env_offset = e->cfg.env_offset;
-    if (a.env == 0) { a.p = e->ph; a.p.auto_reset = 0; a.st = ph; }
-    else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
-    a.img = packed_actor;
-    for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
-    a.nz = MarginNoise{noise_seed, noise_epoch};
-    fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
-    return launch_margin_sweep<S>(kind, md, a, perturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
-                                  static_cast<hipStream_t>(stream));
-}
 }
 
 int pime_margin_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
@@ -1133,11 +1081,19 @@ int pime_margin_sweep(const pime_env* e, int32_t kind, int32_t md, const float* 
     PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
     if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
     if (int rc = use_device(e)) return rc;
-    if (e->cfg.state_mode == PIME_STATE_F64)
-        return margin_sweep_t<double>(e, e->ph64, e->wt64, kind, md, packed_actor, priorK, perturb, P, noise_seed, noise_epoch, n_steps,
-                                      seg_len, setpoints, n_setpoints, band, tail, pairs, summary, actions, outputs, workspace, stream);
-    return margin_sweep_t<float>(e, e->ph32, e->wt32, kind, md, packed_actor, priorK, perturb, P, noise_seed, noise_epoch, n_steps,
-                                 seg_len, setpoints, n_setpoints, band, tail, pairs, summary, actions, outputs, workspace, stream);
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        MarginArgs<S> a{};
+        fill_grid_args(a, e, ph, wt);
+        a.P = P;
+        a.n_seg = sweep_segments(n_steps, seg_len);
+        a.img = packed_actor;
+        for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
+        a.nz = MarginNoise{noise_seed, noise_epoch};
+        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+        return launch_margin_sweep<S>(kind, md, a, perturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
+                                      static_cast<hipStream_t>(stream));
+    });
 }
 
 static int offpolicy_supported(const pime_env* e, int32_t kind, int32_t md) {

@@ -122,7 +122,7 @@ __device__ __forceinline__ void band_step(const EvalBandArgs& b, int t, int tile
 }
 
 // the steps segment `seg` has in a launch of n_steps with a boundary every seg_len steps (seg_len 0: one segment)
-__device__ __forceinline__ int segment_steps(int n_steps, int seg_len, int seg) {
+__host__ __device__ __forceinline__ int segment_steps(int n_steps, int seg_len, int seg) {
     if (seg_len <= 0) return n_steps;
     const int left = n_steps - seg * seg_len;
     return left < seg_len ? left : seg_len;

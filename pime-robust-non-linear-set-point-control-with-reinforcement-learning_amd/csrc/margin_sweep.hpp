@@ -125,7 +125,7 @@ __host__ __device__ __forceinline__ void margin_ph_pair(const PhParams& p, const
             const int bump = t > 0 ? 1 : 0;
             E.r = (S)sp; E.I = S(0); E.t = 0; E.episode += bump; obs[1] = (float)E.r; obs[2] = 0.f;
         }
-        if (k == 0) M.begin((double)ph_lookup<S>(p, table, E.C, E.x), (double)E.r, sweep_segment_steps(s.n_steps, s.seg_len, seg), s.tail);
+        if (k == 0) M.begin((double)ph_lookup<S>(p, table, E.C, E.x), (double)E.r, segment_steps(s.n_steps, s.seg_len, seg), s.tail);
         const double a_env = margin_action<1, 3>(obs, K, row, nz, gid, t, pol, line);
         float rew;
         (void)ph_lane_step<S>(p, table, a_env, E, obs, rew);
@@ -158,7 +158,7 @@ __host__ __device__ __forceinline__ void margin_wt_pair(const WtParams& p, uint3
             const int bump = t > 0 ? 1 : 0;
             W.r = (S)sp; W.I = S(0); W.t = 0; W.episode += bump; obs[2] = (float)W.r; obs[3] = 0.f;
         }
-        if (k == 0) M.begin((double)W.h2, (double)W.r, sweep_segment_steps(s.n_steps, s.seg_len, seg), s.tail);
+        if (k == 0) M.begin((double)W.h2, (double)W.r, segment_steps(s.n_steps, s.seg_len, seg), s.tail);
         const double a_env = margin_action<2, 4>(obs, K, row, nz, gid, t, pol, line);
         float rew;
         double z1n, z2n;
@@ -183,14 +183,7 @@ inline int check_margin_args(const char* fn, int N, const double* priorK, const 
     PIME_REQUIRE(perturb != nullptr, "%s: perturb is NULL", fn);
     PIME_REQUIRE(summary != nullptr, "%s: summary is NULL", fn);
     PIME_REQUIRE(priorK != nullptr, "%s: priorK is NULL", fn);
-    PIME_REQUIRE(band >= 0.0 && band <= 1.79769313486231570815e308, "%s: band %g (finite, >= 0)", fn, band);   // (NaN fails both)
-    PIME_REQUIRE(tail >= 1, "%s: tail %d (>= 1)", fn, tail);
-    PIME_REQUIRE(n_steps >= 1, "%s: bad arguments (n_steps %d, >= 1)", fn, n_steps);
-    PIME_REQUIRE(n_setpoints >= 0 && n_setpoints <= kMaxSetpoints, "%s: n_setpoints %d (0 .. %d)", fn, n_setpoints, kMaxSetpoints);
-    PIME_REQUIRE(seg_len >= 0 && (seg_len == 0 || (setpoints && n_setpoints >= 1 && n_setpoints <= kMaxSetpoints &&
-                                                   (n_steps + seg_len - 1) / seg_len <= n_setpoints)),
-                 "%s: the set-point schedule does not cover n_steps (at most %d segments)", fn, kMaxSetpoints);
-    return PIME_OK;
+    return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
 }
 
 // (margin_sweep.hip)

@@ -103,7 +103,7 @@ __host__ __device__ __forceinline__ void mpc_ph_plant(const PhParams& p, const S
             const int bump = t > 0 ? 1 : 0;
             E.r = (S)sp; E.I = S(0); E.t = 0; E.episode += bump;
         }
-        if (k == 0) M.begin((double)ph_lookup<S>(p, table, E.C, E.x), (double)E.r, sweep_segment_steps(s.n_steps, s.seg_len, seg), s.tail);
+        if (k == 0) M.begin((double)ph_lookup<S>(p, table, E.C, E.x), (double)E.r, segment_steps(s.n_steps, s.seg_len, seg), s.tail);
         const double a_env = mpc_choose(m, search, [&](double u) { return mpc_cost_ph<S>(p, table, E, m, u, u_prev); });
         float rew;
         (void)ph_lane_step<S>(p, table, a_env, E, obs, rew);
@@ -134,7 +134,7 @@ __host__ __device__ __forceinline__ void mpc_wt_plant(const WtParams& p, uint32_
             const int bump = t > 0 ? 1 : 0;
             W.r = (S)sp; W.I = S(0); W.t = 0; W.episode += bump;
         }
-        if (k == 0) M.begin((double)W.h2, (double)W.r, sweep_segment_steps(s.n_steps, s.seg_len, seg), s.tail);
+        if (k == 0) M.begin((double)W.h2, (double)W.r, segment_steps(s.n_steps, s.seg_len, seg), s.tail);
         WtLane<S> model = W;
         if (has_model) { model.a1 = m_a1; model.a2 = m_a2; model.kp = m_kp; }
         const double a_env = mpc_choose(m, search, [&](double u) { return mpc_cost_wt<S>(p, model, m, u, u_prev); });
@@ -161,14 +161,7 @@ inline int check_mpc_args(const char* fn, bool is_ph, const double* model_plants
     PIME_REQUIRE(rho >= 0.0 && rho <= 1.79769313486231570815e308, "%s: rho %g (finite, >= 0)", fn, rho);   // (NaN fails both)
     PIME_REQUIRE(metrics != nullptr, "%s: metrics is NULL", fn);
     PIME_REQUIRE(!(is_ph && model_plants != nullptr), "%s: model_plants on a pH handle (its state x is not measured)", fn);
-    PIME_REQUIRE(band >= 0.0 && band <= 1.79769313486231570815e308, "%s: band %g (finite, >= 0)", fn, band);
-    PIME_REQUIRE(tail >= 1, "%s: tail %d (>= 1)", fn, tail);
-    PIME_REQUIRE(n_steps >= 1, "%s: bad arguments (n_steps %d, >= 1)", fn, n_steps);
-    PIME_REQUIRE(n_setpoints >= 0 && n_setpoints <= kMaxSetpoints, "%s: n_setpoints %d (0 .. %d)", fn, n_setpoints, kMaxSetpoints);
-    PIME_REQUIRE(seg_len >= 0 && (seg_len == 0 || (setpoints && n_setpoints >= 1 && n_setpoints <= kMaxSetpoints &&
-                                                   (n_steps + seg_len - 1) / seg_len <= n_setpoints)),
-                 "%s: the set-point schedule does not cover n_steps (at most %d segments)", fn, kMaxSetpoints);
-    return PIME_OK;
+    return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
 }
 
 // (mpc_eval.hip)

@@ -17,27 +17,12 @@ struct SweepSchedule {
     double setpoint[kMaxSetpoints];
 };
 
-// (segment_steps of eval_metrics.hpp, for both sides)
-__host__ __device__ __forceinline__ int sweep_segment_steps(int n_steps, int seg_len, int seg) {
-    if (seg_len <= 0) return n_steps;
-    const int left = n_steps - seg * seg_len;
-    return left < seg_len ? left : seg_len;
-}
 __host__ __device__ __forceinline__ int sweep_segments(int n_steps, int seg_len) {
     return seg_len > 0 ? (n_steps + seg_len - 1) / seg_len : 1;
 }
 
-// the rows of a finished segment: the values SegMetrics::store writes, in the order of enum pime_metric
-__host__ __device__ __forceinline__ void sweep_rows(const SegMetrics& M, double (&v)[PIME_METRIC_ROWS]) {
-    v[PIME_METRIC_IAE] = M.iae;
-    v[PIME_METRIC_ISE] = M.ise;
-    v[PIME_METRIC_ITAE] = M.itae;
-    v[PIME_METRIC_OVERSHOOT] = M.peak;
-    v[PIME_METRIC_SETTLING] = (double)M.settle;
-    v[PIME_METRIC_SSE] = M.tail_sum / (double)(M.len - M.tail_from);
-    v[PIME_METRIC_RETURN] = M.ret;
-    v[PIME_METRIC_ACTION_VAR] = M.av;
-}
+// the rows of a finished segment in registers: what SegMetrics::store writes, as one lane of one segment
+__host__ __device__ __forceinline__ void sweep_rows(const SegMetrics& M, double (&v)[PIME_METRIC_ROWS]) { M.store(v, 0, 1, 0); }
 
 // a value counts in the summary if it is finite (NaN fails the comparison)
 __host__ __device__ __forceinline__ bool sweep_counts(double v) { return fabs(v) <= 1.79769313486231570815e308; }
@@ -56,7 +41,7 @@ __host__ __device__ __forceinline__ void sweep_ph_pair(const PhParams& p, const 
             const int bump = t > 0 ? 1 : 0;
             E.r = (S)sp; E.I = S(0); E.t = 0; E.episode += bump; obs[1] = (float)E.r; obs[2] = 0.f;
         }
-        if (k == 0) M.begin((double)ph_lookup<S>(p, table, E.C, E.x), (double)E.r, sweep_segment_steps(s.n_steps, s.seg_len, seg), s.tail);
+        if (k == 0) M.begin((double)ph_lookup<S>(p, table, E.C, E.x), (double)E.r, segment_steps(s.n_steps, s.seg_len, seg), s.tail);
         double a_env = 0.0;
 #pragma unroll
         for (int j = 0; j < 3; ++j) a_env += (double)obs[j] * K[j];
@@ -87,7 +72,7 @@ __host__ __device__ __forceinline__ void sweep_wt_pair(const WtParams& p, uint32
             const int bump = t > 0 ? 1 : 0;
             W.r = (S)sp; W.I = S(0); W.t = 0; W.episode += bump; obs[2] = (float)W.r; obs[3] = 0.f;
         }
-        if (k == 0) M.begin((double)W.h2, (double)W.r, sweep_segment_steps(s.n_steps, s.seg_len, seg), s.tail);
+        if (k == 0) M.begin((double)W.h2, (double)W.r, segment_steps(s.n_steps, s.seg_len, seg), s.tail);
         double a_env = 0.0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) a_env += (double)obs[j] * K[j];
@@ -104,14 +89,10 @@ __host__ __device__ __forceinline__ void sweep_wt_pair(const WtParams& p, uint32
     }
 }
 
-// the argument errors of pime_prior_sweep and of its host build, checked before anything runs; `fn` names the entry point.  The
-// schedule's checks and messages are pime_rollout_eval_metrics' (abi.hip: rollout_eval_common).
-inline int check_sweep_args(const char* fn, int N, const double* gains, int G, int n_steps, int seg_len, const double* setpoints,
-                            int n_setpoints, double band, int tail, const double* summary) {
-    PIME_REQUIRE(G >= 1, "%s: G = %d (>= 1)", fn, G);
-    PIME_REQUIRE((long long)G * N <= 2147483647LL, "%s: G x N = %d x %d pairs exceed 2^31 - 1", fn, G, N);
-    PIME_REQUIRE(gains != nullptr, "%s: gains is NULL", fn);
-    PIME_REQUIRE(summary != nullptr, "%s: summary is NULL", fn);
+// the schedule, band and tail errors every plant-grid call and its host build share, after the call's own checks; `fn` names the
+// entry point.  The schedule's checks and messages are pime_rollout_eval_metrics' (abi.hip: rollout_eval_common).
+inline int check_schedule_args(const char* fn, int n_steps, int seg_len, const double* setpoints, int n_setpoints, double band,
+                               int tail) {
     PIME_REQUIRE(band >= 0.0 && band <= 1.79769313486231570815e308, "%s: band %g (finite, >= 0)", fn, band);   // (NaN fails both)
     PIME_REQUIRE(tail >= 1, "%s: tail %d (>= 1)", fn, tail);
     PIME_REQUIRE(n_steps >= 1, "%s: bad arguments (n_steps %d, >= 1)", fn, n_steps);
@@ -126,6 +107,16 @@ inline void fill_sweep_schedule(SweepSchedule& s, int n_steps, int seg_len, cons
                                 int tail) {
     s.n_steps = n_steps; s.seg_len = seg_len; s.tail = tail; s.band = band;
     for (int j = 0; j < kMaxSetpoints; ++j) s.setpoint[j] = seg_len > 0 && j < n_setpoints ? setpoints[j] : 0.0;
+}
+
+// the argument errors of pime_prior_sweep and of its host build, checked before anything runs
+inline int check_sweep_args(const char* fn, int N, const double* gains, int G, int n_steps, int seg_len, const double* setpoints,
+                            int n_setpoints, double band, int tail, const double* summary) {
+    PIME_REQUIRE(G >= 1, "%s: G = %d (>= 1)", fn, G);
+    PIME_REQUIRE((long long)G * N <= 2147483647LL, "%s: G x N = %d x %d pairs exceed 2^31 - 1", fn, G, N);
+    PIME_REQUIRE(gains != nullptr, "%s: gains is NULL", fn);
+    PIME_REQUIRE(summary != nullptr, "%s: summary is NULL", fn);
+    return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
 }
 
 constexpr int kSweepBlockPlants = 64;   // the plants of one block of the summary's sum: one wave

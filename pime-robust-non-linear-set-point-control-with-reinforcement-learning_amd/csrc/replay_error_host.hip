@@ -7,19 +7,9 @@
 #include <thread>
 #include <vector>
 
-#include "env_handle.hpp"
+#include "host_grid.hpp"
 #include "pime_replay_host.h"
 #include "replay_error.hpp"
-
-namespace pime {
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace pime
 
 using namespace pime;
 

@@ -431,30 +431,51 @@ class VecControlEnv:
             level = self._lib.pime_rollout_eval_supported(self._h, kind, int(packed_actor.md))
         return level == 1 or (level == 2 and not schedule)
 
+    # -- the arguments the plant-grid calls share (rollout_eval*, prior_sweep, mpc_eval, margin_sweep) -------------
+    def _prior_row(self, priorK):
+        """priorK as the native calls read it: one contiguous float64 row of obs_dim gains."""
+        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
+        assert k.size == self.obs_dim
+        return k
+
+    @staticmethod
+    def _actor_triple(packed_actor):
+        """(kind, md, img) of a packed actor; None = the prior controller alone."""
+        if packed_actor is None:
+            return -1, 0, None
+        return _EVAL_KINDS[packed_actor.kind], int(packed_actor.md), packed_actor.packed
+
+    @staticmethod
+    def _schedule(setpoints, n_steps, seg_len):
+        """(sp, its pointer or None, its length, n_segments) of a set-point schedule; the caller keeps sp alive over the call."""
+        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        n_seg = max(-(-int(n_steps) // int(seg_len)) if seg_len > 0 else 1, 1)
+        return sp, native.ptr(sp) if sp.size else None, int(sp.size), n_seg
+
+    def _lanes_advanced(self, n_steps):
+        """After a call that stepped every lane n_steps without auto-reset: the lanes sit somewhere inside an episode, so the next
+        rollout must reset first."""
+        self._was_reset = False
+        if self._t_lanes is None:
+            self._t_all += n_steps
+        else:
+            self._t_lanes += n_steps
+
     def rollout_eval(self, packed_actor, priorK, n_steps, setpoints=None, seg_len=0, want_trace=False, ret=None):
         """`n_steps` steps of every lane under the deterministic residual policy in ONE launch (csrc/rollout_eval.hip; no
         exploration noise, no auto-reset): returns (ret float64 [N] = per-lane sum of rewards, accumulated into `ret` if given,
         trace float64 [n_steps, 6, N] or None).  packed_actor None = the prior controller alone.  setpoints / seg_len: a
         step-response schedule (see include/pime_hip.h).  The lanes are left mid-episode: reset before the next rollout."""
-        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
-        assert k.size == self.obs_dim
+        k = self._prior_row(priorK)
         if ret is None:
             ret = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
         trace = torch.empty((n_steps, 6, self.num_envs), dtype=torch.float64, device=self.device) if want_trace else None
-        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
-        if packed_actor is None:
-            kind, md, img = -1, 0, None
-        else:
-            kind = _EVAL_KINDS[packed_actor.kind]
-            md, img = int(packed_actor.md), packed_actor.packed
+        sp, sp_ptr, n_sp, _ = self._schedule(setpoints, n_steps, seg_len)
+        kind, md, img = self._actor_triple(packed_actor)
         native.check(self._lib.pime_rollout_eval(self._h, kind, md, native.ptr(img), native.ptr(k), int(n_steps), int(seg_len),
-                                                 native.ptr(sp) if sp.size else None, int(sp.size), native.ptr(ret),
-                                                 native.ptr(trace), self._stream()), "pime_rollout_eval")
-        self._was_reset = False   # the lanes sit somewhere inside an episode: the next rollout must reset first
-        if self._t_lanes is None:
-            self._t_all += n_steps
-        else:
-            self._t_lanes += n_steps
+                                                 sp_ptr, n_sp, native.ptr(ret), native.ptr(trace), self._stream()),
+                     "pime_rollout_eval")
+        self._lanes_advanced(n_steps)
         return ret, trace
 
     def rollout_eval_metrics(self, packed_actor, priorK, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_trace=False,
@@ -464,28 +485,17 @@ class VecControlEnv:
         ITAE, overshoot, settling step for `band`, steady-state error over the last `tail` steps, return, action variation;
         definitions in include/pime_hip.h).  n_segments = ceil(n_steps / seg_len), 1 without a schedule.  ret and trace (None
         unless `want_trace`) are what `rollout_eval` returns for the same launch."""
-        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
-        assert k.size == self.obs_dim
+        k = self._prior_row(priorK)
         if ret is None:
             ret = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
-        n_seg = -(-int(n_steps) // int(seg_len)) if seg_len > 0 else 1
-        metrics = torch.empty((max(n_seg, 1), native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
+        metrics = torch.empty((n_seg, native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
         trace = torch.empty((n_steps, 6, self.num_envs), dtype=torch.float64, device=self.device) if want_trace else None
-        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
-        if packed_actor is None:
-            kind, md, img = -1, 0, None
-        else:
-            kind = _EVAL_KINDS[packed_actor.kind]
-            md, img = int(packed_actor.md), packed_actor.packed
+        kind, md, img = self._actor_triple(packed_actor)
         native.check(self._lib.pime_rollout_eval_metrics(
-            self._h, kind, md, native.ptr(img), native.ptr(k), int(n_steps), int(seg_len), native.ptr(sp) if sp.size else None,
-            int(sp.size), float(band), int(tail), native.ptr(ret), native.ptr(trace), native.ptr(metrics), self._stream()),
-            "pime_rollout_eval_metrics")
-        self._was_reset = False   # as rollout_eval: the lanes sit somewhere inside an episode
-        if self._t_lanes is None:
-            self._t_all += n_steps
-        else:
-            self._t_lanes += n_steps
+            self._h, kind, md, native.ptr(img), native.ptr(k), int(n_steps), int(seg_len), sp_ptr, n_sp, float(band), int(tail),
+            native.ptr(ret), native.ptr(trace), native.ptr(metrics), self._stream()), "pime_rollout_eval_metrics")
+        self._lanes_advanced(n_steps)
         return ret, metrics, trace
 
     def rollout_eval_band(self, packed_actor, priorK, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, group_lanes=None,
@@ -496,38 +506,28 @@ class VecControlEnv:
         consecutive lanes (a positive multiple of 16; None: all lanes as one group), G = ceil(N / group_lanes).  hist: None, or
         (bins, lo, hi) -> uint32 counts [n_steps, G, bins] of y (stored in an int32 tensor; definitions in include/pime_hip.h).
         ret, metrics and trace are what `rollout_eval_metrics` returns for the same launch."""
-        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
-        assert k.size == self.obs_dim
+        k = self._prior_row(priorK)
         if ret is None:
             ret = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
         n_steps, seg_len = int(n_steps), int(seg_len)
-        n_seg = -(-n_steps // seg_len) if seg_len > 0 else 1
         group_lanes = self.num_envs if group_lanes is None else int(group_lanes)
-        if packed_actor is None:
-            kind, md, img = -1, 0, None
-        else:
-            kind = _EVAL_KINDS[packed_actor.kind]
-            md, img = int(packed_actor.md), packed_actor.packed
+        kind, md, img = self._actor_triple(packed_actor)
         ws_bytes = int(self._lib.pime_rollout_eval_band_workspace_bytes(self._h, kind, md, n_steps, group_lanes))
         if ws_bytes < 0:
             raise native.PimeError(f"pime_rollout_eval_band_workspace_bytes: {native.last_error()}")
         groups = -(-self.num_envs // group_lanes) if group_lanes < self.num_envs else 1
-        metrics = torch.empty((max(n_seg, 1), native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
+        metrics = torch.empty((n_seg, native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
         stats = torch.empty((n_steps, native.BAND_ROWS, groups), dtype=torch.float64, device=self.device)
         workspace = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
         trace = torch.empty((n_steps, 6, self.num_envs), dtype=torch.float64, device=self.device) if want_trace else None
         bins, lo, hi = (0, 0.0, 0.0) if hist is None else (int(hist[0]), float(hist[1]), float(hist[2]))
         counts = None if hist is None else torch.empty((n_steps, groups, max(bins, 0)), dtype=torch.int32, device=self.device)
-        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
         native.check(self._lib.pime_rollout_eval_band(
-            self._h, kind, md, native.ptr(img), native.ptr(k), n_steps, seg_len, native.ptr(sp) if sp.size else None, int(sp.size),
-            float(band), int(tail), native.ptr(ret), native.ptr(trace), native.ptr(metrics), group_lanes, native.ptr(stats),
-            native.ptr(counts), bins, lo, hi, native.ptr(workspace), self._stream()), "pime_rollout_eval_band")
-        self._was_reset = False   # as rollout_eval: the lanes sit somewhere inside an episode
-        if self._t_lanes is None:
-            self._t_all += n_steps
-        else:
-            self._t_lanes += n_steps
+            self._h, kind, md, native.ptr(img), native.ptr(k), n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail),
+            native.ptr(ret), native.ptr(trace), native.ptr(metrics), group_lanes, native.ptr(stats), native.ptr(counts), bins, lo, hi,
+            native.ptr(workspace), self._stream()), "pime_rollout_eval_band")
+        self._lanes_advanced(n_steps)
         return ret, metrics, stats, counts, trace
 
     # -- replay of recorded runs (plant identification) ----------------------------------------------------------
@@ -583,19 +583,18 @@ class VecControlEnv:
         if g.dim() != 2 or g.shape[1] != self.obs_dim or g.shape[0] < 1:
             raise native.PimeError(f"prior_sweep: gains {tuple(g.shape)} must be [G >= 1, {self.obs_dim}]")
         G, n_steps, seg_len = int(g.shape[0]), int(n_steps), int(seg_len)
-        n_seg = max(-(-n_steps // seg_len) if seg_len > 0 else 1, 1)
         ws_bytes = int(self._lib.pime_prior_sweep_workspace_bytes(self._h, G, n_steps, seg_len))
         if ws_bytes < 0:
             raise native.PimeError(f"pime_prior_sweep_workspace_bytes: {native.last_error()}")
-        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
         summary = torch.empty((G, n_seg, native.METRIC_ROWS, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
         pairs = torch.empty((n_seg, native.METRIC_ROWS, G, self.num_envs), dtype=torch.float64, device=self.device) if want_pairs else None
         # the workspace lives for this call only; it comes from torch's allocator, so under a capture (native.capture_guard around
         # torch.cuda.graph, as for every capture of this package) it is a block of the graph's private pool and dropping it frees nothing
         workspace = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
         native.check(self._lib.pime_prior_sweep(
-            self._h, native.ptr(g), G, n_steps, seg_len, native.ptr(sp) if sp.size else None, int(sp.size), float(band), int(tail),
-            native.ptr(pairs), native.ptr(summary), native.ptr(workspace), self._stream()), "pime_prior_sweep")
+            self._h, native.ptr(g), G, n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail), native.ptr(pairs), native.ptr(summary),
+            native.ptr(workspace), self._stream()), "pime_prior_sweep")
         del workspace
         return (summary, pairs) if want_pairs else summary
 
@@ -616,20 +615,18 @@ class VecControlEnv:
         actions, outputs), float64 [n_steps, N]: the applied action and the controlled output after each step.  setpoints / seg_len /
         band / tail: as `rollout_eval_metrics`.  The env itself is read, never advanced (definitions in include/pime_hip.h)."""
         n_steps, seg_len = int(n_steps), int(seg_len)
-        n_seg = max(-(-n_steps // seg_len) if seg_len > 0 else 1, 1)
         model = None
         if model_plants is not None:
             model = torch.as_tensor(model_plants, dtype=torch.float64).to(self.device).contiguous()
             if tuple(model.shape) != (self.num_envs, 3):
                 raise native.PimeError(f"mpc_eval: model_plants {tuple(model.shape)} must be [{self.num_envs}, 3]")
-        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
         metrics = torch.empty((n_seg, native.METRIC_ROWS, self.num_envs), dtype=torch.float64, device=self.device)
         actions = torch.empty((max(n_steps, 0), self.num_envs), dtype=torch.float64, device=self.device) if trace else None
         outputs = torch.empty((max(n_steps, 0), self.num_envs), dtype=torch.float64, device=self.device) if trace else None
         native.check(self._lib.pime_mpc_eval(
-            self._h, native.ptr(model), int(horizon), int(passes), float(rho), n_steps, seg_len, native.ptr(sp) if sp.size else None,
-            int(sp.size), float(band), int(tail), native.ptr(metrics), native.ptr(actions), native.ptr(outputs), self._stream()),
-            "pime_mpc_eval")
+            self._h, native.ptr(model), int(horizon), int(passes), float(rho), n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail),
+            native.ptr(metrics), native.ptr(actions), native.ptr(outputs), self._stream()), "pime_mpc_eval")
         return (metrics, actions, outputs) if trace else metrics
 
     # -- loop-perturbation sweep (delay, gain and sensor-noise margins) ---------------------------------------------
@@ -666,20 +663,14 @@ class VecControlEnv:
                 raise ValueError(f"margin_sweep: under capture perturb must be a contiguous float64 [P >= 1, {native.PERTURB_COLS}] device tensor")
         else:
             pt = torch.as_tensor(check_perturb(perturb), dtype=torch.float64).to(self.device).contiguous()
-        k = np.ascontiguousarray(np.asarray(priorK, dtype=np.float64).reshape(-1))
-        assert k.size == self.obs_dim
+        k = self._prior_row(priorK)
         P, n_steps, seg_len = int(pt.shape[0]), int(n_steps), int(seg_len)
-        n_seg = max(-(-n_steps // seg_len) if seg_len > 0 else 1, 1)
         ws_bytes = int(self._lib.pime_margin_sweep_workspace_bytes(self._h, P, n_steps, seg_len))
         if ws_bytes < 0:
             raise native.PimeError(f"pime_margin_sweep_workspace_bytes: {native.last_error()}")
-        if packed_actor is None:
-            kind, md, img = -1, 0, None
-        else:
-            kind = _EVAL_KINDS[packed_actor.kind]
-            md, img = int(packed_actor.md), packed_actor.packed
+        kind, md, img = self._actor_triple(packed_actor)
         N = self.num_envs
-        sp = np.ascontiguousarray(np.asarray(setpoints if setpoints is not None else [], dtype=np.float64))
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
         summary = torch.empty((P, n_seg, native.METRIC_ROWS, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
         pairs = torch.empty((n_seg, native.METRIC_ROWS, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
         actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
@@ -688,9 +679,8 @@ class VecControlEnv:
         workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
         native.check(self._lib.pime_margin_sweep(
             self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(pt), P, C.c_uint64(int(noise_seed)),
-            C.c_uint32(int(noise_epoch)), n_steps, seg_len, native.ptr(sp) if sp.size else None, int(sp.size), float(band), int(tail),
-            native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()),
-            "pime_margin_sweep")
+            C.c_uint32(int(noise_epoch)), n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail), native.ptr(pairs),
+            native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()), "pime_margin_sweep")
         del workspace
         if not (want_pairs or want_trace):
             return summary

@@ -314,22 +314,10 @@ def check_recording(kind, cfg, lanes, table, rec, perturb=PERTURB, K=None, polic
 
 
 # ------------------------------------------------------------------------------------------------ host library
-_host = None
-
-
 def host_lib():
-    global _host
-    if _host is None:
-        if not os.path.exists(HOST_LIB_PATH):
-            raise RuntimeError(f"{HOST_LIB_PATH} is missing: build it with `make -C {P.PKG}/csrc` (or __graft_entry__.build())")
-        h = C.CDLL(HOST_LIB_PATH)
-        h.pime_margin_sweep_host.restype = C.c_int
-        h.pime_margin_sweep_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32,
-                                             C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-        h.pime_margin_host_last_error.restype = C.c_char_p
-        _host = h
-    return _host
+    return P.load_host(HOST_LIB_PATH, HOST_EXPORTS[0],
+                       [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32,
+                        C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], HOST_EXPORTS[1])
 
 
 def host_raw(kind, cfg, lanes, N_, K, perturb, Pn, seed, epoch, n_steps, seg_len, sp, n_sp, band, tail, pairs, summary, actions, outputs):

@@ -164,21 +164,27 @@ class SweepLanes(C.Structure):
                                           "r", "I", "t", "episode")]
 
 
-_host = None
+_hosts = {}
+
+
+def load_host(path, entry, argtypes, last_error):
+    """The host library at `path`, loaded once (also for mpc_eval, margin_sweep and replay_error): `entry` takes `argtypes` and
+    returns int, `last_error` returns the message of its last failure."""
+    if path not in _hosts:
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: build it with `make -C {PKG}/csrc` (or __graft_entry__.build())")
+        h = C.CDLL(path)
+        getattr(h, entry).restype = C.c_int
+        getattr(h, entry).argtypes = argtypes
+        getattr(h, last_error).restype = C.c_char_p
+        _hosts[path] = h
+    return _hosts[path]
 
 
 def host_lib():
-    global _host
-    if _host is None:
-        if not os.path.exists(HOST_LIB_PATH):
-            raise RuntimeError(f"{HOST_LIB_PATH} is missing: build it with `make -C {PKG}/csrc` (or __graft_entry__.build())")
-        h = C.CDLL(HOST_LIB_PATH)
-        h.pime_prior_sweep_host.restype = C.c_int
-        h.pime_prior_sweep_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                            C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
-        h.pime_sweep_host_last_error.restype = C.c_char_p
-        _host = h
-    return _host
+    return load_host(HOST_LIB_PATH, HOST_EXPORTS[0],
+                     [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                      C.c_int32, C.c_void_p, C.c_void_p], HOST_EXPORTS[1])
 
 
 def _p(a):

@@ -20,7 +20,9 @@ import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from prior_sweep import load_host
+
+ROOT =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "pime-robust-non-linear-set-point-control-with-reinforcement-learning_amd")
 HOST_LIB_PATH = os.path.join(PKG, "libpime_replay_host.so")
 HOST_EXPORTS = ("pime_replay_error_host", "pime_replay_host_last_error")
@@ -55,21 +57,10 @@ def true_lane(kind):
 
 
 # ------------------------------------------------------------------------------------------------ host library
-_host = None
-
-
 def host_lib():
-    global _host
-    if _host is None:
-        if not os.path.exists(HOST_LIB_PATH):
-            raise RuntimeError(f"{HOST_LIB_PATH} is missing: build it with `make -C {PKG}/csrc` (or __graft_entry__.build())")
-        h = C.CDLL(HOST_LIB_PATH)
-        h.pime_replay_error_host.restype = C.c_int
-        h.pime_replay_error_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                             C.c_void_p, C.c_int32]
-        h.pime_replay_host_last_error.restype = C.c_char_p
-        _host = h
-    return _host
+    return load_host(HOST_LIB_PATH, HOST_EXPORTS[0],
+                     [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32],
+                     HOST_EXPORTS[1])
 
 
 def _p(a):
