@@ -652,6 +652,62 @@ int pime_margin_sweep(const pime_env* env, int32_t kind, int32_t md, const float
                       const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary,
                       double* actions, double* outputs, void* workspace, pime_stream stream);
 
+/* -- disturbance-rejection sweep (csrc/disturb_sweep.hip) ------------------------------------------------------------
+ * How well does the closed loop REJECT a disturbance -- a load at the plant input, a step of the plant's parameters -- under the
+ * residual policy and under the prior controller alone?  The entry points above excite the loop through set-point steps only.  ONE
+ * call runs every (disturbance row p, plant lane i) pair of a [P, 6] grid `disturb` -- columns enum pime_disturb_col -- over the N
+ * lanes of the handle.  A pair runs the loop of pime_rollout_eval_metrics (set-point boundaries every seg_len steps, the lane step, the
+ * metrics with the same band and tail) on a register copy of lane i as the handle holds it.  With k the step WITHIN the segment:
+ *   ONSET k0, LENGTH L   k0 = rint(disturb[p][0]) clamped into 0 .. 2^30 (NaN: never); L = rint(disturb[p][1]) clamped likewise (NaN:
+ *     0).  The row is ACTIVE at k iff k >= k0 && (L == 0 || k < k0 + L): L == 0 lasts to the end of the segment, L > 0 is a pulse cut at
+ *     the segment's end.  Every segment starts on the nominal plant again and the row comes back at its step k0.
+ *   LOAD d_u   while active a_env = a_c + d_u (one double addition, normalised action units) IN FRONT of the actuator: pH's
+ *     clip(a, -1, 1) sees the sum, the tank does not clip.  While inactive a_env = a_c with no addition at all.
+ *   M0, M1, M2   while active the lane steps on a disturbed parameter set formed once per pair.  Tank: a1' = (S)((double)a1 * M0),
+ *     a2' with M1, Kp' with M2 (S the state's precision).  pH: q = qww_V * M0, e = -q * sample_t, A' = exp(e), B' = -expm1(e) / q,
+ *     C' = qc_V * M1 in double from the lane's STORED qww_V and qc_V, as a resampling reset forms them; M2 is ignored.  A parameter
+ *     whose multiplier is exactly 1.0 is the lane's own stored word, never recomputed (M0 == 1 keeps the stored A and B, M1 == 1 the
+ *     stored C).
+ *   CONTROLLER  a_c = tanh(mean(obs)) + obs @ priorK as pime_rollout_eval forms it; kind = -1: the prior controller alone.  The
+ *     metrics' action row and `actions` hold the CONTROLLER's output a_c (controller effort); the applied action is a_c + d_u.
+ * Rows PIME_METRIC_ROWS + enum pime_disturb_row of a pair and segment, over the window k >= k0 of that segment (sums sequential in
+ * ascending k from 0.0, e_k = r - y_k with y_k the controlled output after step k):
+ *   E0           r - y of the output step k0 starts from (k0 == 0: the segment's start): had the loop settled?
+ *   PEAK         max |e_k|            PEAK_STEP  k - k0 + 1 of the first step that attains it
+ *   RECOVERY     1 + (the last window step with |e_k| > band) - k0, 0 if there is none; the window's length: not recovered
+ *   IAE          sum |e_k|            ITAE       sum (double)(k - k0 + 1) * |e_k|
+ *   ACTION_PEAK  max |a_c(k) - a_c(k0 - 1)|, a_c(-1) := 0.0
+ * A segment with k0 >= its steps holds NaN in all seven; the summary does not count them.  With d_u = 0 and unit multipliers, for
+ * any ONSET and LENGTH, the first PIME_METRIC_ROWS rows are bit for bit a lane of pime_rollout_eval_metrics from the same lane state.
+ *   kind, md, packed_actor, priorK: as pime_rollout_eval (priorK [host] float64[D])
+ *   disturb  [dev] float64[P, PIME_DISTURB_COLS]
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   pairs    [dev] float64[n_segments, PIME_METRIC_ROWS + PIME_DISTURB_ROWS, P, N] or NULL
+ *   summary  [dev] float64[P, n_segments, PIME_METRIC_ROWS + PIME_DISTURB_ROWS, PIME_SWEEP_STATS]: each row over the N plants, EXACTLY
+ *            the statistics and the addition order of pime_prior_sweep's summary
+ *   actions  [dev] float64[n_steps, P, N] or NULL: a_c                   outputs  [dev] float64[n_steps, P, N] or NULL: y after the step
+ *            NULL pairs / actions / outputs is the normal use and does not change a bit of summary.
+ *   workspace [dev] pime_disturb_sweep_workspace_bytes(env, P, n_steps, seg_len) bytes (-1: bad arguments); private layout, every
+ *            byte read was written by the same call
+ * The tiling is pime_margin_sweep's (one 16-lane tile of ONE row per wave: the row is wave-uniform; the prior alone runs 64 distinct
+ * pairs per wave; a finishing launch reduces the rows per disturbance).  The handle is READ and never written (state, counters,
+ * observations bit-unchanged), but must have been reset.  Asynchronous on the caller's stream, capturable, no allocation, no
+ * synchronisation, no atomics: two calls give the same bits; a pair's result does not depend on P, N or its position in the grid.
+ * Served (pime_disturb_sweep_supported == 1): exactly the classes of pime_margin_sweep.  Width 256, PIME_STATE_MIXED16 handles and the
+ * tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: the refused classes, P < 1, P * N > 2^31 - 1, NULL disturb /
+ * summary / workspace / priorK (and packed_actor with a policy), and the schedule / band / tail cases of pime_rollout_eval_metrics. */
+enum pime_disturb_col { PIME_DISTURB_ONSET = 0, PIME_DISTURB_LENGTH = 1, PIME_DISTURB_LOAD = 2, PIME_DISTURB_M0 = 3, PIME_DISTURB_M1 = 4,
+                        PIME_DISTURB_M2 = 5, PIME_DISTURB_COLS = 6 };
+enum pime_disturb_row { PIME_DISTURB_E0 = 0, PIME_DISTURB_PEAK = 1, PIME_DISTURB_PEAK_STEP = 2, PIME_DISTURB_RECOVERY = 3,
+                        PIME_DISTURB_IAE = 4, PIME_DISTURB_ITAE = 5, PIME_DISTURB_ACTION_PEAK = 6, PIME_DISTURB_ROWS = 7 };
+int pime_disturb_sweep_supported(const pime_env* env, int32_t kind, int32_t md);
+int64_t pime_disturb_sweep_workspace_bytes(const pime_env* env, int32_t P, int32_t n_steps, int32_t seg_len);
+int pime_disturb_sweep(const pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                       const double* disturb, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                       int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
+                       double* outputs, void* workspace, pime_stream stream);
+
 /* -- fused off-policy exploration-----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with
  * AgentTD3.select_action (:300-306: a = (act(s) + N(0, explore_noise)).clamp(-1, 1)), env.step, and ReplayBuffer.append_buffer

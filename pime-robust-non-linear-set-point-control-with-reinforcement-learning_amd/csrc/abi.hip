@@ -15,6 +15,7 @@
 #include "prior_sweep.hpp"
 #include "mpc_eval.hpp"
 #include "margin_sweep.hpp"
+#include "disturb_sweep.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -257,7 +258,7 @@ int h2d_from_double(const FieldRef& f, int n, const double* in, hipStream_t s) {
 
 }  // namespace
 
-// ---- the plant-grid calls (rollout_eval, prior_sweep, mpc_eval, margin_sweep; replay_error in part): one host path ----------------
+// ---- the plant-grid calls (rollout_eval, prior_sweep, mpc_eval, margin_sweep, disturb_sweep; replay_error in part): one host path -
 // f(ph, wt) on the handle's state pointers in its state's precision (PIME_STATE_F64: double, else float), so an entry point names its
 // arguments once; inside f the precision is state_scalar_t<decltype(ph)>
 template <typename F>
@@ -267,7 +268,7 @@ static int with_state(const pime_env* e, const F& f) {
 template <typename Ph>
 using state_scalar_t = std::remove_pointer_t<decltype(std::declval<Ph>().r)>;   // (PhPtrs<S>::r is S*)
 
-// what EvalArgs, SweepArgs, MpcArgs and MarginArgs have in common, by member name: the handle's lanes, without auto-reset
+// what EvalArgs, SweepArgs, MpcArgs, MarginArgs and DisturbArgs have in common, by member name: the handle's lanes, without auto-reset
 template <typename A, typename Ph, typename Wt>
 static void fill_grid_args(A& a, const pime_env* e, const Ph& ph, const Wt& wt) {
     a.env = e->cfg.kind == PIME_ENV_PH ? 0 : 1;
@@ -1093,6 +1094,53 @@ int pime_margin_sweep(const pime_env* e, int32_t kind, int32_t md, const float* 
         fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
         return launch_margin_sweep<S>(kind, md, a, perturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
                                       static_cast<hipStream_t>(stream));
+    });
+}
+
+// ---- disturbance-rejection sweep (disturb_sweep.hip) -------------------------------------------------------------------------------
+int pime_disturb_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
+
+int64_t pime_disturb_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    if (!pime_disturb_sweep_supported(e, -1, 0) || P < 1 || n_steps < 1 || seg_len < 0 || (long long)P * e->cfg.n_envs > 2147483647LL ||
+        sweep_segments(n_steps, seg_len) > kMaxSetpoints) {
+        set_error("pime_disturb_sweep_workspace_bytes: not served, P %d < 1, P x N > 2^31 - 1, n_steps %d < 1, seg_len %d < 0 or more than "
+                  "%d segments", P, n_steps, seg_len, kMaxSetpoints);
+        return -1;
+    }
+    return (int64_t)disturb_workspace_doubles(P, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
+}
+
+int pime_disturb_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                       const double* disturb, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                       int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
+                       double* outputs, void* workspace, pime_stream stream) {
+    const char* fn = "pime_disturb_sweep";
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    PIME_REQUIRE(e->cfg.state_mode == PIME_STATE_F64 || e->cfg.state_mode == PIME_STATE_MIXED,
+                 "%s: state_mode %d is not served (PIME_STATE_F64 or PIME_STATE_MIXED; PIME_STATE_MIXED16 is refused)", fn,
+                 (int)e->cfg.state_mode);
+    PIME_REQUIRE(e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0,
+                 "%s: the Stacking observation (num_stack %d) is not served (pH or the Integrator water tank)", fn, (int)e->cfg.num_stack);
+    PIME_REQUIRE(kind == -1 || md != 256, "%s: md %d is not served (64 or 128; width 256 is the streamed family)", fn, md);
+    PIME_REQUIRE(pime_disturb_sweep_supported(e, kind, md), "%s: not served for actor kind %d width md %d (pime_disturb_sweep_supported)",
+                 fn, kind, md);
+    if (int rc = check_disturb_args(fn, e->cfg.n_envs, priorK, disturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary))
+        return rc;
+    PIME_REQUIRE(kind == -1 || packed_actor != nullptr, "%s: packed_actor is NULL", fn);
+    PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
+    if (int rc = use_device(e)) return rc;
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        DisturbArgs<S> a{};
+        fill_grid_args(a, e, ph, wt);
+        a.P = P;
+        a.n_seg = sweep_segments(n_steps, seg_len);
+        a.img = packed_actor;
+        for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
+        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+        return launch_disturb_sweep<S>(kind, md, a, disturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
+                                       static_cast<hipStream_t>(stream));
     });
 }
 

@@ -1,5 +1,5 @@
-// What the host builds of the plant-grid calls share (prior_sweep_host.hip, mpc_eval_host.hip, margin_sweep_host.hip; the error
-// buffer also replay_error_host.hip): the last-error buffer, the opening checks of an entry point, a lane of pime_sweep_lanes as the
+// What the host builds of the plant-grid calls share (prior_sweep_host.hip, mpc_eval_host.hip, margin_sweep_host.hip,
+// disturb_sweep_host.hip; the error buffer also replay_error_host.hip): the last-error buffer, the opening checks of an entry point, a lane of pime_sweep_lanes as the
 // register copy the pair / plant functions take, the metric-row sink and THE host statement of the summary's order of additions.
 // Host only and test infrastructure like the libraries that include it; each of them is one translation unit, so set_error is
 // defined here.

@@ -39,6 +39,12 @@ SWEEP_STATS = ("sum", "min", "max", "argmax", "finite")
 PERTURB_NAMES = ("gain", "delay", "sigma")
 PERTURB_COLS = len(PERTURB_NAMES)
 MARGIN_MAX_DELAY = 8
+# pime_disturb_sweep: the columns of a disturbance row (enum pime_disturb_col) and the rejection rows it adds behind METRIC_NAMES
+# (enum pime_disturb_row), in order
+DISTURB_COL_NAMES = ("onset", "length", "load", "m0", "m1", "m2")
+DISTURB_COLS = len(DISTURB_COL_NAMES)
+DISTURB_ROW_NAMES = ("e0", "peak", "peak_step", "recovery", "iae", "itae", "action_peak")
+DISTURB_ROWS = len(DISTURB_ROW_NAMES)
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -187,6 +193,10 @@ _SIGNATURES = {
     "pime_margin_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
     "pime_margin_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.c_uint64, C.c_uint32, _i32, _i32, _vp, _i32, C.c_double,
                                     _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pime_disturb_sweep_supported": (C.c_int, [_vp, _i32, _i32]),
+    "pime_disturb_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
+    "pime_disturb_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
     "pime_mpc_eval": (C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,

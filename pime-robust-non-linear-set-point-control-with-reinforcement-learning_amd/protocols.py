@@ -42,7 +42,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .native import BAND_SIGNALS, BAND_STATS, ENV_PH, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
+from .native import BAND_SIGNALS, BAND_STATS, DISTURB_ROW_NAMES, ENV_PH, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -641,4 +641,80 @@ def loop_margins(result, cost="itae", factor=2.0):
             idx = order[name]
             key = "plant_" + (name + "_margin" if name != "gain_low" else "gain_margin_low")
             out[key] = np.array([_last_ok(vals[idx], ok_p[idx, i]) for i in range(ok_p.shape[1])])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ disturbance rejection
+def disturbance_grid(onset, loads=(), m0=(), m1=(), m2=(), length=0):
+    """The rows of `disturbance_rejection` / `VecControlEnv.disturbance_sweep`: the nominal row (onset, length, 0, 1, 1, 1) first, then
+    one row per value, one axis at a time -- the loads, then the multipliers of the first, second and third plant parameter (pH:
+    qww_V, qc_V; tank: a1, a2, Kp) -- every other column nominal.  float64 [P, 6], columns native.DISTURB_COL_NAMES."""
+    rows = [[onset, length, 0.0, 1.0, 1.0, 1.0]]
+    for col, values in ((2, loads), (3, m0), (4, m1), (5, m2)):
+        for v in np.asarray(values, dtype=np.float64).reshape(-1):
+            row = [onset, length, 0.0, 1.0, 1.0, 1.0]
+            row[col] = float(v)
+            rows.append(row)
+    return np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
+
+
+def disturbance_rejection(env, rows, agent=None, axes=None, plants=None, setpoints=None, steps=None, band=None, tail=10, want_pairs=False):
+    """How well does the closed loop reject a load at the plant input or a step of the plant's parameters?  The step-response
+    protocol of `env` (as `step_response_metrics`: the same start, set-points, steps, band and tail) under every row (onset, length,
+    load, m0, m1, m2) of `rows` [P, 6] (`disturbance_grid`), over the plants in the env's lanes, in ONE call
+    (`VecControlEnv.disturbance_sweep`): the disturbance comes back at step `onset` of every set-point segment.  agent None: the prior
+    controller alone, else an agent the fused evaluation serves.  axes: a plant grid as `robust_grid` takes it, or plants [N, P]:
+    written into the lanes; neither: every lane keeps the plant its reset draws.  Returns a dict for `rejection_summary`: rows
+    [P, 6], summary [P, n_segments, 15, 5] (rows `METRIC_NAMES` then `DISTURB_ROW_NAMES`, stats `SWEEP_STATS`), pairs
+    [n_segments, 15, P, N] and actions, outputs [T, P, N], or None, steps, setpoints, band, tail, n (the plants)."""
+    from .vec_env import check_disturb
+    is_ph = env.kind == ENV_PH
+    rows = check_disturb(rows, is_ph)
+    if axes is not None:
+        plants = _grid(env, axes, "disturbance_rejection")[3]
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    fused = _fused_policy(env, None, agent)
+    if fused is None or not hasattr(env, "disturbance_supported") or not env.disturbance_supported(fused[0]):
+        raise ValueError("disturbance_rejection: the disturbance sweep does not serve this env / agent (VecControlEnv.disturbance_supported)")
+    _protocol_start(env, is_ph, steps, plants)
+    out = env.disturbance_sweep(fused[0], fused[1], rows, len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band,
+                                tail=tail, want_pairs=want_pairs, want_trace=want_pairs)
+    host = lambda v: None if v is None else v.cpu().numpy()
+    summary, pairs, actions, outputs = (out["summary"], out["pairs"], out["actions"], out["outputs"]) if want_pairs else (out, None, None, None)
+    return dict(rows=rows, summary=host(summary), pairs=host(pairs), actions=host(actions), outputs=host(outputs), steps=int(steps),
+                setpoints=setpoints, band=band, tail=tail, n=int(env.num_envs))
+
+
+def rejection_summary(result):
+    """A `disturbance_rejection` result per row, over the plants and the segments the row starts in: dict of float64 [P] --
+      worst_peak, worst_recovery, worst_iae   the worst plant's peak error, recovery step and IAE from the onset (the largest over the
+                                              segments);
+      recovered                               the share of (plant, segment) pairs whose recovery step is smaller than the window's length
+                                              (needs `pairs`; without them 1.0 / 0.0 from the worst plant per segment);
+      worst_e0                                the largest |error| a disturbance met at its onset: had the loop settled?
+    NaN where the row starts in no segment."""
+    summary = np.asarray(result["summary"], dtype=np.float64)
+    rows, steps = np.asarray(result["rows"], dtype=np.float64), int(result["steps"])
+    st = {name: j for j, name in enumerate(SWEEP_STATS)}
+    at = {name: len(METRIC_NAMES) + j for j, name in enumerate(DISTURB_ROW_NAMES)}
+    P = summary.shape[0]
+    window = np.maximum(steps - rows[:, 0], 0.0)                                  # [P] (disturbance_rejection runs whole segments)
+    seen = summary[:, :, at["peak"], st["finite"]] > 0                            # [P, S]
+    worst = lambda name: np.where(seen.any(axis=1), np.where(seen, summary[:, :, at[name], st["max"]], -np.inf).max(axis=1), np.nan)
+    e0 = np.maximum(np.abs(summary[:, :, at["e0"], st["min"]]), np.abs(summary[:, :, at["e0"], st["max"]]))
+    out = dict(worst_peak=worst("peak"), worst_recovery=worst("recovery"), worst_iae=worst("iae"),
+               worst_e0=np.where(seen.any(axis=1), np.where(seen, e0, -np.inf).max(axis=1), np.nan))
+    pairs = result.get("pairs")
+    if pairs is not None:
+        rec = np.asarray(pairs, dtype=np.float64)[:, at["recovery"]]              # [S, P, N]
+        counted = np.isfinite(rec)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["recovered"] = (counted & (rec < window[None, :, None])).sum(axis=(0, 2)) / counted.sum(axis=(0, 2))
+    else:
+        ok = np.where(seen, summary[:, :, at["recovery"], st["max"]] < window[:, None], False)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["recovered"] = np.where(seen.any(axis=1), ok.sum(axis=1) / seen.sum(axis=1), np.nan)
+    assert all(v.shape == (P,) for v in out.values())
     return out

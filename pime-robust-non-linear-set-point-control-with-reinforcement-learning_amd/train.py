@@ -89,6 +89,11 @@ def build_parser():
     p.add_argument("--margins_points", default=0, type=int,
                    help="--margins: instead of the --robust_test plants, a grid of this many points per plant parameter over the "
                         "env's ensemble ranges")
+    p.add_argument("--disturbances", action="store_true",
+                   help="after training: load steps at the plant input and steps of the plant's parameters (trained agent AND prior "
+                        "alone) on the plants of --robust_test, one launch each; writes disturbances.npz into the run directory")
+    p.add_argument("--disturbance_onset", default=-1, type=int, metavar="K",
+                   help="--disturbances: the step within every set-point segment at which the disturbance starts (default: half a segment)")
     p.add_argument("--mpc_model", default=None, type=str, metavar="FILE.npz",
                    help="--mpc_baseline (tank only): control every plant on FILE's `best` plant (an identified.npz of --identify)")
     p.add_argument("--prior_K", default=None, type=str, metavar="FILE.npz",
@@ -374,6 +379,59 @@ def margins(args, agent, cwd):
     return path
 
 
+DISTURBANCE_LOADS = (-0.2, -0.1, 0.1, 0.2)
+DISTURBANCE_MULTIPLIERS = (0.7, 0.85, 1.2, 1.5)
+
+
+def disturbances(args, agent, cwd):
+    """--disturbances: from step --disturbance_onset of every set-point segment to its end, a load on the controller's output (+-0.1,
+    +-0.2 of the action range) or a step of one plant parameter (x 0.7 .. 1.5), one axis at a time around the nominal row, on every
+    plant of --robust_test's plant set under the step-response protocol of --robust_test; one launch for the trained agent and one for
+    the prior controller alone (protocols.disturbance_rejection / rejection_summary).  Writes <cwd>/disturbances.npz -- rows, plants
+    and per controller (prefix agent_ / prior_) summary and the rejection summary -- and prints one line per row for each."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("disturbances skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    onset = int(args.disturbance_onset) if int(getattr(args, "disturbance_onset", -1)) >= 0 else steps // 2
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    m = DISTURBANCE_MULTIPLIERS
+    grid = protocols.disturbance_grid(onset, loads=DISTURBANCE_LOADS, m0=m, m1=m, m2=() if is_ph else m)
+    out, found = {}, {}
+    for who, ag in (("agent", agent), ("prior", None)):
+        env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        fused = protocols._fused_policy(env, None, ag)
+        if fused is None or not hasattr(env, "disturbance_supported") or not env.disturbance_supported(fused[0]):
+            env.close()
+            print(f"disturbances skipped for the {who}: the disturbance sweep does not serve this env / actor (disturbance_supported)")
+            continue
+        res = protocols.disturbance_rejection(env, grid, agent=ag, plants=plants, setpoints=setpoints, steps=steps, band=band, tail=tail,
+                                              want_pairs=True)
+        env.close()
+        found[who] = protocols.rejection_summary(res)
+        out[f"{who}_summary"] = res["summary"]
+        for k, v in found[who].items():
+            out[f"{who}_{k}"] = np.asarray(v)
+    if not found:
+        return None
+    path = os.path.join(cwd, "disturbances.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, rows=grid, plants=plants, setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, band=band, tail=tail,
+             onset=onset, metric_names=np.asarray(protocols.METRIC_NAMES + protocols.DISTURB_ROW_NAMES), **out)
+    print(f"disturbances: {len(grid)} rows x {len(plants)} plants, onset at step {onset} of {steps} -> {path}")
+    for who, r in found.items():
+        for p, row in enumerate(grid):
+            print(f"{who} load {row[2]:+g} m ({row[3]:g}, {row[4]:g}, {row[5]:g}): worst peak {r['worst_peak'][p]:.4g}, recovery "
+                  f"{r['worst_recovery'][p]:g} steps, IAE {r['worst_iae'][p]:.4g}, recovered {r['recovered'][p]:.2f}, |e0| {r['worst_e0'][p]:.3g}")
+    return path
+
+
 def apply_prior_K(env, path):
     """--prior_K FILE.npz: FILE's best_gain (the env's sign: a = -obs @ K) becomes the env's K -- and that of its clones (the
     evaluation env of an off-policy run) -- before the residual agent reads it."""
@@ -448,6 +506,8 @@ def main(argv=None):
             mpc_baseline(args, kargs.cwd, robust_path)
         if args.margins:
             margins(args, agent, kargs.cwd)
+        if args.disturbances:
+            disturbances(args, agent, kargs.cwd)
     return agent
 
 

@@ -115,7 +115,28 @@ def check_perturb(perturb):
     return np.ascontiguousarray(rows)
 
 
-_EVAL_KINDS = {"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR, "sac_actor": native.MLP_SAC_ACTOR,
+def check_disturb(rows, is_ph):
+    """The rows of `VecControlEnv.disturbance_sweep` as float64 [P, 6] (columns native.DISTURB_COL_NAMES), or ValueError: the shape, an
+    onset or a length that is not a non-negative integer, a load that is not finite, a multiplier that is not finite and > 0, M2 != 1
+    on pH (it has two plant parameters)."""
+    rows = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != native.DISTURB_COLS or rows.shape[0] < 1:
+        raise ValueError(f"disturbance_sweep: rows {tuple(rows.shape)} must be [P >= 1, {native.DISTURB_COLS}]")
+    for j, name in ((0, "onset"), (1, "length")):
+        v = rows[:, j]
+        if not np.all(np.isfinite(v)) or np.any(v != np.rint(v)) or np.any(v < 0):
+            raise ValueError(f"disturbance_sweep: {name} must be a non-negative integer")
+    if not np.all(np.isfinite(rows[:, 2])):
+        raise ValueError("disturbance_sweep: a load is not finite")
+    m = rows[:, 3:6]
+    if not np.all(np.isfinite(m)) or np.any(m <= 0):
+        raise ValueError("disturbance_sweep: a multiplier is not finite and > 0")
+    if is_ph and np.any(rows[:, 5] != 1.0):
+        raise ValueError("disturbance_sweep: m2 must be 1 on pH (two plant parameters: qww_V, qc_V)")
+    return np.ascontiguousarray(rows)
+
+
+_EVAL_KINDS ={"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR, "sac_actor": native.MLP_SAC_ACTOR,
                "critic": native.MLP_CRITIC}
 
 
@@ -681,6 +702,61 @@ class VecControlEnv:
             self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(pt), P, C.c_uint64(int(noise_seed)),
             C.c_uint32(int(noise_epoch)), n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail), native.ptr(pairs),
             native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()), "pime_margin_sweep")
+        del workspace
+        if not (want_pairs or want_trace):
+            return summary
+        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+
+    # -- disturbance-rejection sweep (load and plant-parameter steps) -------------------------------------------------
+    def disturbance_supported(self, packed_actor=None):
+        """Does `disturbance_sweep` serve this env (with this packed actor, or the prior controller alone)?
+        (pime_disturb_sweep_supported: the classes of `margin_sweep`.)"""
+        if self.draws.injects:
+            return False
+        if packed_actor is None:
+            return bool(self._lib.pime_disturb_sweep_supported(self._h, -1, 0))
+        if packed_actor.kind not in _EVAL_KINDS or packed_actor.D != self.obs_dim:
+            return False
+        return bool(self._lib.pime_disturb_sweep_supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
+
+    def disturbance_sweep(self, packed_actor, priorK, rows, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_pairs=False,
+                          want_trace=False):
+        """A grid of DISTURBANCES over every lane's plant in ONE call (pime_disturb_sweep, csrc/disturb_sweep.hip): every (row, lane)
+        pair runs the loop of `rollout_eval_metrics` from the lane state as it stands; from step `onset` of every segment, for
+        `length` steps (0: to the segment's end), `load` is added to the controller's output in front of the actuator and the plant's
+        parameters are multiplied by m0, m1, m2 (pH: qww_V, qc_V; tank: a1, a2, Kp) -- rows float64 [P, 6], columns
+        native.DISTURB_COL_NAMES.  packed_actor None = the prior controller alone.  Returns summary float64 [P, n_segments, 15, 5]
+        -- per row, segment and metric row (native.METRIC_NAMES, then native.DISTURB_ROW_NAMES over the steps from the onset: the
+        error the onset met, peak error and its step, recovery step for `band`, IAE, ITAE, the largest move of the controller's
+        output) the stats native.SWEEP_STATS over the lanes, exactly as `prior_sweep`; a segment the row never starts in holds NaN and
+        is not counted -- or, with `want_pairs` and / or `want_trace`, a dict with "summary", "pairs" float64 [n_segments, 15, P, N]
+        and "actions", "outputs" float64 [n_steps, P, N] (the CONTROLLER's output -- the applied action is that plus the load while
+        the row is active -- and the controlled output after each step).  ValueError for a bad row (`check_disturb`); a device tensor
+        is taken as given, so a capture works.  The env itself is read, never advanced (definitions in include/pime_hip.h)."""
+        if torch.is_tensor(rows) and rows.is_cuda:
+            dt = rows
+            if dt.dtype != torch.float64 or dt.dim() != 2 or dt.shape[1] != native.DISTURB_COLS or dt.shape[0] < 1 or not dt.is_contiguous():
+                raise ValueError(f"disturbance_sweep: a device tensor of rows must be contiguous float64 [P >= 1, {native.DISTURB_COLS}]")
+        else:
+            dt = torch.as_tensor(check_disturb(rows, self.kind == native.ENV_PH), dtype=torch.float64).to(self.device).contiguous()
+        k = self._prior_row(priorK)
+        P, n_steps, seg_len = int(dt.shape[0]), int(n_steps), int(seg_len)
+        ws_bytes = int(self._lib.pime_disturb_sweep_workspace_bytes(self._h, P, n_steps, seg_len))
+        if ws_bytes < 0:
+            raise native.PimeError(f"pime_disturb_sweep_workspace_bytes: {native.last_error()}")
+        kind, md, img = self._actor_triple(packed_actor)
+        N, R = self.num_envs, native.METRIC_ROWS + native.DISTURB_ROWS
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
+        summary = torch.empty((P, n_seg, R, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
+        pairs = torch.empty((n_seg, R, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
+        actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
+        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
+        native.check(self._lib.pime_disturb_sweep(
+            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(dt), P, n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail),
+            native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()),
+            "pime_disturb_sweep")
         del workspace
         if not (want_pairs or want_trace):
             return summary

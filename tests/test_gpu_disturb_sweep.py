@@ -1,0 +1,312 @@
+"""The disturbance-rejection sweep on the GPU (pime_disturb_sweep, csrc/disturb_sweep.hip) against tests/disturb_sweep.py.  Shapes: 81
+plants on a handle at lane offset 1000 (six 16-lane tiles per row, the last one with a single plant; two 64-lane tiles under the prior
+alone), the seven rows of tests/disturb_sweep.py, 23 steps in segments of 9 (the last one ragged), tail 4.
+  1. all 36 served classes (2 envs x {prior, 4 policy kinds x widths 64, 128} x float64 / mixed state): the eight rows of rows 1 and 7
+     bit-equal to pime_rollout_eval_metrics from the same lane state, every row through the checker, summary bit-equal to
+     summary_from_pairs(pairs); also N = 130 (three summary blocks) with the prior alone;
+  2. the handle's fields are bit-unchanged, two calls give equal bits, a NaN-filled workspace gives the same bits, NULL pairs /
+     actions / outputs leave summary unchanged, a tile's pairs give the same bits alone (P = 1, N = 16) as inside the grid, one
+     captured replay gives equal bits;
+  3. float64, the prior alone: device bit-equal to the host build (the tank with process noise off; pH on the rows with M0 == 1);
+  4. every refusal and its message;
+  5. protocols.disturbance_rejection / rejection_summary on the three WT_ROBUST_PLANTS with a shortened protocol;
+  6. train.py --disturbances writes disturbances.npz on a toy run and is skipped on a Stacking id."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import disturb_sweep as D
+import prior_sweep as P
+from rollout_replay import DEV
+from test_gpu_margin_sweep import CLASSES, FIELDS, KINDS, _cfg, _make_env, _policy      # the handles, policies and classes of that sweep
+
+pytestmark = pytest.mark.gpu
+
+
+def _lanes(env, kind):
+    out = {k: np.ascontiguousarray(env.get_field(k)) for k in FIELDS[kind] + (("qww_V", "qc_V") if kind == "ph" else ())}
+    out["t"], out["episode"] = out["t"].astype(np.int32), out["episode"].astype(np.int32)
+    return out
+
+
+def _run(env, kind, pk, K, rows=None, pairs=True, trace=True, **kw):
+    args = dict(n_steps=D.N_STEPS, seg_len=D.SEG, setpoints=D.SETPOINTS[kind], band=D.BAND, tail=D.TAIL)
+    args.update(kw)
+    n_steps = args.pop("n_steps")
+    out = env.disturbance_sweep(pk, K, D.DISTURB[kind] if rows is None else rows, n_steps, want_pairs=pairs, want_trace=trace, **args)
+    torch.cuda.synchronize()
+    if not (pairs or trace):
+        return dict(summary=out.cpu().numpy())
+    return {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+
+
+# ---- 1. every served class -------------------------------------------------------------------------------------------------------
+def test_the_cases_are_the_served_classes():
+    from pime_amd import gym_control, native
+    served = set()
+    for kind, name in (("ph", gym_control.PH_V35), ("wt", gym_control.WT_INTEGRATOR), ("stacking", gym_control.WT_STACKING.format(4))):
+        for sm in ("f64", "mixed", "mixed16"):
+            env = gym_control.make_vec(name, 4, device=DEV, state_mode=sm, seed=D.SEED)
+            assert env.disturbance_supported() == bool(native.lib().pime_disturb_sweep_supported(env._h, -1, 0))
+            for pol, code in KINDS.items():
+                for md in ((0,) if pol == "prior" else (64, 128, 256)):
+                    if native.lib().pime_disturb_sweep_supported(env._h, code, md):
+                        served.add((kind, pol, md, sm))
+            env.close()
+    assert served == set(CLASSES) and len(CLASSES) == 36
+
+
+@pytest.mark.parametrize("kind,pol,md,state_mode", CLASSES, ids=lambda v: str(v))
+def test_every_served_class(kind, pol, md, state_mode, ph_table_oracle):
+    env, twin = _make_env(kind, state_mode), _make_env(kind, state_mode)
+    pk, K, term = _policy(pol, env, md)
+    assert env.disturbance_supported(pk)
+    cfg, keep = _cfg(env, kind, ph_table_oracle)
+    lanes = _lanes(env, kind)
+    rec = _run(env, kind, pk, K)
+    assert rec["pairs"].shape == (3, 15, 7, D.N) and rec["actions"].shape == rec["outputs"].shape == (D.N_STEPS, 7, D.N)
+    _, want, _ = twin.rollout_eval_metrics(pk, K, D.N_STEPS, setpoints=D.SETPOINTS[kind], seg_len=D.SEG, band=D.BAND, tail=D.TAIL)
+    want = want.cpu().numpy()
+    for p in (0, 6):
+        assert D.bits_equal(rec["pairs"][:, :8, p], want), f"the undisturbed row {p} is not bit-equal to pime_rollout_eval_metrics"
+    use = D.check_recording(kind, cfg, lanes, ph_table_oracle, rec, K=K, policy=term, tag=f"{kind}-{pol}{md}-{state_mode}")
+    P.check_summary(rec["summary"], rec["pairs"], tag=f"{kind}-{pol}{md}-{state_mode}")
+    assert (rec["summary"][4, 2, 8:, P.FINITE] == 0).all() and (rec["summary"][4, 2, :8, P.FINITE] == D.N).all()
+    print(f"\nDISTURB id={kind}-{pol}{md}-{state_mode} share of the bars: trajectory {use['trajectory']:.3g} return {use['ret']:.3g} action "
+          f"{use['action']:.3g} (gap {use['gap']:.4g})")
+    env.close(); twin.close()
+
+
+def test_three_summary_blocks():
+    env = _make_env("wt", "mixed", n=130)
+    rec = _run(env, "wt", None, -env.K, trace=False)
+    P.check_summary(rec["summary"], rec["pairs"], tag="N = 130")
+    counted = rec["summary"][..., P.FINITE]
+    assert ((counted == 130) | (counted == 0)).all() and (counted[:, :, :8] == 130).all() and rec["summary"].shape == (7, 3, 15, 5)
+    env.close()
+
+
+# ---- 2. structure ----------------------------------------------------------------------------------------------------------------
+def _raw(env, kind_code, md, img, K, rows, Pn, n_steps, seg_len, sp, n_sp, band, tail, pairs, summary, actions, outputs, workspace):
+    import pime_amd.native as nt
+    rc = nt.lib().pime_disturb_sweep(env._h, kind_code, md, nt.ptr(img), nt.ptr(K), nt.ptr(rows), Pn, n_steps, seg_len, nt.ptr(sp), n_sp, band,
+                                     tail, nt.ptr(pairs), nt.ptr(summary), nt.ptr(actions), nt.ptr(outputs), nt.ptr(workspace), env._stream())
+    torch.cuda.synchronize()
+    return rc, nt.last_error()
+
+
+@pytest.mark.parametrize("kind,pol,md,state_mode", [("wt", "modular", 128, "mixed"), ("ph", "prior", 0, "f64"), ("ph", "sac", 64, "mixed"),
+                                                   ("wt", "prior", 0, "mixed")], ids=lambda v: str(v))
+def test_the_handle_is_untouched_and_the_outputs_are_independent(kind, pol, md, state_mode):
+    import pime_amd.native as nt
+    env, twin = _make_env(kind, state_mode), _make_env(kind, state_mode)
+    pk, K, _ = _policy(pol, env, md)
+    before = _lanes(env, kind)
+    counters = (env._t_all, env._was_reset, env.reset_count)
+    obs0 = env.obs.clone()
+    first, second = _run(env, kind, pk, K), _run(env, kind, pk, K)
+    assert all(D.bits_equal(first[k], second[k]) for k in first), "two calls must be bit-identical"
+    quiet = _run(env, kind, pk, K, pairs=False, trace=False)
+    assert D.bits_equal(quiet["summary"], first["summary"]), "NULL pairs / actions / outputs must not change a bit of summary"
+    # the raw call with a NaN-filled workspace: pairs NULL (the finishing launch reads the workspace copy) and pairs given
+    ws_bytes = nt.lib().pime_disturb_sweep_workspace_bytes(env._h, 7, D.N_STEPS, D.SEG)
+    assert ws_bytes == 3 * 15 * 7 * D.N * 8
+    Kd = np.ascontiguousarray(K, dtype=np.float64)
+    dt = torch.as_tensor(D.DISTURB[kind], dtype=torch.float64, device=DEV).contiguous()
+    sp = np.ascontiguousarray(D.SETPOINTS[kind], dtype=np.float64)
+    code, img = (-1, None) if pk is None else (KINDS[pol], pk.packed)
+    for with_pairs in (False, True):
+        ws = torch.full((ws_bytes // 8,), float("nan"), dtype=torch.float64, device=DEV)
+        summary = torch.full((7, 3, 15, 5), float("nan"), dtype=torch.float64, device=DEV)
+        pairs = torch.full((3, 15, 7, D.N), float("nan"), dtype=torch.float64, device=DEV) if with_pairs else None
+        rc, msg = _raw(env, code, md, img, Kd, dt, 7, D.N_STEPS, D.SEG, sp, 3, D.BAND, D.TAIL, pairs, summary, None, None, ws)
+        assert rc == 0, msg
+        assert D.bits_equal(summary.cpu().numpy(), first["summary"]), "a NaN-filled workspace must not change a bit"
+        if with_pairs:
+            assert D.bits_equal(pairs.cpu().numpy(), first["pairs"])
+    after = _lanes(env, kind)
+    for k in before:
+        assert D.bits_equal(before[k].astype(np.float64), after[k].astype(np.float64)), k
+    assert (env._t_all, env._was_reset, env.reset_count) == counters and env._t_lanes is None
+    assert torch.equal(env.obs, obs0)
+    a = torch.full((D.N,), 0.25, dtype=torch.float64, device=DEV)
+    got, want = env.step(a, auto_reset=False), twin.step(a, auto_reset=False)
+    assert all(torch.equal(g, w) for g, w in zip(got, want)), "the next step equals that of an env that never ran the sweep"
+    env.close(); twin.close()
+
+
+@pytest.mark.parametrize("kind,pol,md,state_mode", [("wt", "modular", 128, "mixed"), ("ph", "plain", 64, "f64"), ("wt", "prior", 0, "f64")],
+                         ids=lambda v: str(v))
+def test_a_tile_alone_gives_the_bits_it_gives_inside_the_grid(kind, pol, md, state_mode):
+    big, small = _make_env(kind, state_mode), _make_env(kind, state_mode, n=16, offset=D.OFFSET + 32)
+    for k in FIELDS[kind]:
+        if k not in ("t", "episode"):
+            assert D.bits_equal(big.get_field(k)[32:48], small.get_field(k)), "the same global lanes draw the same state"
+    pk, K, _ = _policy(pol, big, md)
+    a = _run(big, kind, pk, K)
+    b = _run(small, kind, pk, K, rows=D.DISTURB[kind][3:4])
+    for k in ("pairs", "actions", "outputs"):
+        assert D.bits_equal(a[k][..., 3:4, 32:48], b[k]), k
+    big.close(); small.close()
+
+
+@pytest.mark.parametrize("kind,pol,md", [("wt", "modular", 128), ("ph", "prior", 0)], ids=lambda v: str(v))
+def test_captured_in_a_graph_and_replayed(kind, pol, md):
+    import pime_amd.native as nt
+    env = _make_env(kind, "mixed")
+    pk, K, _ = _policy(pol, env, md)
+    want = _run(env, kind, pk, K)
+    dt = torch.as_tensor(D.DISTURB[kind], dtype=torch.float64, device=DEV).contiguous()   # uploaded (and validated) before the capture
+    graph = torch.cuda.CUDAGraph()
+    with nt.capture_guard(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        out = env.disturbance_sweep(pk, K, dt, D.N_STEPS, setpoints=D.SETPOINTS[kind], seg_len=D.SEG, band=D.BAND, tail=D.TAIL,
+                                    want_pairs=True, want_trace=True)
+    for x in out.values():
+        x.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize()
+    got = {k: v.cpu().numpy() for k, v in out.items()}
+    assert all(D.bits_equal(got[k], want[k]) for k in want)
+    env.close()
+
+
+# ---- 3. the host build -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["ph", "wt"])
+def test_float64_prior_is_bit_equal_to_the_host_build(kind, ph_table_oracle):
+    env = _make_env(kind, "f64", **({"noise_scale": 0.} if kind == "wt" else {}))
+    cfg, keep = _cfg(env, kind, ph_table_oracle)
+    lanes = _lanes(env, kind)
+    K = np.asarray(-env.K, dtype=np.float64).reshape(-1)
+    rec = _run(env, kind, None, K)
+    host = D.host_disturb(kind, cfg, lanes, K=K)
+    exact = [p for p in range(7) if kind == "wt" or D.DISTURB[kind][p, 3] == 1.0]      # (M0 != 1 on pH: the device's exp and libm's)
+    assert len(exact) == (7 if kind == "wt" else 6)
+    for k in ("pairs", "actions", "outputs"):
+        assert D.bits_equal(rec[k][..., exact, :], host[k][..., exact, :]), f"{k} is not bit-equal to the host build's"
+    assert D.bits_equal(rec["summary"][exact], host["summary"][exact])
+    env.close()
+
+
+# ---- 4. refusals -----------------------------------------------------------------------------------------------------------------
+def test_unserved_handles_and_widths_are_refused():
+    from pime_amd import gym_control, native
+    dt = torch.as_tensor(D.DISTURB["wt"], dtype=torch.float64, device=DEV).contiguous()
+    ws = torch.zeros(15 * 7 * 8, dtype=torch.float64, device=DEV)
+    for name, sm, word in ((gym_control.PH_V35, "mixed16", "state_mode"), (gym_control.WT_INTEGRATOR, "mixed16", "state_mode"),
+                           (gym_control.WT_STACKING.format(1), "mixed", "Stacking"), (gym_control.WT_STACKING.format(10), "f64", "Stacking")):
+        env = gym_control.make_vec(name, 8, device=DEV, state_mode=sm, seed=D.SEED)
+        env.reset()
+        assert not env.disturbance_supported() and native.lib().pime_disturb_sweep_supported(env._h, -1, 0) == 0
+        assert native.lib().pime_disturb_sweep_workspace_bytes(env._h, 7, D.N_STEPS, 0) == -1
+        summary = torch.full((7, 1, 15, 5), -777.0, dtype=torch.float64, device=DEV)
+        K = np.zeros(env.obs_dim)
+        rc, msg = _raw(env, -1, 0, None, K, dt, 7, D.N_STEPS, 0, None, 0, D.BAND, D.TAIL, None, summary, None, None, ws)
+        assert rc == -1 and word in msg and "not served" in msg and (summary == -777.0).all(), (name, sm, rc, msg)
+        with pytest.raises(native.PimeError):
+            env.disturbance_sweep(None, K, [[0, 0, 0.1, 1, 1, 1]], D.N_STEPS)
+        env.close()
+    env = _make_env("wt", "mixed", n=8)
+    img = torch.zeros(16, dtype=torch.float32, device=DEV)
+    summary = torch.full((7, 1, 15, 5), -777.0, dtype=torch.float64, device=DEV)
+    for code in (0, 1, 2):
+        assert native.lib().pime_disturb_sweep_supported(env._h, code, 256) == 0
+        rc, msg = _raw(env, code, 256, img, np.zeros(4), dt, 7, D.N_STEPS, 0, None, 0, D.BAND, D.TAIL, None, summary, None, None, ws)
+        assert rc == -1 and "md 256" in msg and (summary == -777.0).all(), (code, rc, msg)
+    rc, msg = _raw(env, 7, 64, img, np.zeros(4), dt, 7, D.N_STEPS, 0, None, 0, D.BAND, D.TAIL, None, summary, None, None, ws)
+    assert rc == -1 and "kind 7" in msg
+    env.close()
+
+
+@pytest.mark.parametrize("kind", ["ph", "wt"])
+def test_argument_errors(kind):
+    env = _make_env(kind, "mixed", n=8, reset=False)
+    sp = np.ascontiguousarray(D.SETPOINTS[kind], dtype=np.float64)
+    K = np.ascontiguousarray(D.PRIOR_K[kind])
+    dt = torch.as_tensor(D.DISTURB[kind], dtype=torch.float64, device=DEV).contiguous()
+    summary = torch.full((7, 3, 15, 5), -777.0, dtype=torch.float64, device=DEV)
+    ws = torch.zeros(3 * 15 * 7 * 8, dtype=torch.float64, device=DEV)
+    base = dict(K=K, dt=dt, P=7, n_steps=D.N_STEPS, seg_len=D.SEG, sp=sp, n_sp=3, band=D.BAND, tail=D.TAIL, summary=summary, ws=ws, code=-1,
+                md=0, img=None)
+    call = lambda kw: _raw(env, kw["code"], kw["md"], kw["img"], kw["K"], kw["dt"], kw["P"], kw["n_steps"], kw["seg_len"], kw["sp"], kw["n_sp"],
+                           kw["band"], kw["tail"], None, kw["summary"], None, None, kw["ws"])
+    rc, msg = call(base)
+    assert rc == -4 and "before pime_env_reset" in msg and (summary == -777.0).all()
+    env.reset()
+    cases = [("P = 0", dict(P=0)), ("P = -3", dict(P=-3)), ("exceed 2^31 - 1", dict(P=2 ** 28)), ("disturb is NULL", dict(dt=None)),
+             ("summary is NULL", dict(summary=None)), ("workspace is NULL", dict(ws=None)), ("priorK is NULL", dict(K=None)),
+             ("packed_actor is NULL", dict(code=2, md=64)), ("band", dict(band=-1.0)), ("band", dict(band=float("nan"))),
+             ("band", dict(band=float("inf"))), ("tail 0", dict(tail=0)), ("n_steps 0", dict(n_steps=0)), ("n_setpoints 17", dict(n_sp=17)),
+             ("set-point schedule", dict(n_sp=2)), ("set-point schedule", dict(sp=None)), ("set-point schedule", dict(seg_len=-1))]
+    bad = []
+    for word, over in cases:
+        rc, msg = call(dict(base, **over))
+        if rc != -1 or word not in msg or "pime_disturb_sweep" not in msg or not (summary == -777.0).all():
+            bad.append((word, rc, msg))
+    assert not bad, bad
+    rc, msg = call(base)          # and the good call goes through
+    assert rc == 0 and not (summary == -777.0).any(), msg
+    bad_rows = [[[0.5, 0, 0, 1, 1, 1]], [[0, -1, 0, 1, 1, 1]], [[0, 0, float("nan"), 1, 1, 1]], [[0, 0, 0, 0, 1, 1]]]
+    if kind == "ph":
+        bad_rows.append([[0, 0, 0, 1, 1, 0.8]])
+    for rows in bad_rows:
+        with pytest.raises(ValueError):
+            env.disturbance_sweep(None, K, rows, 4)
+    env.close()
+
+
+# ---- 5. protocols ----------------------------------------------------------------------------------------------------------------
+def test_disturbance_rejection_on_the_robust_plants():
+    from pime_amd import protocols
+    plants = np.asarray(protocols.WT_ROBUST_PLANTS)
+    steps, onset = 60, 30
+    grid = protocols.disturbance_grid(onset, loads=(0.2, -0.2), m0=(1.5,), m2=(0.7,))
+    env = _make_env("wt", "mixed", n=3, reset=False, offset=0)
+    res = protocols.disturbance_rejection(env, grid, plants=plants, steps=steps, want_pairs=True)
+    env.close()
+    assert res["summary"].shape == (5, 5, 15, 5) and res["pairs"].shape == (5, 15, 5, 3) and res["n"] == 3
+    P.check_summary(res["summary"], res["pairs"], tag="disturbance_rejection")
+    env = _make_env("wt", "mixed", n=3, reset=False, offset=0)
+    prior = protocols.step_response_metrics(env, plants=plants, steps=steps)
+    env.close()
+    for j, name in enumerate(protocols.METRIC_NAMES):
+        assert D.bits_equal(res["pairs"][:, j, 0], prior[name]), f"the nominal row is the step-response protocol's {name}"
+    out = res["outputs"]
+    assert D.bits_equal(out[:onset, 1], out[:onset, 0]) and (out[onset:steps, 1] != out[onset:steps, 0]).any(), \
+        "a load row follows the nominal row up to its onset and leaves it there"
+    r = protocols.rejection_summary(res)
+    assert all(v.shape == (5,) and np.isfinite(v).all() for v in r.values())
+    # (60 steps do not settle the tank: at the onset the set-point step's own error is still there, so a load may shrink the peak)
+    assert (r["worst_iae"][1:] != r["worst_iae"][0]).all(), "every disturbance leaves another error integral than none"
+    assert D.bits_equal(res["pairs"][0, D.E0, 1:], np.broadcast_to(res["pairs"][0, D.E0, 0], (4, 3))), \
+        "in the first segment every row meets its onset where the nominal row is"
+    print(f"\nDISTURB robust plants, prior alone, onset {onset} of {steps}: worst peak {r['worst_peak'].round(4).tolist()}, recovery "
+          f"{r['worst_recovery'].tolist()}, IAE {r['worst_iae'].round(3).tolist()}, recovered {r['recovered'].tolist()}, |e0| "
+          f"{r['worst_e0'].round(4).tolist()}")
+
+
+def test_train_disturbances_writes_the_file(tmp_path, capsys):
+    import os
+    from pime_amd import protocols, train
+    common = ["--algo", "ResidualIntegratorModularPPO", "--env", "NonLinearWaterTankChangingParamUniformGoalIntegrator-SquareDistance-v2",
+              "--net_dim", "64", "--num_envs", "64", "--target_step", str(64 * 200), "--batch_size", "2048", "--repeat_times", "2",
+              "--break_step", str(64 * 200), "--eval_times1", "8", "--eval_times2", "16", "--eval_gap", "1"]
+    train.main(common + ["--disturbances", "--disturbance_onset", "200", "--log_root", str(tmp_path / "a")])
+    found = [os.path.join(d, f) for d, _, fs in os.walk(tmp_path) for f in fs if f == "disturbances.npz"]
+    assert len(found) == 1
+    z = np.load(found[0], allow_pickle=False)
+    P_ = 1 + len(train.DISTURBANCE_LOADS) + 3 * len(train.DISTURBANCE_MULTIPLIERS)
+    assert z["rows"].shape == (P_, 6) and (z["rows"][0] == [200, 0, 0, 1, 1, 1]).all() and int(z["onset"]) == 200
+    np.testing.assert_array_equal(z["plants"], protocols.WT_ROBUST_PLANTS)
+    for who in ("agent", "prior"):
+        assert z[f"{who}_summary"].shape == (P_, 5, 15, 5)
+        for k in ("worst_peak", "worst_recovery", "worst_iae", "recovered", "worst_e0"):
+            assert z[f"{who}_{k}"].shape == (P_,) and np.isfinite(z[f"{who}_{k}"]).all(), (who, k)
+    assert not D.bits_equal(z["agent_summary"], z["prior_summary"]), "the trained residual is not the prior alone"
+    out = capsys.readouterr().out
+    assert "worst peak" in out and "agent load" in out and "prior load" in out
+    import argparse
+    from pime_amd import gym_control
+    assert train.disturbances(argparse.Namespace(env=gym_control.WT_STACKING.format(4)), None, str(tmp_path / "b")) is None
+    assert "disturbances skipped" in capsys.readouterr().out
