@@ -278,6 +278,30 @@ static void fill_grid_args(A& a, const pime_env* e, const Ph& ph, const Wt& wt) 
     else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
 }
 
+// what the row-grid entry points (pime_margin_sweep, pime_disturb_sweep) share of their arguments; `rows` is the grid
+struct RowGridCall {
+    int32_t kind, md;
+    const float* packed_actor;
+    const double *priorK, *rows;
+    int32_t P, n_steps, seg_len;
+    const double* setpoints;
+    int32_t n_setpoints;
+    double band;
+    int32_t tail;
+    const double* summary;
+    const void* workspace;
+};
+// ... and what MarginArgs and DisturbArgs share beyond fill_grid_args
+template <typename A, typename Ph, typename Wt>
+static void fill_row_grid_args(A& a, const pime_env* e, const Ph& ph, const Wt& wt, const RowGridCall& c) {
+    fill_grid_args(a, e, ph, wt);
+    a.P = c.P;
+    a.n_seg = sweep_segments(c.n_steps, c.seg_len);
+    a.img = c.packed_actor;
+    for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = c.priorK[j];
+    fill_sweep_schedule(a.s, c.n_steps, c.seg_len, c.setpoints, c.n_setpoints, c.band, c.tail);
+}
+
 // float64 or mixed state, pH or the Integrator tank: the handles the plant-grid calls serve
 static bool grid_handle(const pime_env* e) {
     if (e == nullptr) return false;
@@ -1044,101 +1068,78 @@ int pime_mpc_eval(const pime_env* e, const double* model_plants, int32_t horizon
     });
 }
 
-// ---- loop-perturbation sweep (margin_sweep.hip) ----------------------------------------------------------------------------------
+// ---- the row-grid sweeps (row_grid.hpp): loop perturbations (margin_sweep.hip), disturbances (disturb_sweep.hip) ------------------
 int pime_margin_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
     if (!grid_handle(e)) return 0;
     if (kind == -1) return 1;                                            // the prior controller alone
     if (kind != PIME_MLP_PLAIN_ACTOR && kind != PIME_MLP_MODULAR_ACTOR && kind != PIME_MLP_SAC_ACTOR && kind != PIME_MLP_CRITIC) return 0;
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;       // (width 256, the streamed family: not served)
 }
+int pime_disturb_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
 
-int64_t pime_margin_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+// workspace: float64[n_seg][rows][P][N], the copy of `pairs` the finishing launch reads when `pairs` is NULL; `fn` names the query
+static int64_t row_grid_workspace_bytes(const char* fn, const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len, int rows) {
     if (!pime_margin_sweep_supported(e, -1, 0) || P < 1 || n_steps < 1 || seg_len < 0 || (long long)P * e->cfg.n_envs > 2147483647LL ||
         sweep_segments(n_steps, seg_len) > kMaxSetpoints) {
-        set_error("pime_margin_sweep_workspace_bytes: not served, P %d < 1, P x N > 2^31 - 1, n_steps %d < 1, seg_len %d < 0 or more than "
-                  "%d segments", P, n_steps, seg_len, kMaxSetpoints);
+        set_error("%s: not served, P %d < 1, P x N > 2^31 - 1, n_steps %d < 1, seg_len %d < 0 or more than %d segments", fn, P, n_steps,
+                  seg_len, kMaxSetpoints);
         return -1;
     }
-    return (int64_t)margin_workspace_doubles(P, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
+    return (int64_t)sweep_segments(n_steps, seg_len) * rows * P * e->cfg.n_envs * (int64_t)sizeof(double);
+}
+int64_t pime_margin_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    return row_grid_workspace_bytes("pime_margin_sweep_workspace_bytes", e, P, n_steps, seg_len, PIME_METRIC_ROWS);
+}
+int64_t pime_disturb_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    return row_grid_workspace_bytes("pime_disturb_sweep_workspace_bytes", e, P, n_steps, seg_len, kDisturbAllRows);
+}
+
+// the refusals of a row-grid entry point `fn` (its grid is `rows_name` in the messages); then the handle's device is current
+static int row_grid_open(const char* fn, const char* rows_name, const pime_env* e, const RowGridCall& c) {
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    PIME_REQUIRE(e->cfg.state_mode == PIME_STATE_F64 || e->cfg.state_mode == PIME_STATE_MIXED,
+                 "%s: state_mode %d is not served (PIME_STATE_F64 or PIME_STATE_MIXED; PIME_STATE_MIXED16 is refused)", fn,
+                 (int)e->cfg.state_mode);
+    PIME_REQUIRE(e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0,
+                 "%s: the Stacking observation (num_stack %d) is not served (pH or the Integrator water tank)", fn, (int)e->cfg.num_stack);
+    PIME_REQUIRE(c.kind == -1 || c.md != 256, "%s: md %d is not served (64 or 128; width 256 is the streamed family)", fn, c.md);
+    PIME_REQUIRE(pime_margin_sweep_supported(e, c.kind, c.md), "%s: not served for actor kind %d width md %d (%s_supported)", fn, c.kind,
+                 c.md, fn);
+    if (int rc = check_row_grid_args(fn, e->cfg.n_envs, c.priorK, c.rows, rows_name, c.P, c.n_steps, c.seg_len, c.setpoints, c.n_setpoints,
+                                     c.band, c.tail, c.summary))
+        return rc;
+    PIME_REQUIRE(c.kind == -1 || c.packed_actor != nullptr, "%s: packed_actor is NULL", fn);
+    PIME_REQUIRE(c.workspace != nullptr, "%s: workspace is NULL", fn);
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
+    return use_device(e);
 }
 
 int pime_margin_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
                       const double* perturb, int32_t P, uint64_t noise_seed, uint32_t noise_epoch, int32_t n_steps, int32_t seg_len,
                       const double* setpoints, int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary,
                       double* actions, double* outputs, void* workspace, pime_stream stream) {
-    const char* fn = "pime_margin_sweep";
-    PIME_REQUIRE(e != nullptr, "NULL env handle");
-    PIME_REQUIRE(e->cfg.state_mode == PIME_STATE_F64 || e->cfg.state_mode == PIME_STATE_MIXED,
-                 "%s: state_mode %d is not served (PIME_STATE_F64 or PIME_STATE_MIXED; PIME_STATE_MIXED16 is refused)", fn,
-                 (int)e->cfg.state_mode);
-    PIME_REQUIRE(e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0,
-                 "%s: the Stacking observation (num_stack %d) is not served (pH or the Integrator water tank)", fn, (int)e->cfg.num_stack);
-    PIME_REQUIRE(kind == -1 || md != 256, "%s: md %d is not served (64 or 128; width 256 is the streamed family)", fn, md);
-    PIME_REQUIRE(pime_margin_sweep_supported(e, kind, md), "%s: not served for actor kind %d width md %d (pime_margin_sweep_supported)",
-                 fn, kind, md);
-    if (int rc = check_margin_args(fn, e->cfg.n_envs, priorK, perturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary))
-        return rc;
-    PIME_REQUIRE(kind == -1 || packed_actor != nullptr, "%s: packed_actor is NULL", fn);
-    PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
-    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
-    if (int rc = use_device(e)) return rc;
+    const RowGridCall c{kind, md, packed_actor, priorK, perturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary, workspace};
+    if (int rc = row_grid_open("pime_margin_sweep", "perturb", e, c)) return rc;
     return with_state(e, [&](const auto& ph, const auto& wt) {
         using S = state_scalar_t<decltype(ph)>;
         MarginArgs<S> a{};
-        fill_grid_args(a, e, ph, wt);
-        a.P = P;
-        a.n_seg = sweep_segments(n_steps, seg_len);
-        a.img = packed_actor;
-        for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
+        fill_row_grid_args(a, e, ph, wt, c);
         a.nz = MarginNoise{noise_seed, noise_epoch};
-        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
         return launch_margin_sweep<S>(kind, md, a, perturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
                                       static_cast<hipStream_t>(stream));
     });
-}
-
-// ---- disturbance-rejection sweep (disturb_sweep.hip) -------------------------------------------------------------------------------
-int pime_disturb_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
-
-int64_t pime_disturb_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
-    if (!pime_disturb_sweep_supported(e, -1, 0) || P < 1 || n_steps < 1 || seg_len < 0 || (long long)P * e->cfg.n_envs > 2147483647LL ||
-        sweep_segments(n_steps, seg_len) > kMaxSetpoints) {
-        set_error("pime_disturb_sweep_workspace_bytes: not served, P %d < 1, P x N > 2^31 - 1, n_steps %d < 1, seg_len %d < 0 or more than "
-                  "%d segments", P, n_steps, seg_len, kMaxSetpoints);
-        return -1;
-    }
-    return (int64_t)disturb_workspace_doubles(P, e->cfg.n_envs, sweep_segments(n_steps, seg_len)) * (int64_t)sizeof(double);
 }
 
 int pime_disturb_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
                        const double* disturb, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
                        int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
                        double* outputs, void* workspace, pime_stream stream) {
-    const char* fn = "pime_disturb_sweep";
-    PIME_REQUIRE(e != nullptr, "NULL env handle");
-    PIME_REQUIRE(e->cfg.state_mode == PIME_STATE_F64 || e->cfg.state_mode == PIME_STATE_MIXED,
-                 "%s: state_mode %d is not served (PIME_STATE_F64 or PIME_STATE_MIXED; PIME_STATE_MIXED16 is refused)", fn,
-                 (int)e->cfg.state_mode);
-    PIME_REQUIRE(e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0,
-                 "%s: the Stacking observation (num_stack %d) is not served (pH or the Integrator water tank)", fn, (int)e->cfg.num_stack);
-    PIME_REQUIRE(kind == -1 || md != 256, "%s: md %d is not served (64 or 128; width 256 is the streamed family)", fn, md);
-    PIME_REQUIRE(pime_disturb_sweep_supported(e, kind, md), "%s: not served for actor kind %d width md %d (pime_disturb_sweep_supported)",
-                 fn, kind, md);
-    if (int rc = check_disturb_args(fn, e->cfg.n_envs, priorK, disturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary))
-        return rc;
-    PIME_REQUIRE(kind == -1 || packed_actor != nullptr, "%s: packed_actor is NULL", fn);
-    PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
-    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
-    if (int rc = use_device(e)) return rc;
+    const RowGridCall c{kind, md, packed_actor, priorK, disturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary, workspace};
+    if (int rc = row_grid_open("pime_disturb_sweep", "disturb", e, c)) return rc;
     return with_state(e, [&](const auto& ph, const auto& wt) {
         using S = state_scalar_t<decltype(ph)>;
         DisturbArgs<S> a{};
-        fill_grid_args(a, e, ph, wt);
-        a.P = P;
-        a.n_seg = sweep_segments(n_steps, seg_len);
-        a.img = packed_actor;
-        for (int j = 0; j < e->obs_dim; ++j) a.K.k[j] = priorK[j];
-        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+        fill_row_grid_args(a, e, ph, wt, c);
         return launch_disturb_sweep<S>(kind, md, a, disturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
                                        static_cast<hipStream_t>(stream));
     });

@@ -103,11 +103,6 @@ __host__ __device__ __forceinline__ void disturb_rows(const SegMetrics& M, const
     Q.rows(v + PIME_METRIC_ROWS);
 }
 
-// the prior controller alone (the host build's only policy)
-struct DisturbNoPolicy {
-    static constexpr bool kPolicy = false;
-};
-
 // the controller's output from the env's observation, formed as rollout_eval_kernel forms it (the prior term in double, ascending j
 // from 0.0; the policy term added on the left)
 template <int D, typename Pol>
@@ -211,18 +206,6 @@ __host__ __device__ __forceinline__ void disturb_wt_pair(const WtParams& p, uint
     }
 }
 
-// the argument errors of pime_disturb_sweep and of its host build, checked before anything runs; `fn` names the entry point.  The
-// schedule's, the band's and the tail's checks and messages are pime_rollout_eval_metrics' (abi.hip: rollout_eval_common).
-inline int check_disturb_args(const char* fn, int N, const double* priorK, const double* disturb, int P, int n_steps, int seg_len,
-                              const double* setpoints, int n_setpoints, double band, int tail, const double* summary) {
-    PIME_REQUIRE(P >= 1, "%s: P = %d (>= 1)", fn, P);
-    PIME_REQUIRE((long long)P * N <= 2147483647LL, "%s: P x N = %d x %d pairs exceed 2^31 - 1", fn, P, N);
-    PIME_REQUIRE(disturb != nullptr, "%s: disturb is NULL", fn);
-    PIME_REQUIRE(summary != nullptr, "%s: summary is NULL", fn);
-    PIME_REQUIRE(priorK != nullptr, "%s: priorK is NULL", fn);
-    return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
-}
-
 // (disturb_sweep.hip)
 template <typename S>
 struct DisturbArgs {
@@ -239,7 +222,6 @@ struct DisturbArgs {
     SweepSchedule s;
 };
 // workspace: float64[n_seg][kDisturbAllRows][P][N], the copy of `pairs` the finishing launch reads when `pairs` is NULL
-inline long long disturb_workspace_doubles(int P, int N, int n_seg) { return (long long)n_seg * kDisturbAllRows * P * N; }
 template <typename S>
 int launch_disturb_sweep(int kind, int md, const DisturbArgs<S>& a, const double* disturb, double* pairs, double* summary, double* actions,
                          double* outputs, double* workspace, hipStream_t stream);

@@ -1,5 +1,5 @@
 // libpime_disturb_host.so (include/pime_disturb_host.h): the pair function of pime_disturb_sweep -- disturb_sweep.hpp, the source the
-// kernel runs -- compiled for the host under the prior controller alone (DisturbNoPolicy), in float64 and float32 state, no handle;
+// kernel runs -- compiled for the host under the prior controller alone (PriorOnlyPolicy), in float64 and float32 state, no handle;
 // the opening checks, the lanes and the summary's order are host_grid.hpp's.
 //
 // NOT part of the product path: libpime_hip.so has no CPU fallback and the pime_amd package never loads this library.  Like the CPU
@@ -11,17 +11,10 @@
 
 namespace pime {
 namespace {
-// a host pair keeps its fifteen rows -- vals [n_seg][kDisturbAllRows][N], column i -- and, if asked, its signals: actions / outputs
-// [n_steps][P * N] column col
-struct DisturbHostSink {
+// a host pair keeps its fifteen rows -- vals [n_seg][kDisturbAllRows][N], column i -- and, if asked, its signals
+struct DisturbHostSink : HostTraceSink {
     double* vals;
     int N, i;
-    double *actions, *outputs;
-    size_t PN, col;
-    void step(int t, double u, double y) const {
-        if (actions) actions[(size_t)t * PN + col] = u;
-        if (outputs) outputs[(size_t)t * PN + col] = y;
-    }
     void operator()(int seg, const SegMetrics& M, const DistMetrics& Q) const {
         double v[kDisturbAllRows];
         disturb_rows(M, Q, v);
@@ -34,31 +27,24 @@ void disturb_host_run(const pime_env_cfg* cfg, const HostGrid& g, const pime_swe
                       const double* ph_qc, const double* priorK, const double* disturb, int P, const SweepSchedule& s, double* pairs,
                       double* summary, double* actions, double* outputs) {
     const std::vector<S> table = host_table<S>(cfg);
-    const int cells = sweep_segments(s.n_steps, s.seg_len) * kDisturbAllRows;
-    std::vector<double> vals((size_t)cells * N);
+    const int n_seg = sweep_segments(s.n_steps, s.seg_len);
+    std::vector<double> vals((size_t)n_seg * kDisturbAllRows * N);
     for (int p = 0; p < P; ++p) {
         const DisturbRow row = disturb_row(disturb + (size_t)p * PIME_DISTURB_COLS);
         for (int i = 0; i < N; ++i) {
-            DisturbHostSink sink{vals.data(), N, i, actions, outputs, (size_t)P * N, (size_t)p * N + i};
+            DisturbHostSink sink{{actions, outputs, (size_t)P * N, (size_t)p * N + i}, vals.data(), N, i};
             if (g.is_ph) {
                 const double K[3] = {priorK[0], priorK[1], priorK[2]};
                 PhLane<S> E = host_ph_lane<S>(g.ph, lanes, i);
                 E.qww = ph_qww[i]; E.qc = ph_qc[i];
-                disturb_ph_pair<S>(g.ph, table.data(), E, K, row, s, DisturbNoPolicy{}, sink);
+                disturb_ph_pair<S>(g.ph, table.data(), E, K, row, s, PriorOnlyPolicy{}, sink);
             } else {
                 const double K[4] = {priorK[0], priorK[1], priorK[2], priorK[3]};
                 const uint32_t gid = cfg->env_offset + (uint32_t)i;   // the PLANT's global lane keys the process noise
-                disturb_wt_pair<S>(g.wt, gid, host_wt_lane<S>(lanes, i), K, row, s, DisturbNoPolicy{}, sink);
+                disturb_wt_pair<S>(g.wt, gid, host_wt_lane<S>(lanes, i), K, row, s, PriorOnlyPolicy{}, sink);
             }
         }
-        for (int cell = 0; cell < cells; ++cell) {   // host_reduce_rows (host_grid.hpp) at fifteen rows per segment
-            const double* x = vals.data() + (size_t)cell * N;
-            if (pairs) {
-                double* q = pairs + ((size_t)cell * P + p) * N;
-                for (int i = 0; i < N; ++i) q[i] = x[i];
-            }
-            host_reduce_row(x, N, summary + ((size_t)p * cells + cell) * PIME_SWEEP_STATS);
-        }
+        host_reduce_rows(vals.data(), n_seg, kDisturbAllRows, N, p, P, pairs, summary);
     }
 }
 }  // namespace
@@ -78,7 +64,7 @@ int pime_disturb_sweep_host(const pime_env_cfg* cfg, const pime_sweep_lanes* lan
     HostGrid g{};
     if (int rc = host_grid_open(fn, cfg, lanes, N, true, g)) return rc;
     if (g.is_ph) PIME_REQUIRE(ph_qww != nullptr && ph_qc != nullptr, "%s: ph_qww or ph_qc is NULL", fn);
-    if (int rc = check_disturb_args(fn, N, priorK, disturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary)) return rc;
+    if (int rc = check_row_grid_args(fn, N, priorK, disturb, "disturb", P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary)) return rc;
     SweepSchedule s{};
     fill_sweep_schedule(s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
     if (cfg->state_mode == PIME_STATE_F64)

@@ -1,6 +1,6 @@
 // What the host builds of the plant-grid calls share (prior_sweep_host.hip, mpc_eval_host.hip, margin_sweep_host.hip,
 // disturb_sweep_host.hip; the error buffer also replay_error_host.hip): the last-error buffer, the opening checks of an entry point, a lane of pime_sweep_lanes as the
-// register copy the pair / plant functions take, the metric-row sink and THE host statement of the summary's order of additions.
+// register copy the pair / plant functions take, the metric-row and trace sinks and THE host statement of the summary's order of additions.
 // Host only and test infrastructure like the libraries that include it; each of them is one translation unit, so set_error is
 // defined here.
 #pragma once
@@ -103,16 +103,27 @@ inline void host_reduce_row(const double* x, int N, double* out) {
     out[PIME_SWEEP_FINITE] = (double)cnt;
 }
 
-// the rows of sweep row `r` of R (a gain row, a perturbation row): vals into pairs [n_seg][ROWS][R][N] (if asked) and, reduced, into
-// summary [R][n_seg][ROWS][PIME_SWEEP_STATS]
-inline void host_reduce_rows(const double* vals, int n_seg, int N, int r, int R, double* pairs, double* summary) {
-    for (int cell = 0; cell < n_seg * PIME_METRIC_ROWS; ++cell) {
+// a host pair's signals, if asked: actions / outputs [n_steps][P * N], column col
+struct HostTraceSink {
+    double *actions, *outputs;
+    size_t PN, col;
+    void step(int t, double u, double y) const {
+        if (actions) actions[(size_t)t * PN + col] = u;
+        if (outputs) outputs[(size_t)t * PN + col] = y;
+    }
+};
+
+// the rows of sweep row `r` of R (a gain row, a perturbation row, a disturbance row), ROWS per segment: vals into pairs
+// [n_seg][ROWS][R][N] (if asked) and, reduced, into summary [R][n_seg][ROWS][PIME_SWEEP_STATS]
+inline void host_reduce_rows(const double* vals, int n_seg, int ROWS, int N, int r, int R, double* pairs, double* summary) {
+    const int cells = n_seg * ROWS;
+    for (int cell = 0; cell < cells; ++cell) {
         const double* x = vals + (size_t)cell * N;
         if (pairs) {
             double* q = pairs + ((size_t)cell * R + r) * N;
             for (int i = 0; i < N; ++i) q[i] = x[i];
         }
-        host_reduce_row(x, N, summary + ((size_t)r * n_seg * PIME_METRIC_ROWS + cell) * PIME_SWEEP_STATS);
+        host_reduce_row(x, N, summary + ((size_t)r * cells + cell) * PIME_SWEEP_STATS);
     }
 }
 

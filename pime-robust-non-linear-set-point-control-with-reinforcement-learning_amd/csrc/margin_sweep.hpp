@@ -87,11 +87,6 @@ __host__ __device__ __forceinline__ void margin_measure(const MarginNoise& nz, u
     if constexpr (NM > 1) om[1] = om[1] + sigma * n1;
 }
 
-// the prior controller alone (the host build's only policy)
-struct MarginNoPolicy {
-    static constexpr bool kPolicy = false;
-};
-
 // measurement, controller, actuator: the applied action of step t from the env's observation
 template <int NM, int D, typename Pol>
 __host__ __device__ __forceinline__ double margin_action(const float (&obs)[D], const double (&K)[D], const MarginRow& row,
@@ -174,18 +169,6 @@ __host__ __device__ __forceinline__ void margin_wt_pair(const WtParams& p, uint3
     }
 }
 
-// the argument errors of pime_margin_sweep and of its host build, checked before anything runs; `fn` names the entry point.  The
-// schedule's, the band's and the tail's checks and messages are pime_rollout_eval_metrics' (abi.hip: rollout_eval_common).
-inline int check_margin_args(const char* fn, int N, const double* priorK, const double* perturb, int P, int n_steps, int seg_len,
-                             const double* setpoints, int n_setpoints, double band, int tail, const double* summary) {
-    PIME_REQUIRE(P >= 1, "%s: P = %d (>= 1)", fn, P);
-    PIME_REQUIRE((long long)P * N <= 2147483647LL, "%s: P x N = %d x %d pairs exceed 2^31 - 1", fn, P, N);
-    PIME_REQUIRE(perturb != nullptr, "%s: perturb is NULL", fn);
-    PIME_REQUIRE(summary != nullptr, "%s: summary is NULL", fn);
-    PIME_REQUIRE(priorK != nullptr, "%s: priorK is NULL", fn);
-    return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
-}
-
 // (margin_sweep.hip)
 template <typename S>
 struct MarginArgs {
@@ -203,7 +186,6 @@ struct MarginArgs {
     SweepSchedule s;
 };
 // workspace: float64[n_seg][PIME_METRIC_ROWS][P][N], the copy of `pairs` the finishing launch reads when `pairs` is NULL
-inline long long margin_workspace_doubles(int P, int N, int n_seg) { return (long long)n_seg * PIME_METRIC_ROWS * P * N; }
 template <typename S>
 int launch_margin_sweep(int kind, int md, const MarginArgs<S>& a, const double* perturb, double* pairs, double* summary, double* actions,
                         double* outputs, double* workspace, hipStream_t stream);

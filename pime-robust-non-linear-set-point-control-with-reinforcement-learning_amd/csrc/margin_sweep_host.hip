@@ -1,5 +1,5 @@
 // libpime_margin_host.so (include/pime_margin_host.h): the pair function of pime_margin_sweep -- margin_sweep.hpp, the source the
-// kernel runs -- compiled for the host under the prior controller alone (MarginNoPolicy), in float64 and float32 state, no handle;
+// kernel runs -- compiled for the host under the prior controller alone (PriorOnlyPolicy), in float64 and float32 state, no handle;
 // the opening checks, the lanes and the summary's order are host_grid.hpp's.
 //
 // NOT part of the product path: libpime_hip.so has no CPU fallback and the pime_amd package never loads this library.  Like the CPU
@@ -11,15 +11,8 @@
 
 namespace pime {
 namespace {
-// a host pair keeps its rows (HostRowSink) and, if asked, its signals: actions / outputs [n_steps][P * N] column col
-struct MarginHostSink : HostRowSink {
-    double *actions, *outputs;
-    size_t PN, col;
-    void step(int t, double u, double y) const {
-        if (actions) actions[(size_t)t * PN + col] = u;
-        if (outputs) outputs[(size_t)t * PN + col] = y;
-    }
-};
+// a host pair keeps its rows and, if asked, its signals
+struct MarginHostSink : HostRowSink, HostTraceSink {};
 
 template <typename S>
 void margin_host_run(const pime_env_cfg* cfg, const HostGrid& g, const pime_sweep_lanes* lanes, int N, const double* priorK,
@@ -31,17 +24,17 @@ void margin_host_run(const pime_env_cfg* cfg, const HostGrid& g, const pime_swee
     for (int p = 0; p < P; ++p) {
         const MarginRow row = margin_row(perturb + (size_t)p * PIME_PERTURB_COLS);
         for (int i = 0; i < N; ++i) {
-            MarginHostSink sink{{vals.data(), N, i}, actions, outputs, (size_t)P * N, (size_t)p * N + i};
+            MarginHostSink sink{{vals.data(), N, i}, {actions, outputs, (size_t)P * N, (size_t)p * N + i}};
             const uint32_t gid = cfg->env_offset + (uint32_t)i;   // the PLANT's global lane keys both noises
             if (g.is_ph) {
                 const double K[3] = {priorK[0], priorK[1], priorK[2]};
-                margin_ph_pair<S>(g.ph, table.data(), gid, host_ph_lane<S>(g.ph, lanes, i), K, row, nz, s, MarginNoPolicy{}, sink);
+                margin_ph_pair<S>(g.ph, table.data(), gid, host_ph_lane<S>(g.ph, lanes, i), K, row, nz, s, PriorOnlyPolicy{}, sink);
             } else {
                 const double K[4] = {priorK[0], priorK[1], priorK[2], priorK[3]};
-                margin_wt_pair<S>(g.wt, gid, host_wt_lane<S>(lanes, i), K, row, nz, s, MarginNoPolicy{}, sink);
+                margin_wt_pair<S>(g.wt, gid, host_wt_lane<S>(lanes, i), K, row, nz, s, PriorOnlyPolicy{}, sink);
             }
         }
-        host_reduce_rows(vals.data(), n_seg, N, p, P, pairs, summary);
+        host_reduce_rows(vals.data(), n_seg, PIME_METRIC_ROWS, N, p, P, pairs, summary);
     }
 }
 }  // namespace
@@ -60,7 +53,7 @@ int pime_margin_sweep_host(const pime_env_cfg* cfg, const pime_sweep_lanes* lane
     const char* fn = "pime_margin_sweep_host";
     HostGrid g{};
     if (int rc = host_grid_open(fn, cfg, lanes, N, true, g)) return rc;
-    if (int rc = check_margin_args(fn, N, priorK, perturb, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary)) return rc;
+    if (int rc = check_row_grid_args(fn, N, priorK, perturb, "perturb", P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary)) return rc;
     SweepSchedule s{};
     fill_sweep_schedule(s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
     const MarginNoise nz{noise_seed, noise_epoch};

@@ -119,6 +119,25 @@ inline int check_sweep_args(const char* fn, int N, const double* gains, int G, i
     return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
 }
 
+// the prior controller alone: the policy argument of the pair functions that take one (margin_sweep.hpp, disturb_sweep.hpp) and
+// the only policy of their host builds
+struct PriorOnlyPolicy {
+    static constexpr bool kPolicy = false;
+};
+
+// the argument errors of a row-grid call (pime_margin_sweep, pime_disturb_sweep) and of its host build, checked before anything
+// runs; `fn` names the entry point, `rows_name` its grid argument
+inline int check_row_grid_args(const char* fn, int N, const double* priorK, const double* rows, const char* rows_name, int P,
+                               int n_steps, int seg_len, const double* setpoints, int n_setpoints, double band, int tail,
+                               const double* summary) {
+    PIME_REQUIRE(P >= 1, "%s: P = %d (>= 1)", fn, P);
+    PIME_REQUIRE((long long)P * N <= 2147483647LL, "%s: P x N = %d x %d pairs exceed 2^31 - 1", fn, P, N);
+    PIME_REQUIRE(rows != nullptr, "%s: %s is NULL", fn, rows_name);
+    PIME_REQUIRE(summary != nullptr, "%s: summary is NULL", fn);
+    PIME_REQUIRE(priorK != nullptr, "%s: priorK is NULL", fn);
+    return check_schedule_args(fn, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+}
+
 constexpr int kSweepBlockPlants = 64;   // the plants of one block of the summary's sum: one wave
 
 // (prior_sweep.hip)

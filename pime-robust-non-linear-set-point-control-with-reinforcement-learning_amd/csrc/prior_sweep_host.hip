@@ -34,7 +34,7 @@ int pime_prior_sweep_host(const pime_env_cfg* cfg, const pime_sweep_lanes* lanes
                 sweep_wt_pair<double>(g.wt, cfg->env_offset + (uint32_t)i, host_wt_lane<double>(lanes, i), K, s, sink);   // the PLANT's global lane keys the noise
             }
         }
-        host_reduce_rows(vals.data(), n_seg, N, r, G, pairs, summary);
+        host_reduce_rows(vals.data(), n_seg, PIME_METRIC_ROWS, N, r, G, pairs, summary);
     }
     return PIME_OK;
 }

@@ -650,17 +650,49 @@ class VecControlEnv:
             native.ptr(metrics), native.ptr(actions), native.ptr(outputs), self._stream()), "pime_mpc_eval")
         return (metrics, actions, outputs) if trace else metrics
 
+    # -- the row-grid sweeps: what margin_sweep and disturbance_sweep share ---------------------------------------------
+    def _row_grid_supported(self, supported, packed_actor):
+        """`supported` (pime_margin_sweep_supported, pime_disturb_sweep_supported) for this env with this packed actor, or with the
+        prior controller alone."""
+        if self.draws.injects:
+            return False
+        if packed_actor is None:
+            return bool(supported(self._h, -1, 0))
+        if packed_actor.kind not in _EVAL_KINDS or packed_actor.D != self.obs_dim:
+            return False
+        return bool(supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
+
+    def _row_grid_sweep(self, fn, R, packed_actor, priorK, rows, own, n_steps, setpoints, seg_len, band, tail, want_pairs, want_trace):
+        """The native call `fn` on the validated device tensor `rows` [P, columns]: R metric rows per pair and segment, `own` the
+        call's own arguments (between P and n_steps).  Returns what the public method documents."""
+        k = self._prior_row(priorK)
+        P, n_steps, seg_len = int(rows.shape[0]), int(n_steps), int(seg_len)
+        ws_bytes = int(getattr(self._lib, fn + "_workspace_bytes")(self._h, P, n_steps, seg_len))
+        if ws_bytes < 0:
+            raise native.PimeError(f"{fn}_workspace_bytes: {native.last_error()}")
+        kind, md, img = self._actor_triple(packed_actor)
+        N = self.num_envs
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
+        summary = torch.empty((P, n_seg, R, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
+        pairs = torch.empty((n_seg, R, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
+        actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
+        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
+        native.check(getattr(self._lib, fn)(
+            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(rows), P, *own, n_steps, seg_len, sp_ptr, n_sp, float(band),
+            int(tail), native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace),
+            self._stream()), fn)
+        del workspace
+        if not (want_pairs or want_trace):
+            return summary
+        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+
     # -- loop-perturbation sweep (delay, gain and sensor-noise margins) ---------------------------------------------
     def margin_supported(self, packed_actor=None):
         """Does `margin_sweep` serve this env (with this packed actor, or the prior controller alone)?
         (pime_margin_sweep_supported: pH and the Integrator tank, float64 or mixed state, in-kernel draws; actor widths 64 / 128.)"""
-        if self.draws.injects:
-            return False
-        if packed_actor is None:
-            return bool(self._lib.pime_margin_sweep_supported(self._h, -1, 0))
-        if packed_actor.kind not in _EVAL_KINDS or packed_actor.D != self.obs_dim:
-            return False
-        return bool(self._lib.pime_margin_sweep_supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
+        return self._row_grid_supported(self._lib.pime_margin_sweep_supported, packed_actor)
 
     def margin_sweep(self, packed_actor, priorK, perturb, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, noise_seed=0,
                      noise_epoch=0, want_pairs=False, want_trace=False):
@@ -684,40 +716,15 @@ class VecControlEnv:
                 raise ValueError(f"margin_sweep: under capture perturb must be a contiguous float64 [P >= 1, {native.PERTURB_COLS}] device tensor")
         else:
             pt = torch.as_tensor(check_perturb(perturb), dtype=torch.float64).to(self.device).contiguous()
-        k = self._prior_row(priorK)
-        P, n_steps, seg_len = int(pt.shape[0]), int(n_steps), int(seg_len)
-        ws_bytes = int(self._lib.pime_margin_sweep_workspace_bytes(self._h, P, n_steps, seg_len))
-        if ws_bytes < 0:
-            raise native.PimeError(f"pime_margin_sweep_workspace_bytes: {native.last_error()}")
-        kind, md, img = self._actor_triple(packed_actor)
-        N = self.num_envs
-        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
-        summary = torch.empty((P, n_seg, native.METRIC_ROWS, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
-        pairs = torch.empty((n_seg, native.METRIC_ROWS, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
-        actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
-        outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
-        # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
-        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
-        native.check(self._lib.pime_margin_sweep(
-            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(pt), P, C.c_uint64(int(noise_seed)),
-            C.c_uint32(int(noise_epoch)), n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail), native.ptr(pairs),
-            native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()), "pime_margin_sweep")
-        del workspace
-        if not (want_pairs or want_trace):
-            return summary
-        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+        return self._row_grid_sweep("pime_margin_sweep", native.METRIC_ROWS, packed_actor, priorK, pt,
+                                    (C.c_uint64(int(noise_seed)), C.c_uint32(int(noise_epoch))), n_steps, setpoints, seg_len, band, tail,
+                                    want_pairs, want_trace)
 
     # -- disturbance-rejection sweep (load and plant-parameter steps) -------------------------------------------------
     def disturbance_supported(self, packed_actor=None):
         """Does `disturbance_sweep` serve this env (with this packed actor, or the prior controller alone)?
         (pime_disturb_sweep_supported: the classes of `margin_sweep`.)"""
-        if self.draws.injects:
-            return False
-        if packed_actor is None:
-            return bool(self._lib.pime_disturb_sweep_supported(self._h, -1, 0))
-        if packed_actor.kind not in _EVAL_KINDS or packed_actor.D != self.obs_dim:
-            return False
-        return bool(self._lib.pime_disturb_sweep_supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
+        return self._row_grid_supported(self._lib.pime_disturb_sweep_supported, packed_actor)
 
     def disturbance_sweep(self, packed_actor, priorK, rows, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_pairs=False,
                           want_trace=False):
@@ -739,28 +746,8 @@ class VecControlEnv:
                 raise ValueError(f"disturbance_sweep: a device tensor of rows must be contiguous float64 [P >= 1, {native.DISTURB_COLS}]")
         else:
             dt = torch.as_tensor(check_disturb(rows, self.kind == native.ENV_PH), dtype=torch.float64).to(self.device).contiguous()
-        k = self._prior_row(priorK)
-        P, n_steps, seg_len = int(dt.shape[0]), int(n_steps), int(seg_len)
-        ws_bytes = int(self._lib.pime_disturb_sweep_workspace_bytes(self._h, P, n_steps, seg_len))
-        if ws_bytes < 0:
-            raise native.PimeError(f"pime_disturb_sweep_workspace_bytes: {native.last_error()}")
-        kind, md, img = self._actor_triple(packed_actor)
-        N, R = self.num_envs, native.METRIC_ROWS + native.DISTURB_ROWS
-        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
-        summary = torch.empty((P, n_seg, R, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
-        pairs = torch.empty((n_seg, R, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
-        actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
-        outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
-        # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
-        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
-        native.check(self._lib.pime_disturb_sweep(
-            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(dt), P, n_steps, seg_len, sp_ptr, n_sp, float(band), int(tail),
-            native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace), self._stream()),
-            "pime_disturb_sweep")
-        del workspace
-        if not (want_pairs or want_trace):
-            return summary
-        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+        return self._row_grid_sweep("pime_disturb_sweep", native.METRIC_ROWS + native.DISTURB_ROWS, packed_actor, priorK, dt, (), n_steps,
+                                    setpoints, seg_len, band, tail, want_pairs, want_trace)
 
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):

@@ -5,8 +5,9 @@ alone), the seven rows of tests/disturb_sweep.py, 23 steps in segments of 9 (the
      bit-equal to pime_rollout_eval_metrics from the same lane state, every row through the checker, summary bit-equal to
      summary_from_pairs(pairs); also N = 130 (three summary blocks) with the prior alone;
   2. the handle's fields are bit-unchanged, two calls give equal bits, a NaN-filled workspace gives the same bits, NULL pairs /
-     actions / outputs leave summary unchanged, a tile's pairs give the same bits alone (P = 1, N = 16) as inside the grid, one
-     captured replay gives equal bits;
+     actions / outputs leave summary unchanged, a tile's pairs give the same bits alone (P = 1, N = 16) as inside the grid, a grid
+     with more quads than resident workgroups (a workgroup walks on to its second quad) repeats its rows bit for bit, one captured
+     replay gives equal bits;
   3. float64, the prior alone: device bit-equal to the host build (the tank with process noise off; pH on the rows with M0 == 1);
   4. every refusal and its message;
   5. protocols.disturbance_rejection / rejection_summary on the three WT_ROBUST_PLANTS with a shortened protocol;
@@ -20,7 +21,8 @@ import torch
 import disturb_sweep as D
 import prior_sweep as P
 from rollout_replay import DEV
-from test_gpu_margin_sweep import CLASSES, FIELDS, KINDS, _cfg, _make_env, _policy      # the handles, policies and classes of that sweep
+from test_gpu_margin_sweep import (CLASSES, FIELDS, KINDS, WALKS, _cfg, _make_env, _policy,      # the handles, policies and classes of
+                                   check_walk, walk_rows)                                       # that sweep
 
 pytestmark = pytest.mark.gpu
 
@@ -150,6 +152,17 @@ def test_a_tile_alone_gives_the_bits_it_gives_inside_the_grid(kind, pol, md, sta
     for k in ("pairs", "actions", "outputs"):
         assert D.bits_equal(a[k][..., 3:4, 32:48], b[k]), k
     big.close(); small.close()
+
+
+@pytest.mark.parametrize("kind,pol,md,state_mode,n,per_cu,trace", WALKS, ids=lambda v: str(v))
+def test_a_workgroup_walks_more_than_one_quad(kind, pol, md, state_mode, n, per_cu, trace):
+    env = _make_env(kind, state_mode, n=n)
+    pk, K, _ = _policy(pol, env, md)
+    Pn = walk_rows(per_cu)
+    big = _run(env, kind, pk, K, rows=np.tile(D.DISTURB[kind], (Pn // 7, 1)), trace=trace)
+    small = _run(env, kind, pk, K, trace=trace)
+    check_walk(big, small, Pn)
+    env.close()
 
 
 @pytest.mark.parametrize("kind,pol,md", [("wt", "modular", 128), ("ph", "prior", 0)], ids=lambda v: str(v))

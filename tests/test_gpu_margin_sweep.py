@@ -6,8 +6,9 @@ segments of 9 (the last one ragged), tail 4.
      pime_rollout_eval_metrics from the same lane state, every row through the checker, summary bit-equal to
      summary_from_pairs(pairs); also N = 130 (three summary blocks) with the prior alone;
   2. the handle's fields are bit-unchanged, two calls give equal bits, a NaN-filled workspace gives the same bits, NULL pairs /
-     actions / outputs leave summary unchanged, a tile's pairs give the same bits alone (P = 1, N = 16) as inside the grid, one
-     captured replay gives equal bits;
+     actions / outputs leave summary unchanged, a tile's pairs give the same bits alone (P = 1, N = 16) as inside the grid, a grid
+     with more quads than resident workgroups (a workgroup walks on to its second quad) repeats its rows bit for bit, one captured
+     replay gives equal bits;
   3. float64, the prior alone: device bit-equal to the host build (the tank with process noise off);
   4. every refusal and its message;
   5. protocols.loop_sweep / loop_margins on the three WT_ROBUST_PLANTS with a shortened protocol;
@@ -215,6 +216,38 @@ def test_a_tile_alone_gives_the_bits_it_gives_inside_the_grid(kind, pol, md, sta
     for k in ("pairs", "actions", "outputs"):
         assert G.bits_equal(a[k][..., 2:3, 32:48], b[k]), k
     big.close(); small.close()
+
+
+# one tile per row (N = 16 with a policy, N = 64 under the prior alone), so a quad is four rows; the launcher keeps at most 4 policy
+# workgroups (8 without an image) resident per compute unit: beyond 16 (32) x CUs rows some workgroup takes its second quad
+WALKS = [("wt", "modular", 128, "mixed", 16, 16, True), ("ph", "prior", 0, "f64", 64, 32, False)]
+SEVEN = (0, 1, 2, 3, 4, 1, 2)      # the file's five rows as a period of seven
+
+
+def walk_rows(per_cu):
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    return 7 * -(-(per_cu * cus + 4) // 7)
+
+
+def check_walk(big, small, Pn):
+    """Rows repeated with period 7: every row p of `big` is bit-equal to row p % 7, and rows 0 .. 6 to the P = 7 call `small`."""
+    axis = dict(summary=0, pairs=2, actions=1, outputs=1)
+    assert set(big) == set(small)
+    for k in big:
+        assert big[k].shape[axis[k]] == Pn and small[k].shape[axis[k]] == 7
+        assert P.bits_equal(big[k], np.take(small[k], np.arange(Pn) % 7, axis=axis[k])), f"{k}: a row is not the row of its period"
+
+
+@pytest.mark.parametrize("kind,pol,md,state_mode,n,per_cu,trace", WALKS, ids=lambda v: str(v))
+def test_a_workgroup_walks_more_than_one_quad(kind, pol, md, state_mode, n, per_cu, trace):
+    env = _make_env(kind, state_mode, n=n)
+    pk, K, _ = _policy(pol, env, md)
+    Pn = walk_rows(per_cu)
+    seven = G.PERTURB[list(SEVEN)]
+    big = _run(env, kind, pk, K, perturb=np.tile(seven, (Pn // 7, 1)), trace=trace)
+    small = _run(env, kind, pk, K, perturb=seven, trace=trace)
+    check_walk(big, small, Pn)
+    env.close()
 
 
 @pytest.mark.parametrize("kind,pol,md", [("wt", "modular", 128), ("ph", "prior", 0)], ids=lambda v: str(v))
