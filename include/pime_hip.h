@@ -708,6 +708,65 @@ int pime_disturb_sweep(const pime_env* env, int32_t kind, int32_t md, const floa
                        int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
                        double* outputs, void* workspace, pime_stream stream);
 
+/* -- frequency-response sweep (csrc/freq_sweep.hip) -----------------------------------------------------------------
+ * What is the loop's transfer function -- its gain margin, phase margin, peak sensitivity and bandwidth -- under the residual
+ * policy and under the prior controller alone?  The entry points above are time-domain experiments; this one excites the loop with a
+ * tabulated waveform and correlates the response with it (a lock-in).  ONE call runs every (excitation row p, plant lane i) pair of a
+ * [P, 3] grid `excite` -- columns enum pime_freq_col -- over the N lanes of the handle.  A pair runs the loop of
+ * pime_rollout_eval_metrics (set-point boundaries every seg_len steps, the lane step, the metrics with the same band and tail) on a
+ * register copy of lane i as the handle holds it.  With k the step WITHIN the segment and (c_k, s_k) = wave[p][k] (the table is
+ * indexed by k: the excitation restarts with every segment), the excitation of step k is e_k = A * s_k, one double multiplication,
+ * applied at EVERY step of the segment at the row's POINT (rint, clamped into 0 .. 2, NaN: 0; enum pime_freq_point):
+ *   SETPOINT     the lane's set-point word of step k is (S)(sp + e_k) (S the state's precision, sp the segment's set-point; without a
+ *     schedule the lane's stored word) and the observation's set-point column follows it: the env integrates the error against the
+ *     modulated set-point, as for a real reference change.  The metrics keep the segment's nominal set-point.  Measures the
+ *     complementary sensitivity T.
+ *   LOAD         a_env = a_c + e_k, one double addition IN FRONT of the actuator (pH's clip(a, -1, 1) sees the sum, the tank does not
+ *     clip): the classical loop-breaking measurement.  a_c and a_env carry the same step index: L = -A_c / (A_c + E) at the
+ *     fundamental.
+ *   MEASUREMENT  the controller reads obs[c] + (float)e_k in float32 on the controlled output's column (pH: 0, y; tank: 1, h2); the
+ *     env integrates the TRUE error, as in pime_margin_sweep.  Measures the noise sensitivity.
+ * A == 0.0: nothing is added and no word is rewritten -- for any POINT, ONSET and table the first PIME_METRIC_ROWS rows are bit for
+ * bit a lane of pime_rollout_eval_metrics from the same lane state.  The metrics' action row and `actions` hold the CONTROLLER's
+ * output a_c, `outputs` y after the step.
+ * Rows PIME_METRIC_ROWS + enum pime_freq_row of a pair and segment, over the window k >= k0 (ONSET, decoded as pime_disturb_sweep's:
+ * rint clamped into 0 .. 2^30, NaN: never; the steps before k0 let the loop reach its periodic state).  Sums are sequential double
+ * additions in ascending k from 0.0, each product rounded before it is added:
+ *   YC  sum y_k c_k      YS  sum y_k s_k      UC  sum a_c,k c_k      US  sum a_c,k s_k
+ *   Y0  sum y_k          U0  sum a_c,k        Y2  sum y_k^2          U2  sum a_c,k^2
+ * A segment with k0 >= its steps holds NaN in all eight; the summary does not count them.
+ *   kind, md, packed_actor, priorK: as pime_rollout_eval (priorK [host] float64[D])
+ *   excite   [dev] float64[P, PIME_FREQ_COLS]
+ *   wave     [dev] float64[P, wave_len, 2]: (c_k, s_k) per row and segment step; wave_len must be seg_len, or n_steps when seg_len == 0.
+ *            Any waveform: the table comes from the caller (a sinusoid with an integer number of cycles in the window makes c and s
+ *            orthogonal over it), so every stored row is reproducible from the traces bit for bit.
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   pairs    [dev] float64[n_segments, PIME_METRIC_ROWS + PIME_FREQ_ROWS, P, N] or NULL
+ *   summary  [dev] float64[P, n_segments, PIME_METRIC_ROWS + PIME_FREQ_ROWS, PIME_SWEEP_STATS]: each row over the N plants, EXACTLY the
+ *            statistics and the addition order of pime_prior_sweep's summary
+ *   actions  [dev] float64[n_steps, P, N] or NULL: a_c                   outputs  [dev] float64[n_steps, P, N] or NULL: y after the step
+ *            NULL pairs / actions / outputs is the normal use and does not change a bit of summary.
+ *   workspace [dev] pime_freq_sweep_workspace_bytes(env, P, n_steps, seg_len) bytes (-1: bad arguments); private layout, every byte
+ *            read was written by the same call
+ * The tiling is pime_margin_sweep's (one 16-lane tile of ONE row per wave: the row and its table are wave-uniform; the prior alone
+ * runs 64 distinct pairs per wave; a finishing launch reduces the rows per excitation).  The handle is READ and never written, but
+ * must have been reset.  Asynchronous on the caller's stream, capturable, no allocation, no synchronisation, no atomics: two calls give
+ * the same bits; a pair's result does not depend on P, N or its position in the grid.
+ * Served (pime_freq_sweep_supported == 1): exactly the classes of pime_margin_sweep.  Width 256, PIME_STATE_MIXED16 handles and the
+ * tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: the cases of pime_disturb_sweep (with `excite` for `disturb`),
+ * NULL wave, and wave_len other than seg_len (n_steps when seg_len == 0). */
+enum pime_freq_col { PIME_FREQ_POINT = 0, PIME_FREQ_AMPLITUDE = 1, PIME_FREQ_ONSET = 2, PIME_FREQ_COLS = 3 };
+enum pime_freq_point { PIME_FREQ_SETPOINT = 0, PIME_FREQ_LOAD = 1, PIME_FREQ_MEASUREMENT = 2 };
+enum pime_freq_row { PIME_FREQ_YC = 0, PIME_FREQ_YS = 1, PIME_FREQ_UC = 2, PIME_FREQ_US = 3, PIME_FREQ_Y0 = 4, PIME_FREQ_U0 = 5,
+                     PIME_FREQ_Y2 = 6, PIME_FREQ_U2 = 7, PIME_FREQ_ROWS = 8 };
+int pime_freq_sweep_supported(const pime_env* env, int32_t kind, int32_t md);
+int64_t pime_freq_sweep_workspace_bytes(const pime_env* env, int32_t P, int32_t n_steps, int32_t seg_len);
+int pime_freq_sweep(const pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, const double* excite,
+                    const double* wave, int32_t wave_len, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                    int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions, double* outputs,
+                    void* workspace, pime_stream stream);
+
 /* -- fused off-policy exploration-----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with
  * AgentTD3.select_action (:300-306: a = (act(s) + N(0, explore_noise)).clamp(-1, 1)), env.step, and ReplayBuffer.append_buffer

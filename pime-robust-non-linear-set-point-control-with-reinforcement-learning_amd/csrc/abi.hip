@@ -16,6 +16,7 @@
 #include "mpc_eval.hpp"
 #include "margin_sweep.hpp"
 #include "disturb_sweep.hpp"
+#include "freq_sweep.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -258,7 +259,7 @@ int h2d_from_double(const FieldRef& f, int n, const double* in, hipStream_t s) {
 
 }  // namespace
 
-// ---- the plant-grid calls (rollout_eval, prior_sweep, mpc_eval, margin_sweep, disturb_sweep; replay_error in part): one host path -
+// ---- the plant-grid calls (rollout_eval, prior_sweep, mpc_eval, margin_sweep, disturb_sweep, freq_sweep; replay_error in part): one host path -
 // f(ph, wt) on the handle's state pointers in its state's precision (PIME_STATE_F64: double, else float), so an entry point names its
 // arguments once; inside f the precision is state_scalar_t<decltype(ph)>
 template <typename F>
@@ -278,7 +279,7 @@ static void fill_grid_args(A& a, const pime_env* e, const Ph& ph, const Wt& wt) 
     else { a.wp = e->wt; a.wp.auto_reset = 0; a.wst = wt; }
 }
 
-// what the row-grid entry points (pime_margin_sweep, pime_disturb_sweep) share of their arguments; `rows` is the grid
+// what the row-grid entry points (pime_margin_sweep, pime_disturb_sweep, pime_freq_sweep) share of their arguments; `rows` is the grid
 struct RowGridCall {
     int32_t kind, md;
     const float* packed_actor;
@@ -1068,7 +1069,7 @@ int pime_mpc_eval(const pime_env* e, const double* model_plants, int32_t horizon
     });
 }
 
-// ---- the row-grid sweeps (row_grid.hpp): loop perturbations (margin_sweep.hip), disturbances (disturb_sweep.hip) ------------------
+// ---- the row-grid sweeps (row_grid.hpp): loop perturbations (margin_sweep.hip), disturbances (disturb_sweep.hip), excitations (freq_sweep.hip) ------------------
 int pime_margin_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
     if (!grid_handle(e)) return 0;
     if (kind == -1) return 1;                                            // the prior controller alone
@@ -1076,6 +1077,7 @@ int pime_margin_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
     return (md == 64 || md == 128) && !family16(kind, md) ? 1 : 0;       // (width 256, the streamed family: not served)
 }
 int pime_disturb_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
+int pime_freq_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
 
 // workspace: float64[n_seg][rows][P][N], the copy of `pairs` the finishing launch reads when `pairs` is NULL; `fn` names the query
 static int64_t row_grid_workspace_bytes(const char* fn, const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len, int rows) {
@@ -1092,6 +1094,9 @@ int64_t pime_margin_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t 
 }
 int64_t pime_disturb_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
     return row_grid_workspace_bytes("pime_disturb_sweep_workspace_bytes", e, P, n_steps, seg_len, kDisturbAllRows);
+}
+int64_t pime_freq_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    return row_grid_workspace_bytes("pime_freq_sweep_workspace_bytes", e, P, n_steps, seg_len, kFreqAllRows);
 }
 
 // the refusals of a row-grid entry point `fn` (its grid is `rows_name` in the messages); then the handle's device is current
@@ -1142,6 +1147,24 @@ int pime_disturb_sweep(const pime_env* e, int32_t kind, int32_t md, const float*
         fill_row_grid_args(a, e, ph, wt, c);
         return launch_disturb_sweep<S>(kind, md, a, disturb, pairs, summary, actions, outputs, static_cast<double*>(workspace),
                                        static_cast<hipStream_t>(stream));
+    });
+}
+
+int pime_freq_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK, const double* excite,
+                    const double* wave, int32_t wave_len, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                    int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions, double* outputs,
+                    void* workspace, pime_stream stream) {
+    const RowGridCall c{kind, md, packed_actor, priorK, excite, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary, workspace};
+    if (int rc = row_grid_open("pime_freq_sweep", "excite", e, c)) return rc;
+    if (int rc = check_freq_wave("pime_freq_sweep", wave, wave_len, n_steps, seg_len)) return rc;
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        FreqArgs<S> a{};
+        fill_row_grid_args(a, e, ph, wt, c);
+        a.wave = wave;
+        a.wave_len = wave_len;
+        return launch_freq_sweep<S>(kind, md, a, excite, pairs, summary, actions, outputs, static_cast<double*>(workspace),
+                                    static_cast<hipStream_t>(stream));
     });
 }
 

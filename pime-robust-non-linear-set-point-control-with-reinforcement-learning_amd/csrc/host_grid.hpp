@@ -1,5 +1,5 @@
 // What the host builds of the plant-grid calls share (prior_sweep_host.hip, mpc_eval_host.hip, margin_sweep_host.hip,
-// disturb_sweep_host.hip; the error buffer also replay_error_host.hip): the last-error buffer, the opening checks of an entry point, a lane of pime_sweep_lanes as the
+// disturb_sweep_host.hip, freq_sweep_host.hip; the error buffer also replay_error_host.hip): the last-error buffer, the opening checks of an entry point, a lane of pime_sweep_lanes as the
 // register copy the pair / plant functions take, the metric-row and trace sinks and THE host statement of the summary's order of additions.
 // Host only and test infrastructure like the libraries that include it; each of them is one translation unit, so set_error is
 // defined here.
@@ -113,7 +113,7 @@ struct HostTraceSink {
     }
 };
 
-// the rows of sweep row `r` of R (a gain row, a perturbation row, a disturbance row), ROWS per segment: vals into pairs
+// the rows of sweep row `r` of R (a gain row, a perturbation row, a disturbance row, an excitation row), ROWS per segment: vals into pairs
 // [n_seg][ROWS][R][N] (if asked) and, reduced, into summary [R][n_seg][ROWS][PIME_SWEEP_STATS]
 inline void host_reduce_rows(const double* vals, int n_seg, int ROWS, int N, int r, int R, double* pairs, double* summary) {
     const int cells = n_seg * ROWS;

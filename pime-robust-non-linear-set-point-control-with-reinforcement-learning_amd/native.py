@@ -45,6 +45,13 @@ DISTURB_COL_NAMES = ("onset", "length", "load", "m0", "m1", "m2")
 DISTURB_COLS = len(DISTURB_COL_NAMES)
 DISTURB_ROW_NAMES = ("e0", "peak", "peak_step", "recovery", "iae", "itae", "action_peak")
 DISTURB_ROWS = len(DISTURB_ROW_NAMES)
+# pime_freq_sweep: the columns of an excitation row (enum pime_freq_col), the injection points (enum pime_freq_point) and the lock-in
+# rows it adds behind METRIC_NAMES (enum pime_freq_row), in order
+FREQ_COL_NAMES = ("point", "amplitude", "onset")
+FREQ_COLS = len(FREQ_COL_NAMES)
+FREQ_POINTS = {"setpoint": 0, "load": 1, "measurement": 2}
+FREQ_ROW_NAMES = ("yc", "ys", "uc", "us", "y0", "u0", "y2", "u2")
+FREQ_ROWS = len(FREQ_ROW_NAMES)
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -197,6 +204,10 @@ _SIGNATURES = {
     "pime_disturb_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
     "pime_disturb_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
+    "pime_freq_sweep_supported": (C.c_int, [_vp, _i32, _i32]),
+    "pime_freq_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
+    "pime_freq_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp,
+                                  _vp, _vp, _vp]),
     "pime_mpc_eval": (C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,

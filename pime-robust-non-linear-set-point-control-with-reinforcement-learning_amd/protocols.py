@@ -42,7 +42,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .native import BAND_SIGNALS, BAND_STATS, DISTURB_ROW_NAMES, ENV_PH, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
+from .native import BAND_SIGNALS, BAND_STATS, DISTURB_ROW_NAMES, ENV_PH, FREQ_POINTS, FREQ_ROW_NAMES, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -717,4 +717,194 @@ def rejection_summary(result):
         with np.errstate(divide="ignore", invalid="ignore"):
             out["recovered"] = np.where(seen.any(axis=1), ok.sum(axis=1) / seen.sum(axis=1), np.nan)
     assert all(v.shape == (P,) for v in out.values())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ frequency response
+def excitation_grid(cycles, amplitude, point, seg_len, onset):
+    """The rows and the table of `frequency_sweep` / `VecControlEnv.frequency_sweep`: one row per entry of `cycles`, `amplitude`,
+    `point` and `onset` (a scalar serves every row; point: 0 / 1 / 2 or a name of native.FREQ_POINTS).  Row p holds an INTEGER
+    number m = cycles[p] of cycles in its correlation window of W = seg_len - onset steps, so that c and s are orthogonal over it and to a
+    constant: c_k = cos(2 pi m (k - onset) / W), s_k = sin(2 pi m (k - onset) / W) for every k of the segment (the steps before the
+    onset run the same sinusoid: the loop is in its periodic state when the window opens).  m = W / 2 is the Nyquist rate, where s
+    vanishes and nothing is excited.  Returns (rows float64 [P, 3], wave float64 [P, seg_len, 2]).  ValueError: a point that is not
+    served, a value that is not finite, an onset that is not an integer in 0 .. seg_len - 1, cycles that are not an integer in
+    0 .. W / 2."""
+    L = int(seg_len)
+    pts = [FREQ_POINTS.get(v, np.nan) if isinstance(v, str) else v for v in np.atleast_1d(np.asarray(point, dtype=object)).reshape(-1)]
+    try:
+        m, amp, pt, k0 = (np.array(a, dtype=np.float64) for a in np.broadcast_arrays(
+            *(np.atleast_1d(np.asarray(v, dtype=np.float64)).reshape(-1) for v in (cycles, amplitude, pts, onset))))
+    except (TypeError, ValueError):
+        raise ValueError("excitation_grid: cycles, amplitude, point and onset must be scalars or of one length") from None
+    P = m.size
+    if P < 1 or L < 1:
+        raise ValueError("excitation_grid: no cycles or seg_len < 1")
+    if not np.all(np.isin(pt, tuple(float(v) for v in FREQ_POINTS.values()))):
+        raise ValueError(f"excitation_grid: point must be one of {FREQ_POINTS}")
+    if not (np.all(np.isfinite(m)) and np.all(np.isfinite(amp)) and np.all(np.isfinite(k0))):
+        raise ValueError("excitation_grid: cycles, amplitude and onset must be finite")
+    if np.any(k0 != np.rint(k0)) or np.any(k0 < 0) or np.any(k0 >= L):
+        raise ValueError(f"excitation_grid: onset must be an integer in 0 .. seg_len - 1 = {L - 1}")
+    W = L - k0
+    if np.any(m != np.rint(m)) or np.any(m < 0) or np.any(m > W / 2):
+        raise ValueError("excitation_grid: cycles must be an integer in 0 .. (seg_len - onset) / 2")
+    k = np.arange(L, dtype=np.float64)[None, :]
+    theta = 2.0 * np.pi * m[:, None] * (k - k0[:, None]) / W[:, None]
+    wave = np.stack([np.cos(theta), np.sin(theta)], axis=-1)
+    rows = np.column_stack([pt, amp, k0])
+    return np.ascontiguousarray(rows, dtype=np.float64), np.ascontiguousarray(wave, dtype=np.float64)
+
+
+def frequency_sweep(env, rows, wave, agent=None, axes=None, plants=None, setpoints=None, steps=None, band=None, tail=10, want_trace=False):
+    """The step-response protocol of `env` (as `step_response_metrics`: the same start, set-points, steps, band and tail) under every
+    excitation row of `rows` [P, 3] with its table `wave` [P, steps, 2] (`excitation_grid` with seg_len = steps), over the plants in
+    the env's lanes, in ONE call (`VecControlEnv.frequency_sweep`): the excitation restarts with every set-point segment.  agent None:
+    the prior controller alone, else an agent the fused evaluation serves.  axes / plants: as `disturbance_rejection`.  Returns a dict
+    for `frequency_response`: rows, wave, summary [P, n_segments, 16, 5], pairs [n_segments, 16, P, N] (rows `METRIC_NAMES` then
+    `FREQ_ROW_NAMES`), actions and outputs [T, P, N] or None, n_steps, seg_len, steps, setpoints, band, tail, n (the plants)."""
+    from .vec_env import check_excite
+    is_ph = env.kind == ENV_PH
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    rows, wave = check_excite(rows, wave, steps)
+    if axes is not None:
+        plants = _grid(env, axes, "frequency_sweep")[3]
+    band = 0.05 if band is None else band
+    fused = _fused_policy(env, None, agent)
+    if fused is None or not hasattr(env, "frequency_supported") or not env.frequency_supported(fused[0]):
+        raise ValueError("frequency_sweep: the frequency-response sweep does not serve this env / agent (VecControlEnv.frequency_supported)")
+    _protocol_start(env, is_ph, steps, plants)
+    out = env.frequency_sweep(fused[0], fused[1], rows, wave, len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band,
+                              tail=tail, want_pairs=True, want_trace=want_trace)
+    host = lambda v: None if v is None else v.cpu().numpy()
+    return dict(rows=rows, wave=wave, summary=host(out["summary"]), pairs=host(out["pairs"]), actions=host(out["actions"]),
+                outputs=host(out["outputs"]), n_steps=len(setpoints) * int(steps), seg_len=int(steps), steps=int(steps), setpoints=setpoints,
+                band=band, tail=tail, n=int(env.num_envs))
+
+
+def frequency_response(result):
+    """Transfer-function estimates from the lock-in rows of a `frequency_sweep` result (or any dict with rows [P, 3], wave [P, L, 2],
+    pairs [n_segments, 16, P, N] and, for a ragged last segment, n_steps).  Per (row p, segment s) the window is k = k0 .. len_s - 1;
+    a signal x with sums (X0, XC, XS) over it is fitted by least squares with x_k ~ d + b c_k + a s_k -- the normal equations are the
+    table's own sums, so any table serves and a window that is not a whole number of cycles is handled -- and its phasor against the
+    reference s is X = a + j b (x_k = Im(X e^{j theta_k}) for a sinusoid).  E is the same fit of e_k = A s_k, from the table itself.
+    Returns a dict, complex [P, n_segments, N] unless said:
+      Y, U, E        the phasors of the controlled output, the controller's output a_c and the excitation (E [P, n_segments])
+      T              Y / E on SETPOINT rows: the complementary sensitivity (NaN elsewhere)
+      L, S           on LOAD rows the loop transfer function L = -U / (U + E) (a_env = a_c + e carries the same step index) and the
+                     sensitivity S = 1 / (1 + L)
+      N              Y / E on MEASUREMENT rows: the noise sensitivity (-T for a linear loop)
+      share          float64: the share of y's variance over the window that the fitted fundamental explains -- below 1 where the
+                     plant answers with harmonics: a per-plant index of non-linearity
+      omega          float64 [P]: rad per sample, from the phase the table advances by at the onset
+      point          int [P]
+    NaN where the segment never reaches the onset, and in the ratios where nothing is excited (A = 0, the Nyquist rate)."""
+    rows = np.asarray(result["rows"], dtype=np.float64)
+    wave = np.asarray(result["wave"], dtype=np.float64)
+    pairs = np.asarray(result["pairs"], dtype=np.float64)
+    S_, R, P, N = pairs.shape
+    base = len(METRIC_NAMES)
+    assert R == base + len(FREQ_ROW_NAMES) and rows.shape == (P, 3) and wave.shape[0] == P and wave.shape[2] == 2, (pairs.shape, rows.shape, wave.shape)
+    L0 = wave.shape[1]
+    n_steps = int(result.get("n_steps", S_ * L0))
+    at = {name: base + j for j, name in enumerate(FREQ_ROW_NAMES)}
+    point = np.clip(np.nan_to_num(np.rint(rows[:, 0]), nan=0.0), 0, 2).astype(int)
+    nan = np.full((P, S_, N), np.nan + 0j)
+    Y, U = nan.copy(), nan.copy()
+    E = np.full((P, S_), np.nan + 0j)
+    share = np.full((P, S_, N), np.nan)
+    om = np.full(P, np.nan)
+    for p in range(P):
+        k0 = rows[p, 2]
+        if not np.isfinite(k0):
+            continue
+        k0 = int(min(max(np.rint(k0), 0), 2 ** 30))
+        if k0 + 1 < L0:
+            (c0, s0), (c1, s1) = wave[p, k0], wave[p, k0 + 1]
+            om[p] = abs(np.arctan2(s1 * c0 - c1 * s0, c1 * c0 + s1 * s0))
+        for s in range(S_):
+            length = min(L0, n_steps - s * L0)
+            if k0 >= length:
+                continue
+            c, sn = wave[p, k0:length, 0], wave[p, k0:length, 1]
+            W = float(length - k0)
+            G = np.array([[W, c.sum(), sn.sum()], [c.sum(), (c * c).sum(), (c * sn).sum()], [sn.sum(), (c * sn).sum(), (sn * sn).sum()]])
+            Gi = np.linalg.pinv(G, rcond=1e-9, hermitian=True)
+            fit = lambda x0, xc, xs: Gi @ np.stack([x0, xc, xs])                      # (d, b, a) per plant
+            fy = fit(pairs[s, at["y0"], p], pairs[s, at["yc"], p], pairs[s, at["ys"], p])
+            fu = fit(pairs[s, at["u0"], p], pairs[s, at["uc"], p], pairs[s, at["us"], p])
+            fe = Gi @ (rows[p, 1] * G[:, 2])
+            Y[p, s], U[p, s], E[p, s] = fy[2] + 1j * fy[1], fu[2] + 1j * fu[1], fe[2] + 1j * fe[1]
+            y0, y2 = pairs[s, at["y0"], p], pairs[s, at["y2"], p]
+            explained = fy[1] * (pairs[s, at["yc"], p] - G[0, 1] * y0 / W) + fy[2] * (pairs[s, at["ys"], p] - G[0, 2] * y0 / W)
+            total = y2 - y0 * y0 / W
+            with np.errstate(divide="ignore", invalid="ignore"):
+                share[p, s] = np.where(total > 0, explained / total, np.nan)
+    Eb = E[:, :, None]
+    quiet = ~(np.abs(Eb) > 1e-9 * np.maximum(np.abs(rows[:, 1])[:, None, None], 1e-300))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(quiet, np.nan, Y / Eb)
+        loop = np.where(quiet, np.nan, -U / (U + Eb))
+        sens = 1.0 / (1.0 + loop)
+    is_pt = lambda v: (point == v)[:, None, None]
+    return dict(Y=Y, U=U, E=E, T=np.where(is_pt(FREQ_POINTS["setpoint"]), ratio, np.nan), L=np.where(is_pt(FREQ_POINTS["load"]), loop, np.nan),
+                S=np.where(is_pt(FREQ_POINTS["load"]), sens, np.nan), N=np.where(is_pt(FREQ_POINTS["measurement"]), ratio, np.nan),
+                share=share, omega=om, point=point)
+
+
+def _log_interp(w0, w1, f0, f1, level, v0, v1):
+    """f crosses `level` between (w0, f0) and (w1, f1), linearly in log w: (the crossing's w, v there, linear in log w as well)."""
+    x = (level - f0) / (f1 - f0)
+    return float(np.exp(np.log(w0) + x * (np.log(w1) - np.log(w0)))), float(v0 + x * (v1 - v0))
+
+
+def _margins_of(w, L, wt, T):
+    """One plant and segment: (gain margin, phase margin in degrees, peak |S|, bandwidth) from L at ascending w and T at ascending wt."""
+    gm = pm = peak = bw = np.nan
+    ok = np.isfinite(L)
+    w, L = w[ok], L[ok]
+    if w.size >= 1:
+        mag, ph = np.log(np.abs(L)), np.unwrap(np.angle(L))
+        for i in range(w.size - 1):                    # gain crossover: |L| falls through 1
+            if np.isnan(pm) and mag[i] > 0.0 >= mag[i + 1]:
+                pm = np.degrees(_log_interp(w[i], w[i + 1], mag[i], mag[i + 1], 0.0, ph[i], ph[i + 1])[1] + np.pi)
+            if np.isnan(gm) and ph[i] > -np.pi >= ph[i + 1]:   # phase crossover: arg L falls through -180 degrees
+                gm = float(np.exp(-_log_interp(w[i], w[i + 1], ph[i], ph[i + 1], -np.pi, mag[i], mag[i + 1])[1]))
+        s = np.abs(1.0 / (1.0 + L))
+        j = int(np.argmax(s))
+        peak = float(s[j])
+        if 0 < j < w.size - 1:                         # an interior maximum: the parabola through its three points in log w
+            x = np.log(w[j - 1:j + 2]) - np.log(w[j])
+            a, b, _ = np.polyfit(x, s[j - 1:j + 2], 2)
+            if a < 0:
+                peak = float(s[j] - b * b / (4 * a))
+    ok = np.isfinite(T)
+    wt, T = wt[ok], np.abs(T[ok])
+    for i in range(wt.size - 1):                       # bandwidth: |T| falls through 1 / sqrt 2
+        if T[i] > np.sqrt(0.5) >= T[i + 1]:
+            bw = _log_interp(wt[i], wt[i + 1], T[i], T[i + 1], np.sqrt(0.5), 0.0, 0.0)[0]
+            break
+    return gm, pm, peak, bw
+
+
+def stability_margins(response):
+    """Classical margins from a `frequency_response`: per segment and plant, float64 [n_segments, N] each --
+      gain_margin   1 / |L| where arg L first falls through -180 degrees (the unwrapped phase over the LOAD rows in ascending omega)
+      phase_margin  180 degrees + arg L where |L| first falls through 1, in degrees
+      peak_S        the largest |S| = |1 / (1 + L)| over the LOAD rows, refined by the parabola through the three points around an
+                    interior maximum
+      bandwidth     omega (rad per sample) where |T| first falls through 1 / sqrt 2 over the SETPOINT rows
+    Crossings are interpolated linearly in log omega between the two rows that bracket them (log |L| and the phase for the margins,
+    |T| for the bandwidth) and are NaN where the grid brackets none; rows where nothing was excited are left out."""
+    om, point = np.asarray(response["omega"], dtype=np.float64), np.asarray(response["point"])
+    L, T = np.asarray(response["L"]), np.asarray(response["T"])
+    _, S_, N = L.shape
+    pick = lambda v: (lambda idx: idx[np.argsort(om[idx], kind="stable")])(np.flatnonzero((point == v) & np.isfinite(om) & (om > 0)))
+    il, it = pick(FREQ_POINTS["load"]), pick(FREQ_POINTS["setpoint"])
+    out = {k: np.full((S_, N), np.nan) for k in ("gain_margin", "phase_margin", "peak_S", "bandwidth")}
+    for s in range(S_):
+        for i in range(N):
+            g, ph, pk, bw = _margins_of(om[il], L[il, s, i], om[it], T[it, s, i])
+            out["gain_margin"][s, i], out["phase_margin"][s, i], out["peak_S"][s, i], out["bandwidth"][s, i] = g, ph, pk, bw
     return out

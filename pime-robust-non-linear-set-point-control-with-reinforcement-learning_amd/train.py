@@ -14,6 +14,7 @@ Reference quirks kept by default: --gamma and --learning_rate
 import argparse
 import os
 import time
+import warnings
 
 import numpy as np
 import torch
@@ -94,6 +95,14 @@ def build_parser():
                         "alone) on the plants of --robust_test, one launch each; writes disturbances.npz into the run directory")
     p.add_argument("--disturbance_onset", default=-1, type=int, metavar="K",
                    help="--disturbances: the step within every set-point segment at which the disturbance starts (default: half a segment)")
+    p.add_argument("--bode", action="store_true",
+                   help="after training: the loop's frequency response (trained agent AND prior alone) on the plants of --robust_test, one "
+                        "launch each -- sinusoids at the set-point and in front of the actuator, lock-in rows, gain and phase margin, peak "
+                        "sensitivity, bandwidth; writes frequency_response.npz into the run directory")
+    p.add_argument("--bode_points", default=12, type=int, metavar="F",
+                   help="--bode: frequencies, spread logarithmically over the whole numbers of cycles the window holds")
+    p.add_argument("--bode_amplitude", default=0.05, type=float, metavar="A",
+                   help="--bode: amplitude of the excitation (set-point units on set-point rows, normalised action units on load rows)")
     p.add_argument("--mpc_model", default=None, type=str, metavar="FILE.npz",
                    help="--mpc_baseline (tank only): control every plant on FILE's `best` plant (an identified.npz of --identify)")
     p.add_argument("--prior_K", default=None, type=str, metavar="FILE.npz",
@@ -432,6 +441,69 @@ def disturbances(args, agent, cwd):
     return path
 
 
+def bode(args, agent, cwd):
+    """--bode: under the step-response protocol of --robust_test, on every plant of its plant set, a sinusoid of --bode_amplitude at
+    --bode_points frequencies -- whole numbers of cycles in the second half of every set-point segment, the first half letting the loop
+    reach its periodic state -- once at the set-point (the complementary sensitivity T) and once in front of the actuator (the loop
+    transfer function L and the sensitivity S); one launch for the trained agent and one for the prior controller alone
+    (protocols.frequency_sweep / frequency_response / stability_margins).  Writes <cwd>/frequency_response.npz -- rows, omega, plants
+    and per controller (prefix agent_ / prior_) T, L, S, the fundamental's variance share and the margins per segment and plant -- and
+    prints the worst plant's margins of both side by side."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("bode skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    onset = steps // 2
+    window = steps - onset
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    top = max((window - 1) // 2, 1)                        # below the Nyquist rate, where nothing is excited
+    cycles = np.unique(np.rint(np.geomspace(1, top, max(int(getattr(args, "bode_points", 12)), 1))))
+    amplitude = float(getattr(args, "bode_amplitude", 0.05))
+    m = np.concatenate([cycles, cycles])
+    point = np.repeat([protocols.FREQ_POINTS["setpoint"], protocols.FREQ_POINTS["load"]], len(cycles))
+    rows, wave = protocols.excitation_grid(m, amplitude, point, steps, onset)
+    out, found = {}, {}
+    for who, ag in (("agent", agent), ("prior", None)):
+        env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        fused = protocols._fused_policy(env, None, ag)
+        if fused is None or not hasattr(env, "frequency_supported") or not env.frequency_supported(fused[0]):
+            env.close()
+            print(f"bode skipped for the {who}: the frequency-response sweep does not serve this env / actor (frequency_supported)")
+            continue
+        res = protocols.frequency_sweep(env, rows, wave, agent=ag, plants=plants, setpoints=setpoints, steps=steps, band=band, tail=tail)
+        env.close()
+        fr = protocols.frequency_response(res)
+        found[who] = protocols.stability_margins(fr)
+        omega = fr["omega"]
+        out[f"{who}_pairs"] = res["pairs"]
+        for k in ("T", "L", "S", "share"):
+            out[f"{who}_{k}"] = fr[k]
+        for k, v in found[who].items():
+            out[f"{who}_{k}"] = v
+    if not found:
+        return None
+    path = os.path.join(cwd, "frequency_response.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, rows=rows, cycles=m, omega=omega, plants=plants, setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, band=band,
+             tail=tail, onset=onset, amplitude=amplitude, metric_names=np.asarray(protocols.METRIC_NAMES + protocols.FREQ_ROW_NAMES), **out)
+    print(f"bode: {len(rows)} rows ({len(cycles)} frequencies x set-point, load) x {len(plants)} plants, amplitude {amplitude:g}, "
+          f"window {window} of {steps} steps -> {path}")
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)      # (a margin no plant's grid brackets: NaN)
+        worst = {who: (np.nanmin(r["gain_margin"]), np.nanmin(r["phase_margin"]), np.nanmax(r["peak_S"]), np.nanmin(r["bandwidth"]))
+                 for who, r in found.items()}
+    for j, (name, unit) in enumerate((("gain margin", ""), ("phase margin", " deg"), ("peak |S|", ""), ("bandwidth", " rad/sample"))):
+        side = ", ".join(f"{who} {worst[who][j]:.4g}{unit}" for who in worst)
+        print(f"worst plant {name}: {side}")
+    return path
+
+
 def apply_prior_K(env, path):
     """--prior_K FILE.npz: FILE's best_gain (the env's sign: a = -obs @ K) becomes the env's K -- and that of its clones (the
     evaluation env of an off-policy run) -- before the residual agent reads it."""
@@ -508,6 +580,8 @@ def main(argv=None):
             margins(args, agent, kargs.cwd)
         if args.disturbances:
             disturbances(args, agent, kargs.cwd)
+        if args.bode:
+            bode(args, agent, kargs.cwd)
     return agent
 
 

@@ -136,6 +136,28 @@ def check_disturb(rows, is_ph):
     return np.ascontiguousarray(rows)
 
 
+def check_excite(rows, wave, L):
+    """The rows and the table of `VecControlEnv.frequency_sweep` as float64 [P, 3] (columns native.FREQ_COL_NAMES) and [P, L, 2], or
+    ValueError: a shape, a point that is not 0, 1 or 2, an amplitude that is not finite, an onset that is not a non-negative integer,
+    a table entry that is not finite."""
+    rows = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64)
+    wave = np.asarray(wave.detach().cpu().numpy() if torch.is_tensor(wave) else wave, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != native.FREQ_COLS or rows.shape[0] < 1:
+        raise ValueError(f"frequency_sweep: rows {tuple(rows.shape)} must be [P >= 1, {native.FREQ_COLS}]")
+    if wave.shape != (rows.shape[0], int(L), 2):
+        raise ValueError(f"frequency_sweep: wave {tuple(wave.shape)} must be [P = {rows.shape[0]}, L = {int(L)}, 2]")
+    pt, amp, k0 = rows[:, 0], rows[:, 1], rows[:, 2]
+    if not np.all(np.isin(pt, tuple(float(v) for v in native.FREQ_POINTS.values()))):
+        raise ValueError(f"frequency_sweep: point must be one of {native.FREQ_POINTS}")
+    if not np.all(np.isfinite(amp)):
+        raise ValueError("frequency_sweep: an amplitude is not finite")
+    if not np.all(np.isfinite(k0)) or np.any(k0 != np.rint(k0)) or np.any(k0 < 0):
+        raise ValueError("frequency_sweep: onset must be a non-negative integer")
+    if not np.all(np.isfinite(wave)):
+        raise ValueError("frequency_sweep: a wave entry is not finite")
+    return np.ascontiguousarray(rows), np.ascontiguousarray(wave)
+
+
 _EVAL_KINDS ={"modular_actor": native.MLP_MODULAR_ACTOR, "plain_actor": native.MLP_PLAIN_ACTOR, "sac_actor": native.MLP_SAC_ACTOR,
                "critic": native.MLP_CRITIC}
 
@@ -650,7 +672,7 @@ class VecControlEnv:
             native.ptr(metrics), native.ptr(actions), native.ptr(outputs), self._stream()), "pime_mpc_eval")
         return (metrics, actions, outputs) if trace else metrics
 
-    # -- the row-grid sweeps: what margin_sweep and disturbance_sweep share ---------------------------------------------
+    # -- the row-grid sweeps: what margin_sweep, disturbance_sweep and frequency_sweep share ---------------------------------------------
     def _row_grid_supported(self, supported, packed_actor):
         """`supported` (pime_margin_sweep_supported, pime_disturb_sweep_supported) for this env with this packed actor, or with the
         prior controller alone."""
@@ -662,9 +684,10 @@ class VecControlEnv:
             return False
         return bool(supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
 
-    def _row_grid_sweep(self, fn, R, packed_actor, priorK, rows, own, n_steps, setpoints, seg_len, band, tail, want_pairs, want_trace):
+    def _row_grid_sweep(self, fn, R, packed_actor, priorK, rows, own, n_steps, setpoints, seg_len, band, tail, want_pairs, want_trace,
+                        before=()):
         """The native call `fn` on the validated device tensor `rows` [P, columns]: R metric rows per pair and segment, `own` the
-        call's own arguments (between P and n_steps).  Returns what the public method documents."""
+        call's own arguments between P and n_steps, `before` those between the rows and P.  Returns what the public method documents."""
         k = self._prior_row(priorK)
         P, n_steps, seg_len = int(rows.shape[0]), int(n_steps), int(seg_len)
         ws_bytes = int(getattr(self._lib, fn + "_workspace_bytes")(self._h, P, n_steps, seg_len))
@@ -680,7 +703,7 @@ class VecControlEnv:
         # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
         workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
         native.check(getattr(self._lib, fn)(
-            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(rows), P, *own, n_steps, seg_len, sp_ptr, n_sp, float(band),
+            self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(rows), *before, P, *own, n_steps, seg_len, sp_ptr, n_sp, float(band),
             int(tail), native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace),
             self._stream()), fn)
         del workspace
@@ -748,6 +771,41 @@ class VecControlEnv:
             dt = torch.as_tensor(check_disturb(rows, self.kind == native.ENV_PH), dtype=torch.float64).to(self.device).contiguous()
         return self._row_grid_sweep("pime_disturb_sweep", native.METRIC_ROWS + native.DISTURB_ROWS, packed_actor, priorK, dt, (), n_steps,
                                     setpoints, seg_len, band, tail, want_pairs, want_trace)
+
+    # -- frequency-response sweep (tabulated excitation and lock-in rows) ------------------------------------------------
+    def frequency_supported(self, packed_actor=None):
+        """Does `frequency_sweep` serve this env (with this packed actor, or the prior controller alone)?
+        (pime_freq_sweep_supported: the classes of `margin_sweep`.)"""
+        return self._row_grid_supported(self._lib.pime_freq_sweep_supported, packed_actor)
+
+    def frequency_sweep(self, packed_actor, priorK, rows, wave, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_pairs=False,
+                        want_trace=False):
+        """A grid of EXCITATIONS over every lane's plant in ONE call (pime_freq_sweep, csrc/freq_sweep.hip): every (row, lane) pair
+        runs the loop of `rollout_eval_metrics` from the lane state as it stands while amplitude x s_k is added at every step k of every
+        segment at the row's point (native.FREQ_POINTS: the set-point, the controller's output in front of the actuator, the measured
+        output the controller reads) -- rows float64 [P, 3], columns native.FREQ_COL_NAMES; wave float64 [P, L, 2] holds (c_k, s_k)
+        per row and segment step, L = seg_len (n_steps when seg_len is 0): `protocols.excitation_grid` makes both.  packed_actor None =
+        the prior controller alone.  Returns summary float64 [P, n_segments, 16, 5] -- per row, segment and metric row
+        (native.METRIC_NAMES, then native.FREQ_ROW_NAMES: the sums of y c, y s, a_c c, a_c s, y, a_c, y^2 and a_c^2 over the steps from
+        `onset`) the stats native.SWEEP_STATS over the lanes, exactly as `prior_sweep`; a segment that never reaches the onset holds
+        NaN and is not counted -- or, with `want_pairs` and / or `want_trace`, a dict with "summary", "pairs" float64
+        [n_segments, 16, P, N] and "actions", "outputs" float64 [n_steps, P, N] (the CONTROLLER's output and the controlled output
+        after each step).  ValueError for a bad row or table (`check_excite`); device tensors are taken as given apart from their
+        shapes, so a capture works.  The env itself is read, never advanced (definitions in include/pime_hip.h)."""
+        n_steps, seg_len = int(n_steps), int(seg_len)
+        L = seg_len if seg_len > 0 else n_steps
+        if torch.is_tensor(rows) and rows.is_cuda and torch.is_tensor(wave) and wave.is_cuda:
+            rt, wt = rows, wave
+            if rt.dtype != torch.float64 or rt.dim() != 2 or rt.shape[1] != native.FREQ_COLS or rt.shape[0] < 1 or not rt.is_contiguous():
+                raise ValueError(f"frequency_sweep: a device tensor of rows must be contiguous float64 [P >= 1, {native.FREQ_COLS}]")
+            if wt.dtype != torch.float64 or tuple(wt.shape) != (rt.shape[0], L, 2) or not wt.is_contiguous():
+                raise ValueError(f"frequency_sweep: a device tensor of wave must be contiguous float64 [P, {L}, 2]")
+        else:
+            r, w = check_excite(rows, wave, L)
+            rt = torch.as_tensor(r, dtype=torch.float64).to(self.device).contiguous()
+            wt = torch.as_tensor(w, dtype=torch.float64).to(self.device).contiguous()
+        return self._row_grid_sweep("pime_freq_sweep", native.METRIC_ROWS + native.FREQ_ROWS, packed_actor, priorK, rt, (), n_steps,
+                                    setpoints, seg_len, band, tail, want_pairs, want_trace, before=(native.ptr(wt), L))
 
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
