@@ -47,7 +47,8 @@ enum pime_kind { PIME_ENV_PH = 0, PIME_ENV_WT = 1 };
  * PIME_STATE_MIXED16 (BASELINE.json config 5 "fp16 state" = SURVEY.md §8(d) cfg 5): as MIXED with the integrated error I STORED
  * as IEEE binary16 and, through the *_h entry points, observations and rewards written as binary16 (48 instead of 68 bytes of
  * algorithmic traffic per pH env-step); all arithmetic stays float32 / float64.  What it costs in accuracy is stated with
- * pime_env_step_h. */
+ * pime_env_step_h.  Through the float entry points such a handle writes float32 rows whose I is the stored binary16 word, the value the
+ * next step continues from and pime_env_observe returns. */
 enum pime_state_mode { PIME_STATE_F64 = 0, PIME_STATE_MIXED = 1, PIME_STATE_MIXED16 = 2 };
 enum pime_reward { PIME_REWARD_DISTANCE = 0, PIME_REWARD_SQUARE = 1, PIME_REWARD_SPARSE = 2 };
 enum pime_dtype { PIME_F32 = 0, PIME_F64 = 1 };
@@ -59,7 +60,10 @@ enum pime_field {
     PIME_PH_QWW_V = 7, PIME_PH_QC_V = 8, PIME_PH_T = 9, PIME_PH_EPISODE = 10,
     /* water tank (nonlinear_watertank.py attributes: h1, h2, r, integrator, a1, a2, Kp, _episode_steps) */
     PIME_WT_H1 = 32, PIME_WT_H2 = 33, PIME_WT_R = 34, PIME_WT_I = 35, PIME_WT_A1 = 36, PIME_WT_A2 = 37,
-    PIME_WT_KP = 38, PIME_WT_T = 39, PIME_WT_EPISODE = 40
+    PIME_WT_KP = 38, PIME_WT_T = 39, PIME_WT_EPISODE = 40,
+    /* Stacking variant only, read-only: the ring slot of a lane's OLDEST frame (0 after every reset, then one further per step,
+     * modulo num_stack) */
+    PIME_WT_HEAD = 41
 };
 
 /* Titration chemistry, gym_control/envs/ph.py:32-37 */

@@ -202,6 +202,9 @@ int resolve_field(pime_env* e, int field, FieldRef* out) {
             case PIME_WT_KP: r = {WPTR(kp), st}; break;
             case PIME_WT_T: r = {e->wt64.t, 2}; break;
             case PIME_WT_EPISODE: r = {e->wt64.episode, 2}; break;
+            case PIME_WT_HEAD:
+                if (e->cfg.num_stack == 0) { set_error("the Integrator variant has no frame ring"); return PIME_ERR_ARG; }
+                r = {f64 ? (void*)e->wt64.head : (void*)e->wt32.head, 2, false, true}; break;   // read-only: the kernels index the ring with it
             default: set_error("field %d is not a water-tank field", field); return PIME_ERR_ARG;
         }
     }

@@ -57,7 +57,9 @@ __global__ void ph_step_kernel(PhParams p, PhPtrs<S, SI> st, const ActT* __restr
     if (d && p.auto_reset)
         ph_lane_reset<S>(p, st.table, p.env_offset + (uint32_t)i, reset_draws ? reset_draws + 4 * (size_t)i : nullptr, L, o);
     ph_lane_store<S>(p, st, i, L);
-    obs[3 * (size_t)i + 0] = (OT)o[0]; obs[3 * (size_t)i + 1] = (OT)o[1]; obs[3 * (size_t)i + 2] = (OT)o[2];
+    // the row carries the integrated error AS STORED (binary16 in PIME_STATE_MIXED16, also through the float entry points), so the
+    // policy sees the word the next step continues from and pime_env_observe repeats this row bit for bit
+    obs[3 * (size_t)i + 0] = (OT)o[0]; obs[3 * (size_t)i + 1] = (OT)o[1]; obs[3 * (size_t)i + 2] = (OT)(float)(SI)o[2];
 }
 
 template <typename S, typename SI, typename OT>
@@ -171,7 +173,7 @@ __global__ void wt_step_kernel(WtParams p, WtPtrs<S, SI> st, const ActT* __restr
             if (p.num_stack > 0) wt_frames_push<S>(p, st, i, L);
         }
     }
-    wt_write_obs<S>(p, st, i, live, L.h1, L.h2, L.r, L.I, obs, lds);
+    wt_write_obs<S>(p, st, i, live, L.h1, L.h2, L.r, (S)(SI)L.I, obs, lds);   // I as stored (see ph_step_kernel)
 }
 
 template <typename S, typename SI, typename OT>

@@ -55,7 +55,7 @@ FREQ_ROWS = len(FREQ_ROW_NAMES)
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
-    wt_h1=32, wt_h2=33, wt_r=34, wt_I=35, wt_a1=36, wt_a2=37, wt_Kp=38, wt_t=39, wt_episode=40,
+    wt_h1=32, wt_h2=33, wt_r=34, wt_I=35, wt_a1=36, wt_a2=37, wt_Kp=38, wt_t=39, wt_episode=40, wt_head=41,
 )
 
 
