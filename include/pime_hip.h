@@ -771,6 +771,69 @@ int pime_freq_sweep(const pime_env* env, int32_t kind, int32_t md, const float* 
                     int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions, double* outputs,
                     void* workspace, pime_stream stream);
 
+/* -- actuator-limits sweep (csrc/actuator_sweep.hip) ------------------------------------------------------------------
+ * What do a REAL actuator and a real sensor -- saturation, a slew-rate limit, a dead-band, a DAC quantum, an ADC quantum -- do to the
+ * closed loop under the residual policy and under the prior controller alone: wind-up overshoot, limit cycles ("hunting")?  The entry
+ * points above hand the plant the controller's real number and the controller the plant's outputs at full precision.  ONE call runs
+ * every (actuator row p, plant lane i) pair of a [P, 6] grid `actuator` -- columns enum pime_act_col -- over the N lanes of the
+ * handle.  Everything not said here is pime_disturb_sweep's: the loop of pime_rollout_eval_metrics on a register copy of lane i, the
+ * schedule, band and tail, pairs / summary / workspace and a NULL pairs, the tiling, the handle READ and never written, no allocation,
+ * capturable, two calls give the same bits, the served classes, the refusals.
+ * The rows live on the device, so they are DECODED, not validated.  All columns are in normalised action units except QY:
+ *   LO, HI     saturation limits.                                        off: -inf / +inf, or NaN (the stage runs iff LO > -inf || HI < inf)
+ *   RATE       the largest move per sample period.                       off: anything not 0 < RATE < inf
+ *   DEADBAND   hold if the command is within it of the present position. off: anything not > 0
+ *   QU         the actuator's quantum (a DAC step).                      off: anything not > 0
+ *   QY         the sensor's quantum (an ADC step), observation units.    off: anything not > 0
+ * Per launch step t:
+ *   SENSOR      obs_m = obs; with QY on, for the measured plant outputs only (pH: column 0; tank: columns 0 and 1, as in
+ *     pime_margin_sweep) obs_m[j] = (float)(QY * rint((double)obs[j] / QY)).  The set-point and integrator columns are the env's own.
+ *   CONTROLLER  a_c from obs_m as pime_disturb_sweep forms it from obs; kind = -1: the prior controller alone.
+ *   ACTUATOR    in double, on v = a_c and the previous APPLIED action u_prev -- 0.0 before the launch's first step, NOT cleared at a
+ *     segment boundary (like pime_margin_sweep's delay line) -- the stages in this fixed order, each only if it is on:
+ *       dead-band   if (fabs(v - u_prev) <= DEADBAND) v = u_prev;
+ *       slew        v = u_prev + clip(v - u_prev, -RATE, RATE);
+ *       quantise    v = QU * rint(v / QU);
+ *       clamp       v = clip(v, LO, HI);
+ *     with clip(x, lo, hi): x < lo ? lo : x, then x > hi ? hi : x (a NaN limit never binds), rint to nearest-even.  The clamp comes
+ *     last, so a limit holds exactly.  u = v; the lane steps on u (pH's own clip(a, -1, 1) still sees it); u_prev = u.
+ * A stage that is off performs no arithmetic and rewrites no word: a row with all six columns off is bit for bit a lane of
+ * pime_rollout_eval_metrics from the same lane state (a -0.0 stays -0.0).  The metrics' action row and `actions` hold the APPLIED u (as
+ * in pime_margin_sweep), `commands` the controller's a_c, `outputs` y after the step.
+ * Rows PIME_METRIC_ROWS + enum pime_act_row of a pair and segment, over ALL steps of the segment; each can be recomputed from the
+ * three traces (the chain re-run on `commands`):
+ *   SAT_STEPS    steps where the clamp changed v          RATE_STEPS   steps where the slew limit bound (clip(d) != d)
+ *   HOLD_STEPS   steps the dead-band held                 GAP_PEAK     max |a_c - u|
+ *   GAP_IAE      sum |a_c - u|, sequential from 0.0 in ascending step
+ *   REVERSALS    sign changes between successive NON-ZERO moves u_k - u_{k-1}; the last move's sign is forgotten at the segment's
+ *                start, the segment's first move is measured from the u_prev it inherited
+ *   TAIL_Y_P2P   max - min of y over the segment's last `tail` steps (the window of PIME_METRIC_SSE): the limit cycle's amplitude
+ *   TAIL_U_P2P   max - min of u over the same steps
+ * Counts are exact integers stored as double.  Every segment has steps, so no row is NaN by construction.
+ *   kind, md, packed_actor, priorK: as pime_rollout_eval (priorK [host] float64[D])
+ *   actuator [dev] float64[P, PIME_ACT_COLS]
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   pairs    [dev] float64[n_segments, PIME_METRIC_ROWS + PIME_ACT_ROWS, P, N] or NULL
+ *   summary  [dev] float64[P, n_segments, PIME_METRIC_ROWS + PIME_ACT_ROWS, PIME_SWEEP_STATS]: pime_prior_sweep's statistics and order
+ *   actions  [dev] float64[n_steps, P, N] or NULL: u        commands [dev] float64[n_steps, P, N] or NULL: a_c
+ *   outputs  [dev] float64[n_steps, P, N] or NULL: y after the step.  NULL pairs / actions / commands / outputs is the normal use and
+ *            does not change a bit of summary.
+ *   workspace [dev] pime_actuator_sweep_workspace_bytes(env, P, n_steps, seg_len) bytes (-1: bad arguments); private layout, every
+ *            byte read was written by the same call
+ * Served (pime_actuator_sweep_supported == 1): exactly the classes of pime_margin_sweep.  Width 256, PIME_STATE_MIXED16 handles and the
+ * tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: the cases of pime_disturb_sweep (with `actuator` for `disturb`). */
+enum pime_act_col { PIME_ACT_LO = 0, PIME_ACT_HI = 1, PIME_ACT_RATE = 2, PIME_ACT_DEADBAND = 3, PIME_ACT_QU = 4, PIME_ACT_QY = 5,
+                    PIME_ACT_COLS = 6 };
+enum pime_act_row { PIME_ACT_SAT_STEPS = 0, PIME_ACT_RATE_STEPS = 1, PIME_ACT_HOLD_STEPS = 2, PIME_ACT_GAP_PEAK = 3, PIME_ACT_GAP_IAE = 4,
+                    PIME_ACT_REVERSALS = 5, PIME_ACT_TAIL_Y_P2P = 6, PIME_ACT_TAIL_U_P2P = 7, PIME_ACT_ROWS = 8 };
+int pime_actuator_sweep_supported(const pime_env* env, int32_t kind, int32_t md);
+int64_t pime_actuator_sweep_workspace_bytes(const pime_env* env, int32_t P, int32_t n_steps, int32_t seg_len);
+int pime_actuator_sweep(const pime_env* env, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                        const double* actuator, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                        int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
+                        double* commands, double* outputs, void* workspace, pime_stream stream);
+
 /* -- fused off-policy exploration-----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with
  * AgentTD3.select_action (:300-306: a = (act(s) + N(0, explore_noise)).clamp(-1, 1)), env.step, and ReplayBuffer.append_buffer

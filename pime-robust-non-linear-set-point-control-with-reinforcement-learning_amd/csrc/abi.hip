@@ -16,6 +16,7 @@
 #include "mpc_eval.hpp"
 #include "margin_sweep.hpp"
 #include "disturb_sweep.hpp"
+#include "actuator_sweep.hpp"
 #include "freq_sweep.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
@@ -1081,6 +1082,7 @@ int pime_margin_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
 }
 int pime_disturb_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
 int pime_freq_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
+int pime_actuator_sweep_supported(const pime_env* e, int32_t kind, int32_t md) { return pime_margin_sweep_supported(e, kind, md); }
 
 // workspace: float64[n_seg][rows][P][N], the copy of `pairs` the finishing launch reads when `pairs` is NULL; `fn` names the query
 static int64_t row_grid_workspace_bytes(const char* fn, const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len, int rows) {
@@ -1100,6 +1102,9 @@ int64_t pime_disturb_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t
 }
 int64_t pime_freq_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
     return row_grid_workspace_bytes("pime_freq_sweep_workspace_bytes", e, P, n_steps, seg_len, kFreqAllRows);
+}
+int64_t pime_actuator_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    return row_grid_workspace_bytes("pime_actuator_sweep_workspace_bytes", e, P, n_steps, seg_len, kActAllRows);
 }
 
 // the refusals of a row-grid entry point `fn` (its grid is `rows_name` in the messages); then the handle's device is current
@@ -1168,6 +1173,22 @@ int pime_freq_sweep(const pime_env* e, int32_t kind, int32_t md, const float* pa
         a.wave_len = wave_len;
         return launch_freq_sweep<S>(kind, md, a, excite, pairs, summary, actions, outputs, static_cast<double*>(workspace),
                                     static_cast<hipStream_t>(stream));
+    });
+}
+
+int pime_actuator_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actor, const double* priorK,
+                        const double* actuator, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints,
+                        int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
+                        double* commands, double* outputs, void* workspace, pime_stream stream) {
+    const RowGridCall c{kind, md, packed_actor, priorK, actuator, P, n_steps, seg_len, setpoints, n_setpoints, band, tail, summary, workspace};
+    if (int rc = row_grid_open("pime_actuator_sweep", "actuator", e, c)) return rc;
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        ActArgs<S> a{};
+        fill_row_grid_args(a, e, ph, wt, c);
+        a.commands = commands;
+        return launch_actuator_sweep<S>(kind, md, a, actuator, pairs, summary, actions, outputs, static_cast<double*>(workspace),
+                                        static_cast<hipStream_t>(stream));
     });
 }
 

@@ -52,6 +52,12 @@ FREQ_COLS = len(FREQ_COL_NAMES)
 FREQ_POINTS = {"setpoint": 0, "load": 1, "measurement": 2}
 FREQ_ROW_NAMES = ("yc", "ys", "uc", "us", "y0", "u0", "y2", "u2")
 FREQ_ROWS = len(FREQ_ROW_NAMES)
+# pime_actuator_sweep: the columns of an actuator row (enum pime_act_col) and the actuator rows it adds behind METRIC_NAMES
+# (enum pime_act_row), in order
+ACT_COL_NAMES = ("lo", "hi", "rate", "deadband", "qu", "qy")
+ACT_COLS = len(ACT_COL_NAMES)
+ACT_ROW_NAMES = ("sat_steps", "rate_steps", "hold_steps", "gap_peak", "gap_iae", "reversals", "tail_y_p2p", "tail_u_p2p")
+ACT_ROWS = len(ACT_ROW_NAMES)
 
 FIELD = dict(
     ph_x=0, ph_I=1, ph_r=2, ph_y=3, ph_A=4, ph_B=5, ph_C=6, ph_qww_V=7, ph_qc_V=8, ph_t=9, ph_episode=10,
@@ -208,7 +214,11 @@ _SIGNATURES = {
     "pime_freq_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
     "pime_freq_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
-    "pime_mpc_eval": (C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "pime_actuator_sweep_supported": (C.c_int, [_vp, _i32, _i32]),
+    "pime_actuator_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
+    "pime_actuator_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "pime_mpc_eval":(C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,
                                          _vp, _i32, _i32, _vp]),

@@ -42,7 +42,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .native import BAND_SIGNALS, BAND_STATS, DISTURB_ROW_NAMES, ENV_PH, FREQ_POINTS, FREQ_ROW_NAMES, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
+from .native import ACT_ROW_NAMES, BAND_SIGNALS, BAND_STATS, DISTURB_ROW_NAMES, ENV_PH, FREQ_POINTS, FREQ_ROW_NAMES, METRIC_NAMES, REPLAY_ROW_NAMES, SWEEP_STATS
 
 PH_SETPOINTS = (10., 6., 3., 8., 5.)
 WT_SETPOINTS = (3., 6., 9., 4., 2.)
@@ -717,6 +717,111 @@ def rejection_summary(result):
         with np.errstate(divide="ignore", invalid="ignore"):
             out["recovered"] = np.where(seen.any(axis=1), ok.sum(axis=1) / seen.sum(axis=1), np.nan)
     assert all(v.shape == (P,) for v in out.values())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ actuator and sensor limits
+ACT_OFF = (-np.inf, np.inf, np.inf, 0.0, 0.0, 0.0)      # a row with every stage off (columns native.ACT_COL_NAMES)
+# the reference rig (gym_control/envs/real_watertank.py): a 0 .. 10 V pump, a DAC byte (256 levels), an ADC at 10 / 504 V per count
+RIG_VOLTS, RIG_DAC_LEVELS, RIG_ADC_COUNTS = 10.0, 256, 504
+
+
+def actuator_grid(limits=(), rates=(), deadbands=(), qu=(), qy=()):
+    """The rows of `actuator_sweep` / `VecControlEnv.actuator_sweep`: the PRODUCT of the five axes, each axis led by its "off" value
+    -- limits: (lo, hi) pairs; rates, deadbands, qu, qy: scalars -- with `limits` the slowest and `qy` the fastest index, so row 0 is
+    always the all-off row `ACT_OFF`.  float64 [P, 6], P = the product of (1 + len(axis)), columns native.ACT_COL_NAMES."""
+    lim = [ACT_OFF[:2]] + [tuple(float(x) for x in v) for v in np.asarray(limits, dtype=np.float64).reshape(-1, 2)]
+    ax = [[off] + [float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)] for off, v in zip(ACT_OFF[2:], (rates, deadbands, qu, qy))]
+    rows = [[l[0], l[1], r, d, a, y] for l in lim for r in ax[0] for d in ax[1] for a in ax[2] for y in ax[3]]
+    return np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
+
+
+def rig_row(p_max_action=10.0):
+    """ONE row for the reference rig.  A command a in [-1, 1] becomes a * P_max / 2 + P_max / 2 volts, clipped to 0 .. 10 V and
+    floored onto 256 DAC levels; the levels come back through a 10-bit ADC at 10 / 504 V per count.  In normalised action units:
+    0 V is a = -1, 10 V is a = 20 / P_max - 1; one DAC level is (10 / 256) V = (10 / 256) / (P_max / 2) = 20 / (256 P_max).  The rig's
+    observation IS the ADC's volt reading (no level calibration in between) and a policy moves over reading those numbers where it
+    read the simulated levels, so one count is 10 / 504 observation units.  No rate limit, no dead-band.  float64 [6]."""
+    p = float(p_max_action)
+    if not (np.isfinite(p) and p > 0):
+        raise ValueError("rig_row: p_max_action must be finite and > 0")
+    return np.array([-1.0, 2.0 * RIG_VOLTS / p - 1.0, np.inf, 0.0, 2.0 * RIG_VOLTS / (RIG_DAC_LEVELS * p), RIG_VOLTS / RIG_ADC_COUNTS],
+                    dtype=np.float64)
+
+
+def actuator_sweep(env, rows, agent=None, axes=None, plants=None, setpoints=None, steps=None, band=None, tail=10, want_pairs=False):
+    """What do a real actuator and a real sensor do to the closed loop?  The step-response protocol of `env` (as
+    `disturbance_rejection`: the same start, set-points, steps, band and tail) under every row (lo, hi, rate, deadband, qu, qy) of
+    `rows` [P, 6] (`actuator_grid`, `rig_row`), over the plants in the env's lanes, in ONE call (`VecControlEnv.actuator_sweep`).
+    agent None: the prior controller alone, else an agent the fused evaluation serves.  axes / plants: as `disturbance_rejection`.
+    Returns a dict for `actuator_summary`: rows [P, 6], summary [P, n_segments, 16, 5] (rows `METRIC_NAMES` then `ACT_ROW_NAMES`,
+    stats `SWEEP_STATS`), pairs [n_segments, 16, P, N] and actions, commands, outputs [T, P, N], or None, steps, setpoints, band,
+    tail, n (the plants)."""
+    from .vec_env import check_actuator
+    is_ph = env.kind == ENV_PH
+    rows = check_actuator(rows)
+    if axes is not None:
+        plants = _grid(env, axes, "actuator_sweep")[3]
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    fused = _fused_policy(env, None, agent)
+    if fused is None or not hasattr(env, "actuator_supported") or not env.actuator_supported(fused[0]):
+        raise ValueError("actuator_sweep: the actuator sweep does not serve this env / agent (VecControlEnv.actuator_supported)")
+    _protocol_start(env, is_ph, steps, plants)
+    out = env.actuator_sweep(fused[0], fused[1], rows, len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band, tail=tail,
+                             want_pairs=want_pairs, want_trace=want_pairs)
+    host = lambda v: None if v is None else v.cpu().numpy()
+    got = out if want_pairs else {"summary": out}
+    return dict(rows=rows, summary=host(got["summary"]), pairs=host(got.get("pairs")), actions=host(got.get("actions")),
+                commands=host(got.get("commands")), outputs=host(got.get("outputs")), steps=int(steps), setpoints=setpoints, band=band,
+                tail=tail, n=int(env.num_envs))
+
+
+def _act_axis_rows(rows):
+    """axis name -> (row indices, a value per row ascending in harshness) of the rows with exactly that axis on."""
+    rows = np.asarray(rows, dtype=np.float64)
+    on = np.stack([np.isfinite(rows[:, 0]) | np.isfinite(rows[:, 1]), (rows[:, 2] > 0) & np.isfinite(rows[:, 2]), rows[:, 3] > 0,
+                   rows[:, 4] > 0, rows[:, 5] > 0], axis=1)
+    # harshness: a narrower span, a smaller rate, a wider dead-band, a coarser quantum
+    value = np.stack([rows[:, 1] - rows[:, 0], rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5]], axis=1)
+    out = {}
+    for j, (name, sign) in enumerate((("limits", -1.0), ("rate", -1.0), ("deadband", 1.0), ("qu", 1.0), ("qy", 1.0))):
+        idx = np.flatnonzero(on[:, j] & (on.sum(axis=1) == 1))
+        idx = idx[np.argsort(sign * value[idx, j], kind="stable")]
+        out[name] = (idx, value[idx, j])
+    return out
+
+
+def actuator_summary(result):
+    """An `actuator_sweep` result.  Per row, dict of float64 [P] --
+      itae_ratio    the worst plant's ITAE (the largest over the segments) over that of row 0, which must be the all-off row;
+      limit_cycle   the share of (plant, segment) pairs whose TAIL_Y_P2P exceeds the band: the output still swings at the segment's end
+                    (needs `pairs`; without them the share of segments whose worst plant does);
+      reversals     the median REVERSALS over the (plant, segment) pairs (needs `pairs`; NaN without them);
+    and per axis -- "limits" (the span hi - lo), "rate", "deadband", "qu", "qy" -- over the rows that have this axis alone on,
+    walking from the mildest value (the widest span, the largest rate, the smallest dead-band or quantum) to the harshest: the LAST
+    value up to which no plant limit-cycles, i.e. the tightest limit / the largest quantum the loop tolerates (key `<axis>_tolerated`;
+    NaN: the mildest value already cycles, or the grid has no such row)."""
+    summary = np.asarray(result["summary"], dtype=np.float64)
+    rows, band = np.asarray(result["rows"], dtype=np.float64), float(result["band"])
+    if np.isfinite(rows[0, :2]).any() or (rows[0, 2] > 0 and np.isfinite(rows[0, 2])) or (rows[0, 3:] > 0).any():
+        raise ValueError("actuator_summary: row 0 must be the all-off row (actuator_grid puts it there)")
+    st = {name: j for j, name in enumerate(SWEEP_STATS)}
+    at = {name: len(METRIC_NAMES) + j for j, name in enumerate(ACT_ROW_NAMES)}
+    itae = summary[:, :, METRIC_NAMES.index("itae"), st["max"]].max(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = dict(itae_ratio=itae / itae[0])
+    pairs = result.get("pairs")
+    if pairs is not None:
+        pairs = np.asarray(pairs, dtype=np.float64)
+        out["limit_cycle"] = (pairs[:, at["tail_y_p2p"]] > band).mean(axis=(0, 2))
+        out["reversals"] = np.median(pairs[:, at["reversals"]], axis=(0, 2))
+    else:
+        out["limit_cycle"] = (summary[:, :, at["tail_y_p2p"], st["max"]] > band).mean(axis=1)
+        out["reversals"] = np.full(len(rows), np.nan)
+    for name, (idx, vals) in _act_axis_rows(rows).items():
+        out[name + "_tolerated"] = _last_ok(vals, out["limit_cycle"][idx] == 0.0) if len(idx) else float("nan")
     return out
 
 

@@ -95,6 +95,12 @@ def build_parser():
                         "alone) on the plants of --robust_test, one launch each; writes disturbances.npz into the run directory")
     p.add_argument("--disturbance_onset", default=-1, type=int, metavar="K",
                    help="--disturbances: the step within every set-point segment at which the disturbance starts (default: half a segment)")
+    p.add_argument("--actuator", action="store_true",
+                   help="after training: saturation, slew-rate, dead-band, DAC- and ADC-quantum limits of the closed loop (trained agent AND "
+                        "prior alone) on the plants of --robust_test, one launch each, with the reference rig's row; writes "
+                        "actuator_sweep.npz into the run directory")
+    p.add_argument("--actuator_points", default=4, type=int, metavar="Q",
+                   help="--actuator: values per axis (limits, rate, dead-band, actuator quantum, sensor quantum), one axis at a time")
     p.add_argument("--bode", action="store_true",
                    help="after training: the loop's frequency response (trained agent AND prior alone) on the plants of --robust_test, one "
                         "launch each -- sinusoids at the set-point and in front of the actuator, lock-in rows, gain and phase margin, peak "
@@ -441,6 +447,68 @@ def disturbances(args, agent, cwd):
     return path
 
 
+def actuator_rows(points, p_max_action=10.0):
+    """The rows of --actuator: the all-off row, then per axis `points` values, one axis at a time (every other stage off), each halving
+    or doubling from a mild one -- clamps [-c, c] from 1 down, rates from 1 per step down, dead-bands and actuator quanta from 1 / 256
+    up, sensor quanta from 10 / 1024 up -- and the reference rig's row (protocols.rig_row) last.  float64 [2 + 5 * points, 6]."""
+    from . import protocols
+    q = max(int(points), 1)
+    halves = [0.5 ** j for j in range(q)]
+    fine = [2.0 ** j / 256 for j in range(q)]
+    rows = [protocols.actuator_grid(limits=[(-c, c) for c in halves]), protocols.actuator_grid(rates=halves)[1:],
+            protocols.actuator_grid(deadbands=fine)[1:], protocols.actuator_grid(qu=fine)[1:],
+            protocols.actuator_grid(qy=[2.0 ** j * 10 / 1024 for j in range(q)])[1:], protocols.rig_row(p_max_action)[None]]
+    return np.ascontiguousarray(np.concatenate(rows, axis=0))
+
+
+def actuator(args, agent, cwd):
+    """--actuator: the step-response protocol of --robust_test under a real actuator and sensor -- `actuator_rows(--actuator_points)`,
+    one axis at a time around the ideal row, and the reference rig's row -- on every plant of --robust_test's plant set; one launch for
+    the trained agent and one for the prior controller alone (protocols.actuator_sweep / actuator_summary).  Writes
+    <cwd>/actuator_sweep.npz -- rows, plants and per controller (prefix agent_ / prior_) summary and the actuator summary -- and prints
+    one line per row for each."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("actuator sweep skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    grid = actuator_rows(getattr(args, "actuator_points", 4))
+    out, found = {}, {}
+    for who, ag in (("agent", agent), ("prior", None)):
+        env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        fused = protocols._fused_policy(env, None, ag)
+        if fused is None or not hasattr(env, "actuator_supported") or not env.actuator_supported(fused[0]):
+            env.close()
+            print(f"actuator sweep skipped for the {who}: the actuator sweep does not serve this env / actor (actuator_supported)")
+            continue
+        res = protocols.actuator_sweep(env, grid, agent=ag, plants=plants, setpoints=setpoints, steps=steps, band=band, tail=tail,
+                                       want_pairs=True)
+        env.close()
+        found[who] = protocols.actuator_summary(res)
+        out[f"{who}_summary"] = res["summary"]
+        for k, v in found[who].items():
+            out[f"{who}_{k}"] = np.asarray(v)
+    if not found:
+        return None
+    path = os.path.join(cwd, "actuator_sweep.npz")
+    os.makedirs(cwd, exist_ok=True)
+    np.savez(path, rows=grid, plants=plants, setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, band=band, tail=tail,
+             metric_names=np.asarray(protocols.METRIC_NAMES + protocols.ACT_ROW_NAMES), **out)
+    print(f"actuator sweep: {len(grid)} rows x {len(plants)} plants -> {path}")
+    for who, r in found.items():
+        for p, row in enumerate(grid):
+            print(f"{who} clamp [{row[0]:g}, {row[1]:g}] rate {row[2]:g} dead-band {row[3]:g} qu {row[4]:.4g} qy {row[5]:.4g}: worst ITAE x "
+                  f"{r['itae_ratio'][p]:.3g}, limit cycle {r['limit_cycle'][p]:.2f}, reversals {r['reversals'][p]:g}")
+        print(f"{who} tolerated without a limit cycle: " + ", ".join(f"{k[:-10]} {r[k]:.4g}" for k in sorted(r) if k.endswith("_tolerated")))
+    return path
+
+
 def bode(args, agent, cwd):
     """--bode: under the step-response protocol of --robust_test, on every plant of its plant set, a sinusoid of --bode_amplitude at
     --bode_points frequencies -- whole numbers of cycles in the second half of every set-point segment, the first half letting the loop
@@ -580,6 +648,8 @@ def main(argv=None):
             margins(args, agent, kargs.cwd)
         if args.disturbances:
             disturbances(args, agent, kargs.cwd)
+        if args.actuator:
+            actuator(args, agent, kargs.cwd)
         if args.bode:
             bode(args, agent, kargs.cwd)
     return agent

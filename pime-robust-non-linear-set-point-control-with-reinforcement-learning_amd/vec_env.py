@@ -136,6 +136,23 @@ def check_disturb(rows, is_ph):
     return np.ascontiguousarray(rows)
 
 
+def check_actuator(rows):
+    """The rows of `VecControlEnv.actuator_sweep` as float64 [P, 6] (columns native.ACT_COL_NAMES), or ValueError: the shape, a limit
+    that is NaN, lo > hi, a rate, dead-band or quantum that is NaN or negative, a quantum that is infinite.  Off is spelled lo = -inf,
+    hi = +inf, rate = inf (or 0) and 0 for the dead-band and the quanta."""
+    rows = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != native.ACT_COLS or rows.shape[0] < 1:
+        raise ValueError(f"actuator_sweep: rows {tuple(rows.shape)} must be [P >= 1, {native.ACT_COLS}]")
+    lo, hi = rows[:, 0], rows[:, 1]
+    if np.any(np.isnan(lo)) or np.any(np.isnan(hi)) or np.any(lo > hi):
+        raise ValueError("actuator_sweep: a limit is NaN or lo > hi")
+    for j, name in ((2, "rate"), (3, "deadband"), (4, "qu"), (5, "qy")):
+        v = rows[:, j]
+        if np.any(np.isnan(v)) or np.any(v < 0) or (j >= 4 and np.any(np.isinf(v))):
+            raise ValueError(f"actuator_sweep: {name} is NaN, negative or an infinite quantum")
+    return np.ascontiguousarray(rows)
+
+
 def check_excite(rows, wave, L):
     """The rows and the table of `VecControlEnv.frequency_sweep` as float64 [P, 3] (columns native.FREQ_COL_NAMES) and [P, L, 2], or
     ValueError: a shape, a point that is not 0, 1 or 2, an amplitude that is not finite, an onset that is not a non-negative integer,
@@ -685,9 +702,10 @@ class VecControlEnv:
         return bool(supported(self._h, _EVAL_KINDS[packed_actor.kind], int(packed_actor.md)))
 
     def _row_grid_sweep(self, fn, R, packed_actor, priorK, rows, own, n_steps, setpoints, seg_len, band, tail, want_pairs, want_trace,
-                        before=()):
+                        before=(), commands=False):
         """The native call `fn` on the validated device tensor `rows` [P, columns]: R metric rows per pair and segment, `own` the
-        call's own arguments between P and n_steps, `before` those between the rows and P.  Returns what the public method documents."""
+        call's own arguments between P and n_steps, `before` those between the rows and P, `commands` a third trace between actions
+        and outputs (pime_actuator_sweep).  Returns what the public method documents."""
         k = self._prior_row(priorK)
         P, n_steps, seg_len = int(rows.shape[0]), int(n_steps), int(seg_len)
         ws_bytes = int(getattr(self._lib, fn + "_workspace_bytes")(self._h, P, n_steps, seg_len))
@@ -701,15 +719,20 @@ class VecControlEnv:
         actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
         outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
         # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
+        cmds = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if commands and want_trace else None
+        third = (native.ptr(cmds),) if commands else ()
         workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
         native.check(getattr(self._lib, fn)(
             self._h, kind, md, native.ptr(img), native.ptr(k), native.ptr(rows), *before, P, *own, n_steps, seg_len, sp_ptr, n_sp, float(band),
-            int(tail), native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs), native.ptr(workspace),
+            int(tail), native.ptr(pairs), native.ptr(summary), native.ptr(actions), *third, native.ptr(outputs), native.ptr(workspace),
             self._stream()), fn)
         del workspace
         if not (want_pairs or want_trace):
             return summary
-        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+        out = {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+        if commands:
+            out["commands"] = cmds
+        return out
 
     # -- loop-perturbation sweep (delay, gain and sensor-noise margins) ---------------------------------------------
     def margin_supported(self, packed_actor=None):
@@ -806,6 +829,38 @@ class VecControlEnv:
             wt = torch.as_tensor(w, dtype=torch.float64).to(self.device).contiguous()
         return self._row_grid_sweep("pime_freq_sweep", native.METRIC_ROWS + native.FREQ_ROWS, packed_actor, priorK, rt, (), n_steps,
                                     setpoints, seg_len, band, tail, want_pairs, want_trace, before=(native.ptr(wt), L))
+
+    # -- actuator-limits sweep (saturation, slew, dead-band, DAC and ADC quanta) ------------------------------------------
+    def actuator_supported(self, packed_actor=None):
+        """Does `actuator_sweep` serve this env (with this packed actor, or the prior controller alone)?
+        (pime_actuator_sweep_supported: the classes of `margin_sweep`.)"""
+        return self._row_grid_supported(self._lib.pime_actuator_sweep_supported, packed_actor)
+
+    def actuator_sweep(self, packed_actor, priorK, rows, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_pairs=False,
+                       want_trace=False):
+        """A grid of ACTUATOR and SENSOR limits over every lane's plant in ONE call (pime_actuator_sweep, csrc/actuator_sweep.hip):
+        every (row, lane) pair runs the loop of `rollout_eval_metrics` from the lane state as it stands, the controller reading the
+        measured plant outputs on the sensor's quantum `qy` and its command passing, in this order, a dead-band (`deadband`: hold
+        within it of the present position), a slew limit (`rate` per step), the actuator's quantum `qu` and the clamp [`lo`, `hi`] --
+        rows float64 [P, 6], columns native.ACT_COL_NAMES; a stage is OFF for lo = -inf / hi = +inf (or NaN) and for a rate (other
+        than 0 < rate < inf), dead-band or quantum that is not > 0, and a row with every stage off is bit for bit
+        `rollout_eval_metrics`.  packed_actor None = the prior controller alone.  Returns summary float64 [P, n_segments, 16, 5] --
+        per row, segment and metric row (native.METRIC_NAMES on the APPLIED action, then native.ACT_ROW_NAMES: the steps the clamp,
+        the slew limit and the dead-band acted on, the peak and the sum of |command - applied|, the reversals of the applied action,
+        the peak-to-peak of the output and of the applied action over the last `tail` steps) the stats native.SWEEP_STATS over the
+        lanes, exactly as `prior_sweep` -- or, with `want_pairs` and / or `want_trace`, a dict with "summary", "pairs" float64
+        [n_segments, 16, P, N] and "actions", "commands", "outputs" float64 [n_steps, P, N] (the applied action, the controller's
+        command and the controlled output after each step).  ValueError for a bad row (`check_actuator`); a device tensor is taken
+        as given (the kernel decodes, it does not validate), so a capture works.  The env itself is read, never advanced
+        (definitions in include/pime_hip.h)."""
+        if torch.is_tensor(rows) and rows.is_cuda:
+            at = rows
+            if at.dtype != torch.float64 or at.dim() != 2 or at.shape[1] != native.ACT_COLS or at.shape[0] < 1 or not at.is_contiguous():
+                raise ValueError(f"actuator_sweep: a device tensor of rows must be contiguous float64 [P >= 1, {native.ACT_COLS}]")
+        else:
+            at = torch.as_tensor(check_actuator(rows), dtype=torch.float64).to(self.device).contiguous()
+        return self._row_grid_sweep("pime_actuator_sweep", native.METRIC_ROWS + native.ACT_ROWS, packed_actor, priorK, at, (), n_steps,
+                                    setpoints, seg_len, band, tail, want_pairs, want_trace, commands=True)
 
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
