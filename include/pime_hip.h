@@ -834,6 +834,47 @@ int pime_actuator_sweep(const pime_env* env, int32_t kind, int32_t md, const flo
                         int32_t n_setpoints, double band, int32_t tail, double* pairs, double* summary, double* actions,
                         double* commands, double* outputs, void* workspace, pime_stream stream);
 
+/* -- policy sweep (csrc/policy_sweep.hip) -----------------------------------------------------------------------------
+ * Which of my controllers -- the snapshots of one training run, the seeds of one configuration -- is best on its WORST plant?  The
+ * sweeps above take one packed actor and one priorK; this one adds the policy as the grid's axis.  ONE call runs every (policy row p,
+ * plant lane i) pair of P packed actors over the N lanes of the handle.  A pair runs the loop of pime_rollout_eval_metrics (set-point
+ * boundaries every seg_len steps, the lane step, the metrics with the same band and tail) on a register copy of lane i as the handle
+ * holds it, under a_env = tanh(mean_p(obs)) + obs @ priorK[p] as pime_rollout_eval forms it (the prior term in double, ascending j
+ * from 0.0): row p uses image p and its own prior gain.  A pair of row p is bit for bit a lane of pime_rollout_eval_metrics(kind, md,
+ * image p, priorK[p]) from the same lane state; the tank's process noise is keyed on the plant's global lane, so every policy meets
+ * the same disturbance (common random numbers, as every gain of pime_prior_sweep does).
+ *   kind, md      one class for all P images: one of the four policy kinds of pime_rollout_eval at width 64 or 128.  kind = -1 is
+ *                 REFUSED: under the prior controller alone a grid of gains is pime_prior_sweep.
+ *   packed_actors [dev] P images of pime_mlp_packed_floats(kind, D, Di, md) floats (pime_mlp_pack), image p at packed_actors +
+ *                 p * image_stride; 16-byte aligned
+ *   image_stride  floats between two images: >= the packed size and a multiple of 4; the padding is never read
+ *   priorK        [dev] float64[P, D] -- on the DEVICE, unlike the single-policy calls: it is read with the row
+ *   n_steps, seg_len, setpoints [host], n_setpoints, band, tail: as pime_rollout_eval_metrics (same checks, same messages)
+ *   pairs    [dev] float64[n_segments, PIME_METRIC_ROWS, P, N] or NULL
+ *   summary  [dev] float64[P, n_segments, PIME_METRIC_ROWS, PIME_SWEEP_STATS]: each row over the N plants, EXACTLY the statistics and
+ *            the addition order of pime_prior_sweep's summary
+ *   actions  [dev] float64[n_steps, P, N] or NULL: a_env                 outputs  [dev] float64[n_steps, P, N] or NULL: y after the step
+ *            NULL pairs / actions / outputs is the normal use and does not change a bit of summary.
+ *   workspace [dev] pime_policy_sweep_workspace_bytes(env, P, n_steps, seg_len) bytes (-1: bad arguments); private layout, every byte
+ *            read was written by the same call
+ * A tile is 16 plants of one row; a 256-thread workgroup takes a quad of four tiles of the SAME row, and persistent workgroups each
+ * walk a contiguous range of quads, so the image in LDS is re-staged only when the row changes; a finishing launch (the row grid's)
+ * reduces the rows per policy.  The handle is READ and never written (state, counters, observations bit-unchanged), but must have been
+ * reset.  Asynchronous on the caller's stream, capturable, no allocation, no synchronisation, no atomics: two calls give the same
+ * bits; a pair's result does not depend on P, N or its position in the grid.
+ * Served (pime_policy_sweep_supported == 1): the classes of pime_margin_sweep WITH a policy (32: pH and the Integrator water tank,
+ * PIME_STATE_F64 and PIME_STATE_MIXED, four kinds, widths 64 and 128).  kind = -1, width 256, PIME_STATE_MIXED16 handles and the
+ * tank's Stacking observation are REFUSED (0, and the call returns PIME_ERR_ARG).
+ * PIME_ERR_ARG before any launch, with a message naming the argument: the refused classes, P < 1, P * N > 2^31 - 1, NULL
+ * packed_actors / summary / priorK / workspace, an image_stride below the packed size or not a multiple of 4, a base that is not
+ * 16-byte aligned, and the schedule / band / tail cases of pime_rollout_eval_metrics. */
+int pime_policy_sweep_supported(const pime_env* env, int32_t kind, int32_t md);
+int64_t pime_policy_sweep_workspace_bytes(const pime_env* env, int32_t P, int32_t n_steps, int32_t seg_len);
+int pime_policy_sweep(const pime_env* env, int32_t kind, int32_t md, const float* packed_actors, int64_t image_stride,
+                      const double* priorK, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
+                      double band, int32_t tail, double* pairs, double* summary, double* actions, double* outputs, void* workspace,
+                      pime_stream stream);
+
 /* -- fused off-policy exploration-----------------------------------------------------------------------------------
  * replaces, per lock-step of the vectorised off-policy agents: AgentBase.explore_env's body (elegantrl/agent.py:54-70) with
  * AgentTD3.select_action (:300-306: a = (act(s) + N(0, explore_noise)).clamp(-1, 1)), env.step, and ReplayBuffer.append_buffer

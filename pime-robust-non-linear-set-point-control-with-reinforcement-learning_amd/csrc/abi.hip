@@ -18,6 +18,7 @@
 #include "disturb_sweep.hpp"
 #include "actuator_sweep.hpp"
 #include "freq_sweep.hpp"
+#include "policy_sweep.hpp"
 #include "rollout_offpolicy.hpp"
 #include "td3.hpp"
 #include "sac.hpp"
@@ -1189,6 +1190,51 @@ int pime_actuator_sweep(const pime_env* e, int32_t kind, int32_t md, const float
         a.commands = commands;
         return launch_actuator_sweep<S>(kind, md, a, actuator, pairs, summary, actions, outputs, static_cast<double*>(workspace),
                                         static_cast<hipStream_t>(stream));
+    });
+}
+
+// ---- the policy sweep (policy_sweep.hip): P packed actors, each with its own prior gain, over the plants of the handle --------------
+int pime_policy_sweep_supported(const pime_env* e, int32_t kind, int32_t md) {
+    return kind != -1 && pime_margin_sweep_supported(e, kind, md) ? 1 : 0;   // (the prior alone: pime_prior_sweep)
+}
+int64_t pime_policy_sweep_workspace_bytes(const pime_env* e, int32_t P, int32_t n_steps, int32_t seg_len) {
+    return row_grid_workspace_bytes("pime_policy_sweep_workspace_bytes", e, P, n_steps, seg_len, PIME_METRIC_ROWS);
+}
+
+int pime_policy_sweep(const pime_env* e, int32_t kind, int32_t md, const float* packed_actors, int64_t image_stride,
+                      const double* priorK, int32_t P, int32_t n_steps, int32_t seg_len, const double* setpoints, int32_t n_setpoints,
+                      double band, int32_t tail, double* pairs, double* summary, double* actions, double* outputs, void* workspace,
+                      pime_stream stream) {
+    const char* fn = "pime_policy_sweep";
+    PIME_REQUIRE(e != nullptr, "NULL env handle");
+    PIME_REQUIRE(e->cfg.state_mode == PIME_STATE_F64 || e->cfg.state_mode == PIME_STATE_MIXED,
+                 "%s: state_mode %d is not served (PIME_STATE_F64 or PIME_STATE_MIXED; PIME_STATE_MIXED16 is refused)", fn,
+                 (int)e->cfg.state_mode);
+    PIME_REQUIRE(e->cfg.kind == PIME_ENV_PH || e->cfg.num_stack == 0,
+                 "%s: the Stacking observation (num_stack %d) is not served (pH or the Integrator water tank)", fn, (int)e->cfg.num_stack);
+    PIME_REQUIRE(kind != -1, "%s: kind -1 (the prior controller alone) is not served: a grid of prior gains is pime_prior_sweep", fn);
+    PIME_REQUIRE(md != 256, "%s: md %d is not served (64 or 128; width 256 is the streamed family)", fn, md);
+    PIME_REQUIRE(pime_policy_sweep_supported(e, kind, md), "%s: not served for actor kind %d width md %d (%s_supported)", fn, kind, md, fn);
+    const int64_t floats = pime_mlp_packed_floats(kind, e->obs_dim, kind == PIME_MLP_MODULAR_ACTOR ? 1 : 0, md);
+    PIME_REQUIRE(floats > 0, "%s: no packed image for actor kind %d width md %d on %d observation columns", fn, kind, md, (int)e->obs_dim);
+    if (int rc = check_policy_sweep_args(fn, e->cfg.n_envs, packed_actors, image_stride, floats, priorK, P, n_steps, seg_len, setpoints,
+                                         n_setpoints, band, tail, summary))
+        return rc;
+    PIME_REQUIRE(workspace != nullptr, "%s: workspace is NULL", fn);
+    if (!e->was_reset) { set_error("%s before pime_env_reset", fn); return PIME_ERR_STATE; }
+    if (int rc = use_device(e)) return rc;
+    return with_state(e, [&](const auto& ph, const auto& wt) {
+        using S = state_scalar_t<decltype(ph)>;
+        PolicyArgs<S> a{};
+        fill_grid_args(a, e, ph, wt);
+        a.P = P;
+        a.n_seg = sweep_segments(n_steps, seg_len);
+        a.img = packed_actors;
+        a.stride = image_stride;
+        a.K = priorK;
+        fill_sweep_schedule(a.s, n_steps, seg_len, setpoints, n_setpoints, band, tail);
+        return launch_policy_sweep<S>(kind, md, a, pairs, summary, actions, outputs, static_cast<double*>(workspace),
+                                      static_cast<hipStream_t>(stream));
     });
 }
 

@@ -47,6 +47,7 @@ class Arguments:
         self.eval_gap = 5
         self.eval_times1 = 2 ** 2
         self.eval_times2 = 2 ** 4
+        self.checkpoints = 0       # > 0: the Evaluator keeps the last M evaluated actors (train.py --checkpoints / --select_policy)
         self.random_seed = 0
         # attributes the reference's train.py attaches ad hoc and run.py then reads unguarded (run.py:136-160,174-175)
         self.SCN_kwargs = {}
@@ -154,7 +155,9 @@ def train_and_evaluate(args):
     if_on_policy = getattr(agent, "if_on_policy", False)
     buffer = make_buffer(agent, env, args.max_memo, args.if_per)
     evaluator = Evaluator(cwd=cwd, agent_id=args.gpu_id, device=agent.device, env=env_eval, eval_gap=args.eval_gap,
-                          eval_times1=args.eval_times1, eval_times2=args.eval_times2, is_main=is_main)
+                          eval_times1=args.eval_times1, eval_times2=args.eval_times2, is_main=is_main,
+                          checkpoints=getattr(args, "checkpoints", 0))
+    args.evaluator = evaluator   # (train.py --select_policy reads its snapshots after training)
     if_reach_goal = evaluator.evaluate_act(agent)
     logger.dump(step=0)
 
@@ -191,7 +194,7 @@ def train_and_evaluate(args):
 
 
 class Evaluator:
-    def __init__(self, cwd, agent_id, eval_times1, eval_times2, eval_gap, env, device, is_main=True):
+    def __init__(self, cwd, agent_id, eval_times1, eval_times2, eval_gap, env, device, is_main=True, checkpoints=0):
         self.is_main = is_main   # False on data-parallel ranks > 0: evaluate (same call sequence on the shared env) but write nothing
         self.recorder = [(0., -np.inf, 0., 0., 0.)]  # total_step, r_avg, r_std, obj_a, obj_c
         self.r_max = -np.inf
@@ -203,6 +206,10 @@ class Evaluator:
         self.used_time = None
         self.start_time = time.time()
         self.eval_func_time = 1
+        # checkpoints M > 0: the last M evaluated actors are kept (`snapshots`, oldest first) and the nominal-best one besides
+        # (`best_snapshot`), each with its packed image and prior gain as the fused evaluation read them.  0: nothing is recorded.
+        self.checkpoints = max(int(checkpoints), 0)
+        self.snapshots, self.best_snapshot = [], None
         if is_main:
             print(f"{'ID':>2}  {'Step':>8}  {'MaxR':>8} |{'avgR':>8}  {'stdR':>8}   {'objA':>8}  {'objC':>8} |")
 
@@ -211,6 +218,40 @@ class Evaluator:
         """What maps an observation to the deterministic env action: the actor module itself (its forward adds the prior term
         for the residual PPO actors), or the agent's `eval_policy` where the actor's forward is the residual action alone."""
         return getattr(agent, "eval_policy", None) or agent.act
+
+    def _snapshot(self, agent, r_avg, is_best):
+        """Record the actor just evaluated: its state_dict on its device, and -- where the fused evaluation serves it on this env --
+        a copy of its packed image and prior gain (kernels' sign), the row `snapshot_policies` stacks."""
+        if self.checkpoints <= 0:
+            return
+        fused = agent.fused_eval_policy(self.env) if hasattr(self.env, "num_envs") and hasattr(agent, "fused_eval_policy") else None
+        snap = dict(step=int(self.total_step), r_avg=float(r_avg),
+                    state_dict={k: v.detach().clone() for k, v in agent.act.state_dict().items()}, image=None, K=None, cls=None)
+        if fused is not None:
+            pk = fused[0]
+            snap.update(image=pk.packed.detach().clone(), K=np.array(fused[1], dtype=np.float64).reshape(-1),
+                        cls=(pk.kind, pk.D, pk.Di, pk.md))
+        self.snapshots.append(snap)
+        del self.snapshots[:-self.checkpoints]
+        if is_best:
+            self.best_snapshot = snap
+
+    def snapshot_list(self):
+        """The recorded snapshots, oldest first, the nominal-best one in front when the ring no longer holds it."""
+        head = [] if self.best_snapshot is None or any(s is self.best_snapshot for s in self.snapshots) else [self.best_snapshot]
+        return head + list(self.snapshots)
+
+    def snapshot_policies(self):
+        """(ops.PackedPolicies of `snapshot_list()`, that list), or (None, list) when a snapshot has no packed image (the fused
+        evaluation does not serve the agent on the evaluator's env) or nothing was recorded."""
+        from types import SimpleNamespace
+        from ..ops import PackedPolicies
+        snaps = self.snapshot_list()
+        if not snaps or any(s["image"] is None or s["cls"] != snaps[0]["cls"] for s in snaps):
+            return None, snaps
+        kind, D, Di, md = snaps[0]["cls"]
+        shim = lambda s: SimpleNamespace(kind=kind, D=D, Di=Di, md=md, packed=s["image"])
+        return PackedPolicies.from_packed([(shim(s), s["K"]) for s in snaps]), snaps
 
     def _returns(self, act, times, agent=None):
         if hasattr(self.env, "num_envs"):  # one launch evaluates num_envs episodes at once
@@ -230,6 +271,9 @@ class Evaluator:
             self.r_max = r_avg
             if self.is_main:
                 agent.save_load_model(self.cwd, if_save=True)
+            self._snapshot(agent, r_avg, True)
+        else:
+            self._snapshot(agent, r_avg, False)
         logger.record("rollout/ep_rew_mean", r_avg)
         logger.record("rollout/ep_rew_std", r_std)
         logger.record("rollout/log_rew_max", self.r_max)
@@ -256,6 +300,9 @@ class Evaluator:
                 if self.is_main:
                     agent.save_load_model(self.cwd, if_save=True)
                     print(f"{self.agent_id:<2}  {self.total_step:8.2e}  {self.r_max:8.2f} |")
+                self._snapshot(agent, r_avg, True)
+            else:
+                self._snapshot(agent, r_avg, False)
             logger.record("rollout/ep_rew_mean", r_avg)
             logger.record("rollout/ep_rew_std", r_std)
             logger.record("rollout/log_rew_max", self.r_max)

@@ -218,6 +218,10 @@ _SIGNATURES = {
     "pime_actuator_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
     "pime_actuator_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp]),
+    "pime_policy_sweep_supported": (C.c_int, [_vp, _i32, _i32]),
+    "pime_policy_sweep_workspace_bytes": (C.c_int64, [_vp, _i32, _i32, _i32]),
+    "pime_policy_sweep": (C.c_int, [_vp, _i32, _i32, _vp, C.c_int64, _vp, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
     "pime_mpc_eval":(C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _i32, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pime_rollout_offpolicy_supported": (C.c_int, [_vp, _i32]),
     "pime_rollout_offpolicy":(C.c_int, [_vp, _i32, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, C.c_uint64, C.c_uint32, _vp, _vp,

@@ -108,6 +108,87 @@ class PackedMLP:
         return out
 
 
+class PackedPolicies:
+    """A stack of P packed actors of ONE class (kind, D, Di, md), each with its own prior gain: the policy axis of
+    `VecControlEnv.policy_sweep` (pime_policy_sweep).  Holds `packed`, one float32 [P, stride] device tensor -- row p the forward image
+    of policy p as `PackedMLP.packed` held it when it was added; stride = the packed size rounded up to 4 floats, the padding never
+    read -- and `K`, the float64 [P, D] table of prior gains in the KERNELS' sign (a = obs @ K[p]) on the same device.  Rows are
+    copies: a later `repack()` of the source does not reach them."""
+
+    def __init__(self, kind, state_dim, integrator_dim, mid_dim, device, capacity=8):
+        self.kind, self.D, self.Di, self.md = kind, int(state_dim), int(integrator_dim), int(mid_dim)
+        self.device = torch.device(device)
+        n = native.lib().pime_mlp_packed_floats(_KINDS[kind], self.D, self.Di, self.md)
+        if n <= 0:
+            raise native.PimeError(f"fused MLP forward unsupported for {kind} D={state_dim} width={mid_dim}: {native.last_error()}")
+        self.floats, self.stride = int(n), (int(n) + 3) // 4 * 4
+        self._images = torch.zeros((max(int(capacity), 1), self.stride), dtype=torch.float32, device=self.device)
+        self._gains = torch.zeros((max(int(capacity), 1), self.D), dtype=torch.float64, device=self.device)
+        self.device = self._images.device   # ("cuda" -> the indexed device the rows live on)
+        self.P = 0
+
+    def __len__(self):
+        return self.P
+
+    @property
+    def packed(self):
+        return self._images[:self.P]
+
+    @property
+    def K(self):
+        return self._gains[:self.P]
+
+    def _same_class(self, pk):
+        return (pk.kind, pk.D, pk.Di, pk.md) == (self.kind, self.D, self.Di, self.md) and pk.packed.device == self.device
+
+    def _gain_row(self, K):
+        if torch.is_tensor(K):
+            k = K.detach().reshape(-1).to(device=self.device, dtype=torch.float64)
+        else:
+            import numpy as np
+            k = torch.as_tensor(np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))).to(self.device)
+        if k.numel() != self.D:
+            raise ValueError(f"PackedPolicies: a prior gain of {k.numel()} components for {self.D} observation columns")
+        return k
+
+    def append(self, pk, K):
+        """A device-to-device copy of `pk.packed` as it is now, and of the gain row K (kernels' sign).  Returns the new row's index."""
+        if not self._same_class(pk):
+            raise ValueError(f"PackedPolicies: a packed actor of class {(pk.kind, pk.D, pk.Di, pk.md)} on {pk.packed.device} does not "
+                             f"join a stack of class {(self.kind, self.D, self.Di, self.md)} on {self.device}")
+        k = self._gain_row(K)
+        if self.P == self._images.shape[0]:   # grow by doubling: the rows kept, bit for bit
+            images = torch.zeros((2 * self.P, self.stride), dtype=torch.float32, device=self.device)
+            gains = torch.zeros((2 * self.P, self.D), dtype=torch.float64, device=self.device)
+            images[:self.P].copy_(self._images)
+            gains[:self.P].copy_(self._gains)
+            self._images, self._gains = images, gains
+        self._images[self.P, :self.floats].copy_(pk.packed)
+        self._gains[self.P].copy_(k)
+        self.P += 1
+        return self.P - 1
+
+    @classmethod
+    def from_packed(cls, pairs):
+        """pairs: [(PackedMLP, K), ...], one class, one device."""
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("PackedPolicies.from_packed: no policies")
+        first = pairs[0][0]
+        self = cls(first.kind, first.D, first.Di, first.md, first.packed.device, capacity=len(pairs))
+        for pk, K in pairs:
+            self.append(pk, K)
+        return self
+
+    @classmethod
+    def from_state_dicts(cls, kind, sds, Ks, state_dim, integrator_dim=0):
+        """One row per state_dict of `sds` (device tensors, as `PackedMLP.from_state_dict` takes them) with the gain row of `Ks`."""
+        sds, Ks = list(sds), list(Ks)
+        if len(sds) != len(Ks):
+            raise ValueError(f"PackedPolicies.from_state_dicts: {len(sds)} state_dicts and {len(Ks)} gains")
+        return cls.from_packed([(PackedMLP.from_state_dict(kind, sd, state_dim, integrator_dim), K) for sd, K in zip(sds, Ks)])
+
+
 class FusedPPOGrad:
     """Minibatch loss gradients of (actor, critic) by the fused HIP kernels (csrc/ppo_train.hip), written straight
     into the parameters' .grad tensors.  Everything between drawing the minibatch indices and `optimizer.step()`.

@@ -502,6 +502,65 @@ def tune_prior(env, gains, axes=None, plants=None, setpoints=None, steps=None, b
                 best_index=best, best_gain=gains[best].copy())
 
 
+# ------------------------------------------------------------------------------------------------ policy sweep
+def policy_sweep(env, policies, axes=None, plants=None, setpoints=None, steps=None, band=None, tail=10, want_pairs=False):
+    """Which of these controllers is best on its worst plant?  The step-response protocol of `env` (as `step_response_metrics`: the
+    same start, set-points, steps, band and tail) under every row of `policies` (an `ops.PackedPolicies` stack: P packed actors of
+    one class, each with its own prior gain), over the plants in the env's lanes, in ONE call (`VecControlEnv.policy_sweep`).  axes:
+    a plant grid as `robust_grid` takes it, or plants [N, P]: written into the lanes; neither: every lane keeps the plant its reset
+    draws.  Returns a dict for `select_policy`: summary [P, n_segments, 8, 5] (stats `SWEEP_STATS`), settled int64 [P] (the plants
+    of a row that are finite in every metric row and inside `band` at the end of every segment; counted on the device), pairs
+    [n_segments, 8, P, N] or None, steps, setpoints, band, tail, n (the plants)."""
+    is_ph = env.kind == ENV_PH
+    if axes is not None:
+        plants = _grid(env, axes, "policy_sweep")[3]
+    setpoints = tuple(setpoints if setpoints is not None else (PH_SETPOINTS if is_ph else WT_SETPOINTS))
+    steps = steps or (50 if is_ph else env.max_step)
+    band = 0.05 if band is None else band
+    if not hasattr(env, "policy_supported") or not env.policy_supported(policies):
+        raise ValueError("policy_sweep: the policy sweep does not serve this env / stack of actors (VecControlEnv.policy_supported)")
+    _protocol_start(env, is_ph, steps, plants)
+    out = env.policy_sweep(policies, len(setpoints) * steps, setpoints=setpoints, seg_len=steps, band=band, tail=tail, want_pairs=True)
+    pairs = out["pairs"]
+    fit = torch.isfinite(pairs).all(dim=1) & (pairs[:, METRIC_NAMES.index("settling_step")] < steps)    # [S, P, N]
+    settled = fit.all(dim=0).sum(dim=1).cpu().numpy().astype(np.int64)
+    return dict(summary=out["summary"].cpu().numpy(), settled=settled, pairs=pairs.cpu().numpy() if want_pairs else None, steps=int(steps),
+                setpoints=setpoints, band=band, tail=tail, n=int(env.num_envs))
+
+
+def select_policy(result, cost="itae", robust="worst"):
+    """The row of a `policy_sweep` result to deploy, in the vocabulary of `tune_prior`.  cost: a name of `METRIC_NAMES`; robust
+    "worst": a policy costs the sum over segments of the row's MAXIMUM over the plants, "mean": of its mean over the plants.  A
+    policy is FIT when every plant is finite in every segment and metric row and settles in every segment (result["settled"] ==
+    result["n"]); an unfit policy ranks behind every fit one, whatever its cost, and among policies of one kind the smaller cost
+    wins, a non-finite cost counting as +inf; ties go to the lowest row.  Returns a dict:
+      best_index                     the chosen row
+      nominal_index                  the row the same rule chooses with the plant-MEAN cost: what a nominal ranking would deploy
+      cost [P]                       the cost the choice ranked (worst_cost or mean_cost)
+      mean_cost, worst_cost [P]      both costs of every policy
+      worst_plant int64 [P, n_segments]   the lane with the largest value of the cost row
+      settled int64 [P], fit bool [P]
+      order int64 [P]                every row, best first"""
+    if cost not in METRIC_NAMES or robust not in ("worst", "mean"):
+        raise ValueError(f"select_policy: cost {cost!r} must be one of {METRIC_NAMES} and robust {robust!r} 'worst' or 'mean'")
+    summary = np.asarray(result["summary"], dtype=np.float64)
+    n, settled = int(result["n"]), np.asarray(result["settled"], dtype=np.int64).reshape(-1)
+    st = {name: j for j, name in enumerate(SWEEP_STATS)}
+    row = METRIC_NAMES.index(cost)
+    worst = summary[:, :, row, st["max"]].sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = (summary[:, :, row, st["sum"]] / summary[:, :, row, st["finite"]]).sum(axis=1)
+    fit = (summary[:, :, :, st["finite"]] == n).all(axis=(1, 2)) & (settled == n)
+
+    def rank(c):
+        c = np.where(np.isfinite(c), c, np.inf)
+        return np.lexsort((np.arange(len(c)), c, ~fit))     # unfit last, then the cost, then the row
+    order = rank(worst if robust == "worst" else mean)
+    return dict(best_index=int(order[0]), nominal_index=int(rank(mean)[0]), cost=(worst if robust == "worst" else mean).copy(),
+                mean_cost=mean, worst_cost=worst, worst_plant=summary[:, :, row, st["argmax"]].astype(np.int64), settled=settled, fit=fit,
+                order=order.astype(np.int64))
+
+
 # ------------------------------------------------------------------------------------------------ receding-horizon baseline
 def mpc_baseline(env, plants=None, setpoints=None, steps=None, horizon=20, passes=2, rho=0.0, model=None, band=None, tail=10, trace=False):
     """How good could ANY controller be on each plant?  The step-response protocol of `env` (as `step_response_metrics`: the same

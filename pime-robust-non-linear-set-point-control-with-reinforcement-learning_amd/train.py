@@ -90,6 +90,15 @@ def build_parser():
     p.add_argument("--margins_points", default=0, type=int,
                    help="--margins: instead of the --robust_test plants, a grid of this many points per plant parameter over the "
                         "env's ensemble ranges")
+    p.add_argument("--checkpoints", default=0, type=int, metavar="M",
+                   help="keep the last M evaluated actors (and the nominal-best one) in memory for --select_policy (0 = off)")
+    p.add_argument("--select_policy", action="store_true",
+                   help="after training: every kept actor of --checkpoints on the plants of --robust_test in ONE launch; writes "
+                        "policy_sweep.npz and actor_robust.pth (the actor with the best worst-plant ITAE) into the run directory; "
+                        "actor.pth stays the nominal best")
+    p.add_argument("--select_points", default=0, type=int,
+                   help="--select_policy: instead of the --robust_test plants, a grid of this many points per plant parameter over the "
+                        "env's ensemble ranges")
     p.add_argument("--disturbances", action="store_true",
                    help="after training: load steps at the plant input and steps of the plant's parameters (trained agent AND prior "
                         "alone) on the plants of --robust_test, one launch each; writes disturbances.npz into the run directory")
@@ -152,6 +161,7 @@ def prepare_train(args, env):
               "eval_gap", "fix_K", "frozen_modular_integrator", "frozen_transfer", "test_render_times", "target_step",
               "load"):
         setattr(kargs, k, getattr(args, k))
+    kargs.checkpoints = int(getattr(args, "checkpoints", 0))
     if IF_ONPOLICY[algo]:
         kargs.max_memo = args.target_step
     kargs.agent = MODELS[algo](device=args.device)
@@ -391,6 +401,59 @@ def margins(args, agent, cwd):
     side = "  ".join(f"{who} {found[who]['delay_margin']:g}" for who in ("agent", "prior") if who in found)
     print(f"margins: {len(grid)} loop perturbations x {len(plants)} plants -> {path}")
     print(f"delay margin (sample periods, every plant settles and worst-plant ITAE <= 2 x nominal): {side}")
+    return path
+
+
+def select_policy(args, evaluator, cwd):
+    """--select_policy: every actor the evaluator kept (--checkpoints M: the last M evaluated ones and the nominal-best one) under the
+    step-response protocol of --robust_test on every plant of its plant set (or, with --select_points P, of a P-per-parameter grid
+    over the env's ensemble ranges), in ONE launch (protocols.policy_sweep), and the choice by worst-plant ITAE next to the choice a
+    plant-mean ranking makes (protocols.select_policy).  Writes <cwd>/policy_sweep.npz -- summary, plants, the cost table (mean_cost,
+    worst_cost, worst_plant, settled, fit, order), best_index, nominal_index and the training step and evaluation return of each
+    snapshot -- and <cwd>/actor_robust.pth, the chosen actor's state_dict; actor.pth is not touched.  Prints both choices."""
+    from . import protocols
+    if "Stacking" in args.env:
+        print("policy selection skipped: the step-response protocol is defined on the Integrator observation, not on Stacking frames")
+        return None
+    policies, snaps = evaluator.snapshot_policies() if evaluator is not None else (None, [])
+    if policies is None:
+        print("policy selection skipped: no snapshots the fused evaluation serves (--checkpoints M with M > 0, actor widths 64 / 128)")
+        return None
+    is_ph = "NonLinearWaterTank" not in args.env
+    setpoints = protocols.PH_SETPOINTS if is_ph else protocols.WT_SETPOINTS
+    steps, band, tail = (50 if is_ph else 500), 0.05, 10
+    overrides = {} if is_ph else {"reward_type": args.reward_type}
+    if args.env_zero_noise:
+        overrides["noise_scale"] = 0.
+    plants = np.asarray(protocols.PH_PARAM_GRID if is_ph else protocols.WT_ROBUST_PLANTS, dtype=np.float64)
+    n = int(args.select_points)
+    if n > 0:
+        probe = gym_control.make_vec(args.env, 1, device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+        ranges = (probe.qww_Vrange, probe.qc_Vrange) if is_ph else (probe.a1_range, probe.a2_range, probe.Kp_range)
+        probe.close()
+        mesh = np.meshgrid(*[np.linspace(lo, hi, n) for lo, hi in ranges], indexing="ij")
+        plants = np.stack([m.reshape(-1) for m in mesh], axis=1)
+    env = gym_control.make_vec(args.env, len(plants), device=args.device, state_mode=args.state_dtype, seed=args.seed, **overrides)
+    if not hasattr(env, "policy_supported") or not env.policy_supported(policies):
+        env.close()
+        print("policy selection skipped: the policy sweep does not serve this env / actor (policy_supported)")
+        return None
+    res = protocols.policy_sweep(env, policies, plants=plants, setpoints=setpoints, steps=steps, band=band, tail=tail)
+    env.close()
+    sel = protocols.select_policy(res, cost="itae", robust="worst")
+    best, nominal = sel["best_index"], sel["nominal_index"]
+    os.makedirs(cwd, exist_ok=True)
+    path = os.path.join(cwd, "policy_sweep.npz")
+    np.savez(path, summary=res["summary"], plants=plants, setpoints=np.asarray(setpoints, dtype=np.float64), steps=steps, band=band,
+             tail=tail, cost_name="itae", metric_names=np.asarray(protocols.METRIC_NAMES), best_index=best, nominal_index=nominal,
+             snapshot_steps=np.asarray([s["step"] for s in snaps], dtype=np.int64),
+             snapshot_returns=np.asarray([s["r_avg"] for s in snaps], dtype=np.float64),
+             **{k: np.asarray(sel[k]) for k in ("cost", "mean_cost", "worst_cost", "worst_plant", "settled", "fit", "order")})
+    torch.save(snaps[best]["state_dict"], os.path.join(cwd, "actor_robust.pth"))
+    print(f"policy sweep: {len(snaps)} snapshots x {len(plants)} plants -> {path}")
+    for who, j in (("robust  (worst-plant ITAE)", best), ("nominal (plant-mean ITAE) ", nominal)):
+        print(f"  {who}: snapshot {j} of step {snaps[j]['step']}, worst-plant ITAE {sel['worst_cost'][j]:.6g}, mean ITAE "
+              f"{sel['mean_cost'][j]:.6g}, {int(sel['settled'][j])} of {len(plants)} plants settled")
     return path
 
 
@@ -652,6 +715,8 @@ def main(argv=None):
             actuator(args, agent, kargs.cwd)
         if args.bode:
             bode(args, agent, kargs.cwd)
+        if args.select_policy:
+            select_policy(args, getattr(kargs, "evaluator", None), kargs.cwd)
     return agent
 
 

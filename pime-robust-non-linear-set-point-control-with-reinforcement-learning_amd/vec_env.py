@@ -862,6 +862,58 @@ class VecControlEnv:
         return self._row_grid_sweep("pime_actuator_sweep", native.METRIC_ROWS + native.ACT_ROWS, packed_actor, priorK, at, (), n_steps,
                                     setpoints, seg_len, band, tail, want_pairs, want_trace, commands=True)
 
+    # -- policy sweep (many actors, each with its own prior gain, over the lanes' plants) ----------------------------------
+    def policy_supported(self, policies):
+        """Does `policy_sweep` serve this env with this `ops.PackedPolicies` stack?  (pime_policy_sweep_supported: the classes of
+        `margin_sweep` WITH a policy -- pH and the Integrator tank, float64 or mixed state, in-kernel draws, actor widths 64 / 128;
+        the prior controller alone is `prior_sweep`.)"""
+        if self.draws.injects or policies is None or len(policies) < 1:
+            return False
+        if policies.kind not in _EVAL_KINDS or policies.D != self.obs_dim or policies.packed.device != self.obs.device:
+            return False
+        return bool(self._lib.pime_policy_sweep_supported(self._h, _EVAL_KINDS[policies.kind], int(policies.md)))
+
+    def policy_sweep(self, policies, n_steps, setpoints=None, seg_len=0, band=0.05, tail=10, want_pairs=False, want_trace=False):
+        """A grid of POLICIES over every lane's plant in ONE call (pime_policy_sweep, csrc/policy_sweep.hip): every (policy row, lane)
+        pair runs the loop of `rollout_eval_metrics` from the lane state as it stands under row p's packed actor and row p's prior
+        gain -- policies: an `ops.PackedPolicies` stack of P actors of one class.  Row p is bit for bit what `rollout_eval_metrics`
+        with that actor and gain writes from the same lane state, and every policy meets the same process noise (it is keyed on the
+        lane).  Returns summary float64 [P, n_segments, 8, 5] -- per policy, segment and metric row (native.METRIC_NAMES) the stats
+        native.SWEEP_STATS over the lanes, exactly as `prior_sweep` -- or, with `want_pairs` and / or `want_trace`, a dict with
+        "summary", "pairs" float64 [n_segments, 8, P, N] and "actions", "outputs" float64 [n_steps, P, N] (the action and the
+        controlled output after each step).  native.PimeError for a stack `policy_supported` refuses (injected draws among them).
+        Nothing is uploaded or read back, so a capture works.  The env itself is read, never advanced (definitions in
+        include/pime_hip.h)."""
+        fn = "pime_policy_sweep"
+        if self.draws.injects:
+            raise native.PimeError(f"{fn}: injected draws are not served (in-kernel Philox draws only)")
+        if policies is None or len(policies) < 1:
+            raise native.PimeError(f"{fn}: P = {0 if policies is None else len(policies)} (>= 1)")
+        if policies.kind not in _EVAL_KINDS or policies.D != self.obs_dim:
+            raise native.PimeError(f"{fn}: a stack of kind {policies.kind!r} on {policies.D} observation columns is not served on "
+                                   f"this env ({self.obs_dim} columns)")
+        P, n_steps, seg_len = len(policies), int(n_steps), int(seg_len)
+        ws_bytes = int(self._lib.pime_policy_sweep_workspace_bytes(self._h, P, n_steps, seg_len))
+        if ws_bytes < 0:
+            raise native.PimeError(f"{fn}_workspace_bytes: {native.last_error()}")
+        N = self.num_envs
+        sp, sp_ptr, n_sp, n_seg = self._schedule(setpoints, n_steps, seg_len)
+        images, gains = policies.packed, policies.K
+        summary = torch.empty((P, n_seg, native.METRIC_ROWS, len(native.SWEEP_STATS)), dtype=torch.float64, device=self.device)
+        pairs = torch.empty((n_seg, native.METRIC_ROWS, P, N), dtype=torch.float64, device=self.device) if want_pairs else None
+        actions = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        outputs = torch.empty((max(n_steps, 0), P, N), dtype=torch.float64, device=self.device) if want_trace else None
+        # (the workspace lives for this call only and comes from torch's allocator: see prior_sweep)
+        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=self.device)
+        native.check(self._lib.pime_policy_sweep(
+            self._h, _EVAL_KINDS[policies.kind], int(policies.md), native.ptr(images), int(policies.stride), native.ptr(gains), P, n_steps,
+            seg_len, sp_ptr, n_sp, float(band), int(tail), native.ptr(pairs), native.ptr(summary), native.ptr(actions), native.ptr(outputs),
+            native.ptr(workspace), self._stream()), fn)
+        del workspace
+        if not (want_pairs or want_trace):
+            return summary
+        return {"summary": summary, "pairs": pairs, "actions": actions, "outputs": outputs}
+
     # -- state access (float64 numpy on the host; synchronous) -------------------------------------------------
     def get_field(self, name):
         out = np.empty(self.num_envs, dtype=np.float64)
