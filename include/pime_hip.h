@@ -201,17 +201,19 @@ int pime_gae_scan(const float* reward, const float* mask, const float* value, in
  *   kind PIME_MLP_PLAIN_ACTOR    replaces ActorResidualPPO / ActorPPO mean, net_residual.py:19-22,45-48
  *                                (same shape, Tanh); params[8] as above
  *   kind PIME_MLP_MODULAR_ACTOR  replaces ActorResidualIntegratorModularPPO mean, net_residual.py:153-160,172-176
+ *                                params[12] = other_net.0 W,b ; other_net.2 W,b ; integrator_net.0 W,b ;
+ *                                integrator_net.2 W,b ; net.0 W,b ; net.2 W,b ; Di = integrator_dim (trailing
+ *                                columns of x), 1 <= Di < D.  The other kinds ignore Di.
  *   kind PIME_MLP_SAC_ACTOR      replaces ActorSAC's net_state + net_a_avg / net_a_std, elegantrl/net.py:197-205 (width 64 / 128): params =
  *                                ten tensors in module order (net_state.0/2/4, net_a_avg, net_a_std: W, b); ReLU, Hardswish, Hardswish
  *                                body; the image carries both head rows; pime_mlp_forward returns the mean head BEFORE its tanh
- *                                params[12] = other_net.0 W,b ; other_net.2 W,b ; integrator_net.0 W,b ;
- *                                integrator_net.2 W,b ; net.0 W,b ; net.2 W,b ; Di = integrator_dim (trailing
- *                                columns of x)
- * All weights are [dev] float32 in nn.Linear layout ([out, in] row-major).  D <= 32.  Widths: 64 and 128 (every kind: the
- * whole net stays in the 160 KB LDS of a persistent workgroup, csrc/mlp_mfma.hip) and 256 (every kind -- the width
- * run_watertank_changing.sh trains: ResidualPPO on the 30-float Stacking10 observation :20-27, ResidualIntegratorModularPPO on the
- * Integrator observation :11-18 -- on 16-sample tiles of v_mfma_f32_16x16x4_f32 with the weight images streamed through LDS in
- * k-slices, csrc/mlp16.hip; the modular actor's md -> md/2 tower layers are rectangular chain layers there).
+ * All weights are [dev] float32 in nn.Linear layout ([out, in] row-major).  1 <= D <= 32, M >= 1.  Widths: 64 and 128 (every kind: the
+ * whole net stays in the 160 KB LDS of a persistent workgroup, csrc/mlp_mfma.hip) and 256 (every kind but PIME_MLP_SAC_ACTOR, which is
+ * refused there -- the width run_watertank_changing.sh trains: ResidualPPO on the 30-float Stacking10 observation :20-27,
+ * ResidualIntegratorModularPPO on the Integrator observation :11-18 -- on 16-sample tiles of v_mfma_f32_16x16x4_f32 with the weight images streamed through LDS in
+ * k-slices, csrc/mlp16.hip; the modular actor's md -> md/2 tower layers are rectangular chain layers there).  Anything else returns
+ * PIME_ERR_ARG (pime_mlp_packed_floats: 0) with a message and launches nothing; tests/mlp_cases.py: served pins the set.
+ * A NaN in a row of x gives a NaN in that row of out (the ReLU kinds included) and touches no other row.
  * out [dev] float32[M] is the scalar head (value, or pre-tanh action mean without noise and prior term). */
 enum pime_mlp_kind { PIME_MLP_CRITIC = 0, PIME_MLP_PLAIN_ACTOR = 1, PIME_MLP_MODULAR_ACTOR = 2, PIME_MLP_SAC_ACTOR = 3 };
 /* floats in the packed image (0 and an error message if the shape is unsupported) */

@@ -124,6 +124,7 @@ __global__ void pack16_kernel(PackArgs a, float* __restrict__ fwd, float* __rest
 template <int ACT>
 __device__ __forceinline__ float act16(float v) {
     if constexpr (ACT == 0) return v > 0.f ? v : 0.f;
+    else if constexpr (ACT == kActReluNan) return !(v <= 0.f) ? v : 0.f;   // (the forward-only kernel: mlp_device.hpp)
     else if constexpr (ACT == 1) return fast_tanh(v);
     else return v;
 }
@@ -1145,11 +1146,12 @@ __global__ __launch_bounds__(k16Threads, T <= 8 ? 2 : 1) void mlp16_forward_kern
         float xr[8];
         gather_x16(x + (size_t)(m < M ? m : M - 1) * D, D, L.KS0, g, xr);
         f32x4 h1[T], h2[T];
-        first16<T, ACT>(lds + S.w0, lds + S.b0, L.KS0, lane, xr, h1);
+        constexpr int A = forward_act(ACT);   // ReLU in the form that keeps a NaN row a NaN (mlp_device.hpp)
+        first16<T, A>(lds + S.w0, lds + S.b0, L.KS0, lane, xr, h1);
         PIME_NO_HOIST();
-        layer16<T, ACT, true>(img + L.w1, lds + S.b1, lds + S.region, lane, tid, h1, h2);
+        layer16<T, A, true>(img + L.w1, lds + S.b1, lds + S.region, lane, tid, h1, h2);
         PIME_NO_HOIST();
-        layer16<T, ACT, true>(img + L.w2, lds + S.b2, lds + S.region, lane, tid, h2, h1);
+        layer16<T, A, true>(img + L.w2, lds + S.b2, lds + S.region, lane, tid, h2, h1);
         const float y = head16<T>(lds + S.w3, lds[S.b3], lane, h1);
         if (g == 0 && m < M) out[m] = y;
     }
@@ -2186,6 +2188,7 @@ int grid16(int kind, int B, int md, int D, int Di) {
 template <int T, int ACT>
 static int launch_fwd16(const float* x, int M, int D, const float* img, float* out, hipStream_t s) {
     const size_t lds_bytes = sizeof(float) * (size_t)lds16<T>(D, false).total;
+    PIME_REQUIRE(lds_bytes <= 160 * 1024, "16-tile MLP forward needs %zu B of LDS", lds_bytes);
     static LdsLimit lds_limit;  // per instantiation
     PIME_RAISE_LDS(lds_limit, (mlp16_forward_kernel<T, ACT>), 160 * 1024);
     const int ngroups = (M + k16Group - 1) / k16Group;
@@ -2201,6 +2204,7 @@ int launch_forward16(int kind, const float* x, int M, int D, int Di, int md, con
     if (kind == MLP_MODULAR_ACTOR) {
         PIME_REQUIRE(T == 16, "the 16-tile modular actor serves width 256, got %d", md);
         const size_t lds_bytes = sizeof(float) * (size_t)lds16m<16>(D, Di, false).total;
+        PIME_REQUIRE(lds_bytes <= 160 * 1024, "16-tile modular-actor forward needs %zu B of LDS", lds_bytes);
         static LdsLimit lds_limit;
         PIME_RAISE_LDS(lds_limit, (mlp16m_forward_kernel<16>), 160 * 1024);
         const int ngroups = (M + k16Group - 1) / k16Group;

@@ -182,6 +182,14 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);   // (explicit fma: the library is built with -ffp-contract=off)
 }
 
+// nn.ReLU hands a NaN on; `v > 0.f ? v : 0.f` compiles to v_max_f32, which returns the operand that is a number, so a NaN observation
+// leaves a ReLU net as a finite value.  The forward-only kernels (pime_mlp_forward: mlp_forward_kernel, mlp16_forward_kernel), whose
+// callers read the result as the net's, use the form that keeps the NaN (v_cmp + v_cndmask; equal bit for bit on every number).  The
+// fused gradient and rollout kernels keep v_max_f32: with the compare form hipcc spills in the PPO gradient kernels (ppo_fused_pair_kernel<4, 2>:
+// 0 -> 256 bytes of scratch per lane) and the benchmark loses 5 % of its rate.
+constexpr int kActReluNan = 4;
+__host__ __device__ constexpr int forward_act(int act) { return act == 0 ? kActReluNan : act; }
+
 typedef float f32x2_t __attribute__((ext_vector_type(2)));   // packed f32 pairs (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32)
 
 template <int ACT>
@@ -189,6 +197,7 @@ __device__ __forceinline__ float activate(float v) {
     if constexpr (ACT == 0) return v > 0.f ? v : 0.f;  // nn.ReLU
     else if constexpr (ACT == 1) return fast_tanh(v);   // nn.Tanh
     else if constexpr (ACT == 3) return v * __builtin_amdgcn_fmed3f(v + 3.0f, 0.f, 6.0f) * (1.0f / 6.0f);   // nn.Hardswish
+    else if constexpr (ACT == kActReluNan) return !(v <= 0.f) ? v : 0.f;
     else return v;                                      // identity (backward chains)
 }
 

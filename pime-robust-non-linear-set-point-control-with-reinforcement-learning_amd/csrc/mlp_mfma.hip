@@ -65,7 +65,8 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_forward_kernel(const float* _
             PIME_NO_HOIST();
             y = layer_head<T>(lds + L.off[8], lds[L.off[9]], lane, n0);
         } else {
-            constexpr int A1 = MlpActs<KIND>::A1, A2 = MlpActs<KIND>::A2;   // (ActorSAC: the mean head, before its tanh)
+            // (ActorSAC: the mean head, before its tanh; ReLU in the form that keeps a NaN row a NaN: mlp_device.hpp)
+            constexpr int A1 = forward_act(MlpActs<KIND>::A1), A2 = forward_act(MlpActs<KIND>::A2);
             f32x16 a0[T], a1[T];
             layer_first<T, 2>(lds + L.off[0], xrow, D, h, a0);
             PIME_NO_HOIST();
