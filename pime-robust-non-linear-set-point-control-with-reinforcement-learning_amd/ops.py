@@ -315,6 +315,7 @@ class FusedPPOGrad:
     @staticmethod
     def supported(act, cri):
         try:
+            widths = []
             for m in (act, cri):
                 kind = getattr(m, "packed_kind", None)
                 if kind is None or getattr(m, "action_dim", 1) != 1:
@@ -323,6 +324,13 @@ class FusedPPOGrad:
                 md = sd[_PARAM_ORDER[kind][0] + ".weight"].shape[0]
                 if not PackedMLP.supported(kind, m.state_dim, getattr(m, "integrator_dim", 0), md):
                     return False
+                widths.append(md)
+            # the forward image says nothing about the gradient kernels: ask what pime_ppo_minibatch_grad dispatches on (it refuses
+            # a net whose kernel's LDS map does not fit -- under PIME_GRAD_BF16X3=1 a modular actor of width 256 with a plant tower
+            # of 29 floats or more), so that the caller hears "no fused kernel" here and not from inside the first launch
+            if native.lib().pime_ppo_route(_KINDS[act.packed_kind], act.state_dim, getattr(act, "integrator_dim", 0), widths[0],
+                                           widths[1], (C.c_int32 * 3)()) != 0:
+                return False
             return next(cri.parameters()).is_cuda
         except Exception:
             return False

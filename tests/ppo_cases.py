@@ -51,6 +51,8 @@ merged map lacks; D = 8 has no padded rows), the 16-tile family (plain nets) or 
 width 64 the pair kernel serves every D <= 32; width 256 is always the 16-tile family."""
 import collections
 import functools
+import os
+import re
 
 import numpy as np
 
@@ -88,10 +90,44 @@ def net_family(kind, width, D, forced16=False):
     return "split" if kind == "modular" else "16tile"
 
 
-def expected_route(kind, D, Di, aw, cw, forced16=False):
-    """(actor's family, critic's family, launch form "pair" | "dual" | "single")."""
+# PIME_GRAD_BF16X3=1 (read once per process, like PIME_MLP16): the nets of the 16-tile family at widths 128 / 256 run the
+# B3 = true kernels (b3_grad of csrc/mlp16.hip = the variable && width 128 / 256 && family16_grad).  One shape then has no kernel
+# at all (ppo16_fits): ppo16m_kernel<16, true> asks for lds16m<16>(D, Di, true, true).total floats of LDS --
+#   the region, max over the streamed layers' slice buffers and the dW rounds: Dw16SlicedB3<16>::FLOATS =
+#     3 planes x 64 rows x (16 + 4 tiles) x 32 B = 122 880 B (the f32 kernel's own region is smaller, which is why it fits);
+#   the two first-layer images, 16 tiles x 64 lanes x 4 floats = 4 096 B per k-step of 4 inputs: ceil((D - Di) / 4) + ceil(Di / 4);
+#   biases, head and the waves' sums: 256 + 128 + 256 + 128 + 256 + 256 + 4 + 48 floats = 5 328 B
+# -- against 160 KB = 163 840 B: 35 632 B are left for the first layer, 8 k-steps.  Di <= 3 takes one, so the plant tower has 7:
+# D - Di <= 28 is served, a tower of 29 floats or more is not.
+B3_MAX_TOWER_256 = (163840 - 122880 - 5328) // 4096 * 4 - 4
+assert B3_MAX_TOWER_256 == 28
+
+
+def b3_process():
+    """Does this process run the variant?  (The library's own reading of the variable: set, and atoi of it not 0.)"""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("PIME_GRAD_BF16X3", ""))
+    return bool(m) and int(m.group()) != 0
+
+
+def forced16_process():
+    return os.environ.get("PIME_MLP16") is not None
+
+
+def b3_net(kind, width, D, Di=0, forced16=False):
+    """Under PIME_GRAD_BF16X3=1: does this net run a B3 = true kernel (and carry bf16 planes behind its transposed image)?  Every net
+    of width 256; at width 128 the nets of the 16-tile family -- plain actors and critics on 14 floats or more, and under PIME_MLP16=1
+    everything, the modular actor included; never at width 64, never a net of the LDS-resident or the split family.  (True as well
+    for the one shape the variant does not serve: its image is sized before the launch refuses.)"""
+    return width in (128, 256) and net_family(kind, width, D, forced16) == "16tile"
+
+
+def expected_route(kind, D, Di, aw, cw, forced16=False, b3=False):
+    """(actor's family, critic's family, launch form "pair" | "dual" | "single").  b3: under PIME_GRAD_BF16X3=1, where the actor's
+    family is "none" for a modular actor of width 256 with a plant tower above B3_MAX_TOWER_256 (pime_ppo_route refuses it)."""
     fa = net_family("modular" if kind == "modular" else "plain", aw, D, forced16)
     fc = net_family("critic", cw, D, forced16)
+    if b3 and kind == "modular" and aw == 256 and D - Di > B3_MAX_TOWER_256:
+        fa = "none"
     launch = "single"
     if fa == fc == "lds" and aw == cw:
         launch = "pair" if (aw == 64 or D <= 4 or D == 8) else "dual"
@@ -105,8 +141,12 @@ def library_route(kind, D, Di, aw, cw):
     import pime_amd.native as nt
     r = (ctypes.c_int32 * 3)()
     k = nt.MLP_MODULAR_ACTOR if kind == "modular" else nt.MLP_PLAIN_ACTOR
-    nt.check(nt.lib().pime_ppo_route(k, D, Di if kind == "modular" else 0, aw, cw, r), "pime_ppo_route")
-    return ("16tile", "lds", "split")[r[0]], ("16tile", "lds", "split")[r[1]], ("single", "dual", "pair")[r[2]]
+    rc = nt.lib().pime_ppo_route(k, D, Di if kind == "modular" else 0, aw, cw, r)
+    families = ("16tile", "lds", "split", "none")
+    if rc != 0 and "none" not in (families[r[0]], families[r[1]]):   # a net without a kernel is an answer (the query fills the
+        nt.check(rc, "pime_ppo_route")                                 # triple, then refuses); anything else is an error
+    assert (rc != 0) == ("none" in (families[r[0]], families[r[1]]))
+    return families[r[0]], families[r[1]], ("single", "dual", "pair")[r[2]]
 
 
 def first_layer_class(family, kind, D):
@@ -134,7 +174,10 @@ def spec(kind, D, Di, aw, B, cw=None, vet=True):
 
 def spec_id(s):
     tag = f"{s.kind}-{s.aw}" + (f"+{s.cw}" if s.cw != s.aw else "") + f"-D{s.D}" + (f"i{s.Di}" if s.kind == "modular" else "")
-    return f"{tag}-B{s.B}-{s.route[2]}" + ("" if s.vet else "-unvetted")
+    return f"{tag}-B{'cap' if s.B == CAP_B else s.B}-{s.route[2]}" + ("" if s.vet else "-unvetted")
+
+
+CAP_B = 0   # placeholder of the variant's lists: "grid x 64 + 1", resolved where the grid can be read (resolve_cap)
 
 
 def shape_cases():
@@ -218,6 +261,133 @@ def gradient_specs():
         if s not in seen:
             seen.append(s)
     return seen
+
+
+# ------------------------------------------------------------------------------------------- the bf16x3 variant's lists
+# Run in child processes under PIME_GRAD_BF16X3=1 (tests/test_gpu_ppo_sweep.py part f, tests/test_gpu_ppo_chain.py).  A spec's
+# route is the variant's (expected_route(..., b3=True)); where a shape, batch and route are those of an f32 list the spec IS that
+# list's spec, and the case -- seeded from the shape and the batch alone -- is the same one.
+def b3_spec(kind, D, Di, aw, B, cw=None, forced16=False, vet=True):
+    s = spec(kind, D, Di, aw, B, cw, vet)
+    return s._replace(route=expected_route(s.kind, s.D, s.Di, s.aw, s.cw, forced16, b3=True))
+
+
+def b3_nets(s, forced16=False):
+    """(the actor runs a B3 kernel, the critic does)."""
+    return b3_net(okind(s.kind), s.aw, s.D, s.Di, forced16), b3_net("critic", s.cw, s.D, 0, forced16)
+
+
+def b3_kernel_class(s, forced16=False):
+    """kernel_class under the variant, and which of the two nets is B3."""
+    k = okind(s.kind)
+    route = expected_route(s.kind, s.D, s.Di, s.aw, s.cw, forced16, b3=True)
+    return (route, s.aw, s.cw, k, first_layer_class(route[0], k, s.D), first_layer_class(route[1], "critic", s.D),
+            b3_nets(s, forced16))
+
+
+def b3_shape_cases(width=None):
+    """The variable alone, B = 37.  Width 256: plain D 1..32 (one first-layer column block up to 16 floats, two above), modular
+    Di 1 for every D the variant serves, Di 2 and 3, and (31, 3): a plant tower of 28 floats, the last one served.  Width 128:
+    plain D 14..32 (below, the LDS-resident kernels serve both nets and nothing is B3) and the modular actor on 14 and 20 floats:
+    the split pipeline (f32, float atomics) next to a B3 critic."""
+    out = [b3_spec("plain", D, 0, 256, 37) for D in range(1, MAX_D + 1)]
+    out += [b3_spec("modular", D, 1, 256, 37) for D in range(2, MAX_D + 1) if D - 1 <= B3_MAX_TOWER_256]
+    out += [b3_spec("modular", D, Di, 256, 37) for D, Di in ((4, 2), (7, 3), (31, 3))]
+    out += [b3_spec("plain", D, 0, 128, 37) for D in range(14, MAX_D + 1)]
+    out += [b3_spec("modular", D, 1, 128, 37) for D in (14, 20)]
+    return [s for s in out if width in (None, s.aw)]
+
+
+def b3_regime_cases():
+    """The first member of every B3 kernel class of the shape list at the 16-tile family's batch regimes, and per (route, width)
+    one batch of grid x 64 + 1 -- carried as CAP_B: the variant's LDS footprint decides the grid, so the batch is sized where
+    pime_ppo_grid16 can be asked under the variable (resolve_cap)."""
+    seen, out, capped = {}, [], set()
+    for s in b3_shape_cases():
+        seen.setdefault(b3_kernel_class(s), s)
+    for cls, s in seen.items():
+        out += [s._replace(B=B) for B in REGIME_B["16tile"]]
+        if (cls[0], s.aw) not in capped:
+            capped.add((cls[0], s.aw))
+            out.append(s._replace(B=CAP_B))
+    return out
+
+
+def b3_mixed_cases():
+    """A B3 actor next to an f32 LDS-resident critic, at width 256 and (a critic of width 64 has no B3 kernel) at width 128; both B3
+    at different tile counts; an LDS-resident actor next to a B3 critic."""
+    out = []
+    for B in (37, 257):
+        out += [b3_spec("plain", 9, 0, 256, B, cw=128), b3_spec("plain", 20, 0, 256, B, cw=128), b3_spec("modular", 5, 2, 128, B, cw=256),
+                b3_spec("plain", 20, 0, 128, B, cw=64)]
+    return out
+
+
+def b3_forced16_cases():
+    """Both variables, width 128 (width 64 has no B3 kernel): ppo16_kernel<8, ., true> on narrow observations and
+    ppo16m_kernel<8, true> -- Di 1 and 3, and on (20, 1) its two-tile first layer (a plant tower of 19 floats) --, B 2 .. 65; the
+    modular actor once next to a critic of width 64 (the f32 16-tile kernel), and its cap batch."""
+    shapes = (("plain", 3, 0), ("plain", 20, 0), ("modular", 4, 1), ("modular", 7, 3), ("modular", 20, 1))
+    out = [b3_spec(k, D, Di, 128, B, forced16=True) for k, D, Di in shapes for B in (2, 15, 17, 37, 63, 65)]
+    out.append(b3_spec("modular", 4, 1, 128, 37, cw=64, forced16=True))   # ppo16m_kernel<8, true> next to an f32 critic (width 64)
+    return out + [b3_spec("modular", 4, 1, 128, CAP_B, forced16=True)]
+
+
+def b3_per_route_shapes(forced16=False):
+    """One shape per (route, widths, actor kind, which nets are B3): the first of the lists of the process."""
+    seen = {}
+    for s in (b3_forced16_cases() if forced16 else b3_shape_cases() + b3_mixed_cases()):
+        if s.B != CAP_B:
+            seen.setdefault((s.route, s.aw, s.cw, okind(s.kind), b3_nets(s, forced16)), s)
+    return list(seen.values())
+
+
+def b3_property_cases(forced16=False):
+    return [s._replace(B=B) for s in b3_per_route_shapes(forced16) for B in (293, 100)]
+
+
+B3_LISTS = {   # name -> (forced16, list): what the children of the GPU tests are told to run
+    "shapes256": (False, lambda: b3_shape_cases(256)),
+    "shapes128": (False, lambda: b3_shape_cases(128)),
+    "regimes": (False, b3_regime_cases),
+    "mixed": (False, b3_mixed_cases),
+    "forced16": (True, b3_forced16_cases),
+}
+
+
+def b3_gradient_specs():
+    """[(spec, forced16)]: every vetted spec of the variant's lists that gradient_specs() does not already hold (the cap
+    placeholders are resolved and vetted where the grid can be read)."""
+    have, out = set(gradient_specs()), []
+    for forced16, cases in ((False, b3_shape_cases() + b3_regime_cases() + b3_mixed_cases() + b3_property_cases()),
+                            (True, b3_forced16_cases() + b3_property_cases(True))):
+        for s in cases:
+            if s.B != CAP_B and s not in have:
+                have.add(s)
+                out.append((s, forced16))
+    return out
+
+
+def cap_grids(s, forced16=False):
+    """{net: workgroups pime_ppo_grid16 answers for an unbounded batch} of the spec's nets on the 16-tile family, in THIS
+    process (host-only query; it follows the process's variables)."""
+    import pime_amd.native as nt
+    L = nt.lib()
+    out = {}
+    if s.route[0] == "16tile":
+        out["actor"] = L.pime_ppo_grid16(nt.MLP_MODULAR_ACTOR if s.kind == "modular" else nt.MLP_PLAIN_ACTOR, 1 << 30, s.aw, s.D, s.Di)
+    if s.route[1] == "16tile":
+        out["critic"] = L.pime_ppo_grid16(nt.MLP_CRITIC, 1 << 30, s.cw, s.D, 0)
+    assert out and min(out.values()) >= 1
+    return out
+
+
+def resolve_cap(s, forced16=False):
+    """(the spec at B = largest grid x 64 + 1, the grids): every 16-tile net's workgroups take a second group."""
+    grids = cap_grids(s, forced16)
+    B = max(grids.values()) * 64 + 1
+    assert all((B + 63) // 64 > g for g in grids.values()), "no workgroup of the 16-tile kernel takes a second group"
+    return s._replace(B=B), grids
 
 
 # --------------------------------------------------------------------------------------------------------------- generator

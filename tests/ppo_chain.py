@@ -85,6 +85,12 @@ def chain_specs():
     return out
 
 
+def b3_chain_specs(forced16=False):
+    """Under PIME_GRAD_BF16X3=1 (child processes; forced16: with PIME_MLP16=1): ppo_cases.b3_per_route_shapes at B = 293 -- one spec
+    per (route, widths, actor kind, which nets run a B3 kernel and re-split their bf16 planes after every step)."""
+    return [s._replace(B=B) for s in PC.b3_per_route_shapes(forced16)]
+
+
 def deterministic(s):
     """False on the split pipeline, whose gradient sums are float atomics (tests/test_gpu_mlp16.py)."""
     return s.route[0] != "split"

@@ -154,3 +154,71 @@ def test_bf16_planes_hold_the_weights_exactly_in_the_documented_layout():
     env = dict(os.environ, PIME_ROOT=ROOT, PIME_MLP16="1", PIME_GRAD_BF16X3="1")
     r = subprocess.run([sys.executable, "-c", _PLANES_CHILD], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "PLANES_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+_MODULAR_PLANES_CHILD = r"""
+import os, sys
+sys.path.insert(0, os.environ["PIME_ROOT"]); sys.path.insert(0, os.path.join(os.environ["PIME_ROOT"], "tests"))
+import numpy as np, torch
+import ppo_cases as PC
+import test_gpu_ppo_sweep as SW
+
+def unpack(planes, base, n_out, n_k):
+    # One layer's image, pack16_b3_layer of csrc/mlp16.hip: [k-step ks][output tile to][plane][lane (g, i)][e], bf16, holding
+    # V[16 to + i][32 ks + 16 (e >> 2) + 4 g + (e & 3)] of the [n_out x n_k] matrix V the layer multiplies by.  base: in floats.
+    TO, KS = n_out // 16, n_k // 32
+    n = KS * TO * 3 * 512
+    img = (planes[2 * base:2 * base + n].astype(np.uint32) << 16).view(np.float32).reshape(KS, TO, 3, 4, 16, 2, 4).astype(np.float64)
+    order = lambda a: a.transpose(1, 3, 0, 4, 2, 5).reshape(n_out, n_k)   # [ks][to][g][i][eh][el] -> [to][i] x [ks][eh][g][el]
+    return order(img.sum(axis=2)), order(img[:, :, 0]), base + n // 2
+
+def check(name, planes, base, V):
+    rec, hi, end = unpack(planes, base, *V.shape)
+    assert np.array_equal(rec.astype(np.float32), V), (name, float(np.abs(rec - V).max()))   # hi + mid + lo: exact
+    assert np.abs(hi - V).max() <= 2.0 ** -8 * np.abs(V).max(), name                          # the leading piece: bf16 precision
+    assert np.abs(V).max() > 0
+    return end
+
+forced16 = PC.forced16_process()
+assert PC.b3_process()
+for kind, D, Di, md in ((("modular", 7, 3, 256), ("modular", 20, 1, 128)) if forced16 else (("modular", 4, 1, 256), ("modular", 20, 1, 128))):
+    s = PC.b3_spec(kind, D, Di, md, 37, forced16=forced16, vet=False)
+    act, cri, f = SW._fused(PC.build(s))
+    torch.cuda.synchronize()
+    hd = md // 2
+    for net, mod, role, on in zip(f.nets, (act, cri), ("modular", "critic"), PC.b3_nets(s, forced16)):
+        planes = net["img_bwd"][net["n_bwd_f32"]:].cpu().numpy().view(np.uint16)
+        assert (planes.size > 0) == on, (md, role)
+        if not on:
+            continue   # width 128 without PIME_MLP16: the split-pipeline actor carries no planes, the critic next to it does
+        sd = {k: v.detach().cpu().numpy() for k, v in mod.named_parameters()}
+        if role == "modular":
+            # layout_b3_16m: w1o, w1i (the towers' second layers, [md / 2 x md]: parameters 2 and 6 of the pack order), wn, wnt
+            # (net.0, [md x md]: parameter 8, and its transpose), w1ot, w1it (the towers' transposes, [md x md / 2])
+            Wo, Wi, Wn = sd["other_net.2.weight"], sd["integrator_net.2.weight"], sd["net.0.weight"]
+            assert Wo.shape == Wi.shape == (hd, md) and Wn.shape == (md, md)
+            layers = (("w1o", Wo), ("w1i", Wi), ("wn", Wn), ("wnt", Wn.T), ("w1ot", Wo.T), ("w1it", Wi.T))
+        else:   # layout_b3_16: w1, w2, w2t, w1t
+            W1, W2 = sd["net.2.weight"], sd["net.4.weight"]
+            layers = (("w1", W1), ("w2", W2), ("w2t", W2.T), ("w1t", W1.T))
+        base = 0
+        for name, V in layers:
+            base = check((md, role, name), planes, base, np.ascontiguousarray(V))
+        assert 2 * base == planes.size, (md, role, base, planes.size)
+print("PLANES_OK")
+"""
+
+
+@pytest.mark.parametrize("forced16", (True, False), ids=("mlp16", "alone"))
+def test_bf16_planes_of_the_modular_actor_and_of_a_lone_critic(forced16):
+    """layout_b3_16m unpacked on the host -- six images, the towers' second layers and their transposes half as wide or half as
+    deep as net.0's -- at width 256 (Di 3 and Di 1) and, under PIME_MLP16=1, at width 128; hi + mid + lo is the f32 weight or its
+    transpose exactly, hi alone within 2^-8 of the largest weight.  The critic (plain layout, its own module) at width 256 next
+    to them, and at width 128 on 20 floats WITHOUT PIME_MLP16: the one configuration in which the critic alone carries planes
+    (its actor runs the split pipeline)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("PIME_MLP16", "PIME_GRAD_BF16X3")}
+    env.update(PIME_ROOT=ROOT, PIME_GRAD_BF16X3="1")
+    if forced16:
+        env["PIME_MLP16"] = "1"
+    r = subprocess.run([sys.executable, "-c", _MODULAR_PLANES_CHILD], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "PLANES_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

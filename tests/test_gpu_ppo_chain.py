@@ -17,6 +17,11 @@ in every launch form -- held bit for bit to a step-by-step loop whose every step
      packed images equal to the twin's (loss sums: see below), in each launch form (index table: eager / probe / capture / per-step graph,
      then the whole-update graph; index hook: two graphs; launch timer: separate Adam; no graphs; no whole-update graph), and
      when the third update reads a second buffer with the same contents (other data pointers: new graphs, the same end state).
+  e. Parts a. and b. under the bf16x3 variant (PIME_GRAD_BF16X3=1, alone and with PIME_MLP16=1; child processes) over
+     ppo_chain.b3_chain_specs(): every step form re-splits the bf16 planes behind the transposed image (refresh_b3 of csrc/abi.hip:
+     the fused step, pime_adam_step_images, pime_adam_step_dp) or re-packs them; a form that left them stale would take the
+     streamed layers at the previous weights and the first layer at the new ones, which the gradient of a fresh object at the
+     chain's own pre-step weights -- bit-equal on every B3 net -- shows at the step after.
   d. PIME_PPO_CHAIN_REPORT=<path> writes the largest used share of every bound as JSON (a record -- profiles/ppo_chain_gpu.txt --,
      not a threshold).
 
@@ -29,6 +34,8 @@ from.  Against float64 the loss sums are held per step by check_chain."""
 import functools
 import json
 import os
+import subprocess
+import sys
 import types
 
 import numpy as np
@@ -80,6 +87,13 @@ def _images(fused):
     return [(_np(n["img_fwd"]), _np(n["img_bwd"])) for n in fused.nets]
 
 
+def _assert_planes(s, *objects):
+    """Under the bf16x3 variant the transposed images that the recorder compares hold the bf16 planes of the B3 nets."""
+    want = PC.b3_nets(s, PC.forced16_process()) if PC.b3_process() else (False, False)
+    for fused in objects:
+        assert tuple(n["img_bwd"].numel() > n["n_bwd_f32"] for n in fused.nets) == want, f"{PC.spec_id(s)}: bf16 planes"
+
+
 def _load_flat(act, cri, flat):
     """Writes a flat parameter vector into the trainable parameters of (act, cri), in the flat order."""
     o = 0
@@ -108,6 +122,8 @@ class Chain:
         self.lay = _layout_of(case, fused.act, fused.cri)
         assert fused.critic_offset == CH.n_actor(self.lay)
         self.twin = ops.FusedPPOGrad(*SW._modules(case), batch)
+        if case.table is not None:
+            _assert_planes(case.spec, fused, self.twin)
         self.fresh_modules = SW._modules(case)
         imap = fused.image_map()
         self.image_map = None if imap is None else _np(imap).reshape(-1, 2).astype(np.int64)
@@ -244,6 +260,7 @@ def test_data_parallel_step_form_at_world_1(s):
     fused = ops.FusedPPOGrad(act, cri, s.B)
     opt = fused.make_optimizer(CH.HYPER["lr"])
     twin = ops.FusedPPOGrad(*SW._modules(case), s.B)
+    _assert_planes(s, fused, twin)
     n_act, h = fused.critic_offset, CH.HYPER
     tables, _ = SW._tables(case)
     tab = torch.from_numpy(table).to(DEV)
@@ -301,6 +318,57 @@ def test_defer_critic_scale_next_to_a_split_actor(s):
     np.testing.assert_allclose(_np(fused.dp_moments)[:3], [r.sum(), (r * r).sum(), s.B], rtol=2.0 ** -23)
     want = _np(fused.flat_grad)[n_act:].astype(np.float64) * float(scale)
     np.testing.assert_allclose(_np(plain.flat_grad)[n_act:], want, rtol=2.0 ** -22, atol=0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------- e
+_B3_CHILD = r"""
+import os, sys
+sys.path.insert(0, os.environ["PIME_ROOT"]); sys.path.insert(0, os.path.join(os.environ["PIME_ROOT"], "tests"))
+import test_gpu_ppo_chain as t
+t.b3_child()
+"""
+
+
+def b3_child():
+    """What a child of part e runs: parts a. and b. as they are, over the variant's specs of THIS process."""
+    assert PC.b3_process()
+    ran = []
+    for s in CH.b3_chain_specs(PC.forced16_process()):
+        if CH.deterministic(s):
+            test_chain_of_fused_steps(s)
+            for form in FORMS[1:]:
+                test_chain_in_the_other_step_forms(s, form)
+            test_data_parallel_step_form_at_world_1(s)
+        else:   # the split-pipeline actor (f32, atomics) next to a B3 critic, whose part stays bit-equal (check_chain)
+            test_chain_on_the_split_pipeline(s)
+            test_defer_critic_scale_next_to_a_split_actor(s)
+        ran.append(PC.spec_id(s))
+    print("PPO_CHAIN_B3 " + json.dumps({"used": _USED, "bit_equal": _BIT_EQUAL, "ran": ran, "routes": SW._ROUTES}))
+
+
+def test_chain_under_the_bf16x3_variant():
+    """Two children, one after the other: PIME_GRAD_BF16X3=1 alone (ppo16_kernel<16 | 8, ., true> and ppo16m_kernel<16, true> alone,
+    next to each other at different widths, next to the LDS-resident kernels and next to the split pipeline), then with
+    PIME_MLP16=1 (ppo16_kernel<8, ., true> on 3 floats, ppo16m_kernel<8, true> next to a B3 critic and next to an f32 one).  A child that dies on a signal or runs into its
+    time limit fails the test there; the second is not started."""
+    for forced16 in (False, True):
+        env = {k: v for k, v in os.environ.items() if k not in ("PIME_MLP16", "PIME_GRAD_BF16X3", "PIME_PPO_CHAIN_REPORT",
+                                                                 "PIME_PPO_SWEEP_REPORT")}
+        env.update(PIME_ROOT=SW.ROOT, PIME_GRAD_BF16X3="1")
+        if forced16:
+            env["PIME_MLP16"] = "1"
+        r = subprocess.run([sys.executable, "-c", _B3_CHILD], env=env, capture_output=True, text=True, timeout=300)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("PPO_CHAIN_B3 ")]
+        assert r.returncode == 0 and line, f"child (PIME_MLP16: {forced16}) exited with {r.returncode}\n" + r.stdout[-3000:] + r.stderr[-4000:]
+        rec = json.loads(line[0].split(" ", 1)[1])
+        tag = " (PIME_MLP16)" * forced16 + " (PIME_GRAD_BF16X3)"
+        for k, v in rec["used"].items():
+            _USED[k] = max(_USED.get(k, 0.0), float(v))
+        for k in rec["bit_equal"]:
+            _BIT_EQUAL[k + tag] = True
+        assert rec["ran"] == [PC.spec_id(s) for s in CH.b3_chain_specs(forced16)]
+        want = {"/".join(s.route) + f" {s.aw}+{s.cw}" + tag for s in CH.b3_chain_specs(forced16)}
+        assert set(rec["routes"]) == want and len(want) == (7 if not forced16 else 2)
 
 
 # ----------------------------------------------------------------------------------------------------------------------- c

@@ -9,7 +9,13 @@ branch of the loss populated) -- so "within 3e-4 of the tensor's largest entry" 
   c. actor and critic of different widths: ppo_fused_kernel<T, KIND> as a launch of its own;
   d. per (route, widths): NaN in the workspaces and in every trajectory row the indices do not name; stale slabs of a larger
      launch; frozen parameters (gradients routed to the dump, skipped by the fused Adam, images kept equal to a re-pack);
-  e. widths 64 / 128 through the 16-tile family under PIME_MLP16=1, in a child process.
+  e. widths 64 / 128 through the 16-tile family under PIME_MLP16=1, in a child process;
+  f. the bf16x3 variant (PIME_GRAD_BF16X3=1: ppo16_kernel<8 | 16, ., true>, ppo16m_kernel<8 | 16, true>, pack16_b3_kernel) in child
+     processes, one test per list of ppo_cases.B3_LISTS: the same run_case and the same properties of d., the same bars; per B3
+     kernel class the error of every gradient element pooled and held to the f32 path's pool of the same list (99th percentile
+     at most twice the f32 path's, or 5e-7: the contract of tests/test_gpu_bf16x3.py), since the 3e-4 bar cannot see a lost
+     low-order piece (2^-16 per term); and the one shape the variant does not serve.  The report's key "b3" holds the variant's
+     shares, routes, cap grids and both paths' pools (a record: profiles/ppo_sweep_b3_gpu.txt).
 Every case asserts the route its spec names against pime_ppo_route.  Per case: every gradient tensor, every element, at 3e-4 of
 the oracle tensor's largest entry; critic_scale at rtol 3e-6; the float64 target moments at rtol 1e-12; loss_sums[0, 1, 2, 4] at
 the bars of tests/test_gpu_ppo_fused.py and tests/test_gpu_mlp16.py.  PIME_PPO_SWEEP_REPORT=<path> writes the largest used share
@@ -34,6 +40,10 @@ DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _USED = {}     # bar -> largest used share seen
 _ROUTES = {}   # "actor family/critic family/launch widths" -> cases
+_POOL = {}     # (B3 kernel class, net) -> [every gradient element's error / the tensor's largest entry]: part f
+_POOL_CLASS = [None]   # (class label, (pool the actor, pool the critic)) of the case that run_case is on, set by part f's children
+# part f's record: the variant's own used shares and routes, per list and class both paths' pools, the grids read for the cap batches
+_B3 = {"used_share_of_bar": {}, "routes_hit": {}, "pools": {}, "grids": {}}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -42,7 +52,7 @@ def _report():
     path = os.environ.get("PIME_PPO_SWEEP_REPORT")
     if path:
         with open(path, "w") as fh:
-            json.dump({"used_share_of_bar": _USED, "routes_hit": _ROUTES}, fh, indent=1, sort_keys=True)
+            json.dump({"used_share_of_bar": _USED, "routes_hit": _ROUTES, "b3": _B3}, fh, indent=1, sort_keys=True)
 
 
 def _note(kind, value):
@@ -85,10 +95,22 @@ def _call(fused, tables, idx, scale, **kw):
     torch.cuda.synchronize()
 
 
-def _assert_route(s, forced16=False):
+def _assert_route(s, forced16=None):
+    """The library's route is the spec's and the model's of THIS process (its PIME_MLP16, its PIME_GRAD_BF16X3); per net, the
+    transposed image carries bf16 planes exactly where the model says the net runs a B3 kernel -- launch_ppo16 picks the kernel by
+    the same b3_grad that sizes the image, so no case passes by silently running the f32 kernel."""
+    import pime_amd.native as nt
+    forced16 = PC.forced16_process() if forced16 is None else forced16
+    b3 = PC.b3_process()
     got = PC.library_route(s.kind, s.D, s.Di, s.aw, s.cw)
-    assert got == s.route == PC.expected_route(s.kind, s.D, s.Di, s.aw, s.cw, forced16), f"{PC.spec_id(s)}: the library routes {got}"
-    key = "/".join(got) + f" {s.aw}+{s.cw}" + (" (PIME_MLP16)" if forced16 else "")
+    assert got == s.route == PC.expected_route(s.kind, s.D, s.Di, s.aw, s.cw, forced16, b3), f"{PC.spec_id(s)}: the library routes {got}"
+    L = nt.lib()
+    ka = nt.MLP_MODULAR_ACTOR if s.kind == "modular" else nt.MLP_PLAIN_ACTOR
+    for k, kind, w, di in ((ka, PC.okind(s.kind), s.aw, s.Di), (nt.MLP_CRITIC, "critic", s.cw, 0)):
+        n_bwd, n_f32 = L.pime_ppo_bwd_image_floats(k, s.D, di, w), L.pime_ppo_bwd_image_f32_floats(k, s.D, di, w)
+        assert n_f32 > 0 and (n_bwd > n_f32) == (b3 and PC.b3_net(kind, w, s.D, di, forced16)) and n_bwd >= n_f32, \
+            f"{PC.spec_id(s)}: {kind} of width {w}: image of {n_bwd} floats, {n_f32} of them f32"
+    key = "/".join(got) + f" {s.aw}+{s.cw}" + (" (PIME_MLP16)" if forced16 else "") + (" (PIME_GRAD_BF16X3)" if b3 else "")
     _ROUTES[key] = _ROUTES.get(key, 0) + 1
 
 
@@ -109,6 +131,8 @@ def _check_gradients(case, act, cri, what, only=None):
         big = np.abs(want).max()
         assert big > 0
         err = np.abs(got - want).max() / big
+        if _POOL_CLASS[0] is not None and _POOL_CLASS[0][1][net == "cri"]:
+            _POOL.setdefault((_POOL_CLASS[0][0], net), []).append((np.abs(got - want) / big).astype(np.float32).ravel())
         print(f"ppo sweep {what} {name}: {err:.2e} of the largest entry")
         _note(f"grad {name} (bar 3e-4 of the largest entry)", err / PC.BAR)
         assert err <= PC.BAR, f"{what}: gradient of {name}: {err:.2e} of the largest entry (bar {PC.BAR:.0e})"
@@ -120,6 +144,10 @@ def run_case(case, forced16=False):
     assert s.vet and mid is not None
     _assert_route(s, forced16)
     act, cri, fused = _fused(case)
+    from pime_amd import ops
+    assert ops.FusedPPOGrad.supported(act, cri) is True, f"{PC.spec_id(s)}: served by the library, refused by supported()"
+    planes = PC.b3_nets(s, forced16) if PC.b3_process() else (False, False)
+    assert tuple(n["img_bwd"].numel() > n["n_bwd_f32"] for n in fused.nets) == planes, f"{PC.spec_id(s)}: bf16 planes"
     tables, idx = _tables(case)
     for net in fused.nets:
         net["ws"].fill_(float("nan"))
@@ -310,8 +338,10 @@ def test_frozen_parameters(s):
         got = [(n["img_fwd"].clone(), n["img_bwd"].clone()) for n in fused.nets]
         fused.repack()
         torch.cuda.synchronize()
-        for (gf, gb), n in zip(got, fused.nets):
+        planes = PC.b3_nets(s, PC.forced16_process()) if PC.b3_process() else (False, False)
+        for (gf, gb), n, b3 in zip(got, fused.nets, planes):
             assert torch.equal(gf, n["img_fwd"]) and torch.equal(gb, n["img_bwd"]), f"{freeze}: packed images drifted from the parameters"
+            assert (gb.numel() > n["n_bwd_f32"]) == b3, f"{freeze}: the compared transposed image does not hold the bf16 planes"
 
 
 # ------------------------------------------------------------------------------------------------------------------------ e
@@ -341,3 +371,194 @@ def test_widths_64_and_128_through_the_16_tile_family():
         _ROUTES[k] = _ROUTES.get(k, 0) + v
     assert set(rec["routes_hit"]) == {"16tile/16tile/single 64+64 (PIME_MLP16)", "16tile/16tile/single 128+128 (PIME_MLP16)",
                                       "lds/16tile/single 64+64 (PIME_MLP16)"}
+
+
+# ------------------------------------------------------------------------------------------------------------------------ f
+_B3_CHILD = r"""
+import os, sys
+sys.path.insert(0, os.environ["PIME_ROOT"]); sys.path.insert(0, os.path.join(os.environ["PIME_ROOT"], "tests"))
+import test_gpu_ppo_sweep as t
+t.b3_child(sys.argv[1])
+"""
+
+
+def _class_label(s, forced16):
+    route, aw, cw, kind, fa, fc, on = PC.b3_kernel_class(s, forced16)
+    return "/".join(route) + f" {aw}+{cw} {kind} first layer {fa}/{fc} B3 " + "+".join(n for n, b in zip(("actor", "critic"), on) if b)
+
+
+def _pool_stats():
+    out = {}
+    for (label, net), parts in _POOL.items():
+        d = np.concatenate(parts).astype(np.float64)
+        out[f"{label} | {net}"] = {"n": int(d.size), "p99": float(np.quantile(d, 0.99)), "rms": float(np.sqrt((d * d).mean())),
+                                   "max": float(d.max()), "far": float((d > 2e-6).mean())}
+    return out
+
+
+def b3_child(name):
+    """What a child of part f runs (both switches are read once per process, and the parent set them): a list of
+    ppo_cases.B3_LISTS through run_case -- under the variant, or with the variable unset for the f32 path's pools --, the three
+    properties of d. over the variant's per-route shapes, or the shape the variant does not serve."""
+    forced16, grids = PC.forced16_process(), {}
+    if name == "boundary":
+        _b3_boundary()
+    elif name == "properties":
+        assert PC.b3_process() and not forced16
+        for s in PC.b3_per_route_shapes():
+            for prop in (test_nothing_unwritten_or_unnamed_is_read, test_stale_slabs_of_a_larger_launch_do_not_reach_a_smaller_one,
+                         test_frozen_parameters):
+                prop(s)
+    else:
+        want16, cases = PC.B3_LISTS[name]
+        assert want16 == forced16
+        for s in cases():
+            if s.B == PC.CAP_B:   # grid x 64 + 1, from the grid of THIS process's kernels
+                label = PC.spec_id(s)
+                s, g = PC.resolve_cap(s, forced16)
+                grids[label] = dict(g, B=s.B)
+            _POOL_CLASS[0] = (_class_label(s, forced16), PC.b3_nets(s, forced16))
+            run_case(PC.build(s), forced16)
+        _POOL_CLASS[0] = None
+        if forced16 and PC.b3_process():   # the properties on ppo16_kernel<8, ., true> below 14 floats and ppo16m_kernel<8, true>
+            for s in PC.b3_per_route_shapes(True):
+                for prop in (test_nothing_unwritten_or_unnamed_is_read, test_stale_slabs_of_a_larger_launch_do_not_reach_a_smaller_one,
+                             test_frozen_parameters):
+                    prop(s)
+    print("PPO_SWEEP_B3 " + json.dumps({"used_share_of_bar": _USED, "routes_hit": _ROUTES, "pools": _pool_stats(), "grids": grids}))
+
+
+def _b3_run(name, variant=True, forced16=False, timeout=300):
+    """One child, given only the switches it needs.  A child that dies on a signal or runs into its time limit fails the test there
+    (TimeoutExpired, or the assertion below): the test's remaining children are not started."""
+    env = {k: v for k, v in os.environ.items() if k not in ("PIME_MLP16", "PIME_GRAD_BF16X3", "PIME_PPO_SWEEP_REPORT")}
+    env["PIME_ROOT"] = ROOT
+    if variant:
+        env["PIME_GRAD_BF16X3"] = "1"
+    if forced16:
+        env["PIME_MLP16"] = "1"
+    r = subprocess.run([sys.executable, "-c", _B3_CHILD, name], env=env, capture_output=True, text=True, timeout=timeout)
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("PPO_SWEEP_B3 ")]
+    assert r.returncode == 0 and line, f"child {name} (variant: {variant}) exited with {r.returncode}\n" + r.stdout[-3000:] + r.stderr[-4000:]
+    return json.loads(line[0].split(" ", 1)[1])
+
+
+def _merge(rec):
+    for k, v in rec["used_share_of_bar"].items():
+        _note(k, v)
+        _B3["used_share_of_bar"][k] = max(_B3["used_share_of_bar"].get(k, 0.0), float(v))
+    for k, v in rec["routes_hit"].items():
+        _ROUTES[k] = _ROUTES.get(k, 0) + v
+        _B3["routes_hit"][k] = _B3["routes_hit"].get(k, 0) + v
+    _B3["grids"].update(rec["grids"])
+
+
+def _b3_list(name, routes, forced16=False):
+    """The list under the variant (every bar of run_case), then with the variable unset: the f32 path's pools, class by class."""
+    rec = _b3_run(name, True, forced16)
+    _merge(rec)
+    tag = (" (PIME_MLP16)" if forced16 else "") + " (PIME_GRAD_BF16X3)"
+    assert set(rec["routes_hit"]) == {r + tag for r in routes}
+    assert rec["pools"], "no B3 net in the list"
+    ref = _b3_run(name, False, forced16)
+    assert set(ref["pools"]) == set(rec["pools"])
+    failed = []
+    for key, b in sorted(rec["pools"].items()):
+        a = ref["pools"][key]
+        _B3["pools"][f"{name}: {key}"] = {"f32": a, "bf16x3": b}
+        row = (f"{name}: {key}: f32 p99 {a['p99']:.2e} rms {a['rms']:.2e} max {a['max']:.2e} beyond 2e-6 {a['far']:.5f} | bf16x3 p99 "
+               f"{b['p99']:.2e} rms {b['rms']:.2e} max {b['max']:.2e} beyond 2e-6 {b['far']:.5f} ({b['n']} elements)")
+        print("ppo sweep b3 pool " + row)
+        if not b["p99"] <= max(2.0 * a["p99"], 5e-7):
+            failed.append(row)
+    assert not failed, "the variant's 99th percentile exceeds max(2 x the f32 path's, 5e-7):\n" + "\n".join(failed)
+    return rec
+
+
+def test_b3_shapes_at_width_256():
+    """ppo16_kernel<16, actor | critic, true> on D 1..32 (one and two first-layer column blocks), ppo16m_kernel<16, true> on every
+    plant tower up to 28 floats and Di 1..3."""
+    _b3_list("shapes256", {"16tile/16tile/single 256+256"})
+
+
+def test_b3_shapes_at_width_128():
+    """ppo16_kernel<8, actor | critic, true> on D 14..32; the split-pipeline actor (f32, atomics) next to ppo16_kernel<8, critic, true>."""
+    _b3_list("shapes128", {"16tile/16tile/single 128+128", "split/16tile/single 128+128"})
+
+
+def test_b3_classes_in_every_batch_regime():
+    rec = _b3_list("regimes", {"16tile/16tile/single 256+256", "16tile/16tile/single 128+128", "split/16tile/single 128+128"})
+    assert len(rec["grids"]) == 3 and all(g["B"] > 64 * max(v for k, v in g.items() if k != "B") for g in rec["grids"].values())
+
+
+def test_b3_nets_of_different_widths():
+    """ppo16_kernel<16, actor, true> next to the LDS-resident f32 critic, next to ppo16_kernel<8, critic, true>; the LDS-resident
+    modular actor next to ppo16_kernel<16, critic, true>; ppo16_kernel<8, actor, true> next to the LDS-resident critic of width 64."""
+    _b3_list("mixed", {"16tile/lds/single 256+128", "16tile/16tile/single 256+128", "lds/16tile/single 128+256", "16tile/lds/single 128+64"})
+
+
+def test_b3_under_forced_16_tile_family():
+    """Both switches: ppo16_kernel<8, ., true> below 14 floats and ppo16m_kernel<8, true> (Di 1 and 3, one and two first-layer
+    tiles), B 2 .. 65 and the cap batch, and the three properties on both."""
+    rec = _b3_list("forced16", {"16tile/16tile/single 128+128", "16tile/16tile/single 128+64"}, forced16=True)
+    assert len(rec["grids"]) == 1
+
+
+def test_b3_properties():
+    """NaN in the workspaces and the unnamed rows, stale slabs of a larger launch, frozen parameters (the re-packed images compared
+    include the planes) over ppo_cases.b3_per_route_shapes()."""
+    rec = _b3_run("properties", True, timeout=300)
+    _merge(rec)
+    assert set(rec["routes_hit"]) == {r + " (PIME_GRAD_BF16X3)" for r in (
+        "16tile/16tile/single 256+256", "16tile/16tile/single 128+128", "split/16tile/single 128+128", "16tile/lds/single 256+128",
+        "16tile/16tile/single 256+128", "lds/16tile/single 128+256", "16tile/lds/single 128+64")}
+
+
+def _b3_boundary():
+    """(in the child, under the variable)"""
+    import ctypes
+    import warnings
+    import pime_amd.native as nt
+    from pime_amd import backend, ops
+    assert PC.b3_process() and not PC.forced16_process()
+    for D, Di in ((30, 1), (32, 3)):
+        s = PC.b3_spec("modular", D, Di, 256, 37, vet=False)
+        assert s.route == ("none", "16tile", "single") == PC.library_route(s.kind, s.D, s.Di, s.aw, s.cw)
+        r = (ctypes.c_int32 * 3)()
+        assert nt.lib().pime_ppo_route(nt.MLP_MODULAR_ACTOR, D, Di, 256, 256, r) != 0
+        assert "LDS map does not fit" in nt.last_error() and "actor" in nt.last_error()
+        case = PC.build(s)
+        act, cri = _modules(case)
+        assert ops.FusedPPOGrad.supported(act, cri) is False
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            assert backend.HipBackend().fused_ppo(act, cri, 37) is False
+        text = " ".join(str(w.message) for w in seen)
+        assert "no fused PPO gradient kernel" in text and "runs through torch autograd" in text and "LDS map does not fit" in text, text
+        # the object built all the same: the call refuses, and writes no gradient
+        act, cri, fused = _fused(case)
+        tables, idx = _tables(case)
+        fused.flat_grad_dp.fill_(-7.25)
+        fused._dump.fill_(-7.25)
+        with pytest.raises(nt.PimeError, match="LDS"):
+            _call(fused, tables, idx, torch.zeros(1, device=DEV), overwrite=True)
+        torch.cuda.synchronize()
+        assert bool((fused.flat_grad_dp == -7.25).all()) and bool((fused._dump == -7.25).all()), "a refused call wrote gradients"
+        with pytest.raises(nt.PimeError, match="LDS"):
+            _call(fused, tables, idx, torch.zeros(1, device=DEV))
+        torch.cuda.synchronize()
+        assert bool((fused.flat_grad_dp == -7.25).all())
+    s = PC.b3_spec("modular", 31, 3, 256, 37)
+    act, cri = _modules(PC.build(s))
+    assert ops.FusedPPOGrad.supported(act, cri) is True
+    run_case(PC.build(s))
+
+
+def test_b3_does_not_serve_a_wide_plant_tower_at_width_256():
+    """Modular actor, width 256, (D, Di) = (30, 1) and (32, 3) -- plant towers of 29 floats: pime_ppo_route refuses and names the
+    LDS map; FusedPPOGrad.supported and HipBackend.fused_ppo answer what the library answers (False, with the "no fused PPO gradient
+    kernel ... runs through torch autograd" warning up front); an object constructed all the same raises PimeError on the call and
+    writes no element of the gradient buffer.  (31, 3), a tower of 28 floats, is served in the same process and passes run_case."""
+    rec = _b3_run("boundary", True, timeout=240)
+    _merge(rec)
+    assert set(rec["routes_hit"]) == {"16tile/16tile/single 256+256 (PIME_GRAD_BF16X3)"}

@@ -15,8 +15,14 @@ import pytest
 import ppo_cases as PC
 import ppo_chain as CH
 
-SPECS = CH.chain_specs()
+B3_SPECS = [s for f16 in (False, True) for s in CH.b3_chain_specs(f16)]   # the bf16x3 variant's chains: the same checker
+SPECS = CH.chain_specs() + [s for s in B3_SPECS if s not in CH.chain_specs()]
 MAX_SHARE = 0.5
+
+
+def _id(s):
+    """(a spec of the variant under PIME_MLP16=1 differs from the default process's in its route alone)"""
+    return PC.spec_id(s) + ("-mlp16" if s not in CH.chain_specs() and s in CH.b3_chain_specs(True) else "")
 
 
 @functools.lru_cache(maxsize=None)
@@ -26,18 +32,24 @@ def _case(s):
 
 
 def test_the_spec_list():
-    ids = [PC.spec_id(s) for s in SPECS]
+    ids = [_id(s) for s in SPECS]
     assert len(set(ids)) == len(ids) and all(s.B == CH.B == 293 and s.vet for s in SPECS)
     assert {(s.route, s.aw, s.cw) for s in PC.per_route_shapes()} <= {(s.route, s.aw, s.cw) for s in SPECS}
     for want in (("modular", 3, 1, 128), ("modular", 4, 1, 64), ("modular", 4, 1, 256), ("plain", 30, 0, 256)):
         assert any((s.kind, s.D, s.Di, s.aw) == want and s.cw == s.aw for s in SPECS), want
     assert any(not CH.deterministic(s) for s in SPECS) and sum(CH.deterministic(s) for s in SPECS) >= 10
-    for s in SPECS:
+    for s in CH.chain_specs():
         assert s.route == PC.expected_route(s.kind, s.D, s.Di, s.aw, s.cw)
+    for f16 in (False, True):
+        for s in CH.b3_chain_specs(f16):
+            assert s.route == PC.expected_route(s.kind, s.D, s.Di, s.aw, s.cw, f16, b3=True) and any(PC.b3_nets(s, f16))
+            assert s.B == CH.B and s.vet
+    assert len(CH.b3_chain_specs()) == 8 and len(CH.b3_chain_specs(True)) == 3
+    assert [CH.deterministic(s) for s in CH.b3_chain_specs()].count(False) == 1   # the split-pipeline actor next to a B3 critic
     assert PC.spec("modular", 3, 1, 128, CH.B).route == ("lds", "lds", "pair")   # the bench's nets: the pair kernel
 
 
-@pytest.mark.parametrize("s", SPECS, ids=PC.spec_id)
+@pytest.mark.parametrize("s", SPECS, ids=_id)
 def test_index_tables(s):
     case, table = _case(s)
     assert table.shape == (CH.K, s.B) and table.dtype == np.int64 and CH.K == 4
@@ -50,7 +62,7 @@ def test_index_tables(s):
     assert not np.array_equal(table[1], table[2])
 
 
-@pytest.mark.parametrize("s", SPECS, ids=PC.spec_id)
+@pytest.mark.parametrize("s", SPECS, ids=_id)
 def test_a_clean_recording_passes_with_half_of_every_bound_to_spare(s):
     case, table = _case(s)
     used = CH.check_chain(CH.synthesise(case, table), case, table)
@@ -62,7 +74,7 @@ def test_a_clean_recording_passes_with_half_of_every_bound_to_spare(s):
         assert v <= MAX_SHARE, f"{PC.spec_id(s)}: float32 numpy uses {v:.3f} of the bound '{k}'"
 
 
-@pytest.mark.parametrize("s", SPECS, ids=PC.spec_id)
+@pytest.mark.parametrize("s", SPECS, ids=_id)
 def test_every_fault_trips_its_assertion(s):
     case, table = _case(s)
     for fault, name in CH.FAULTS.items():
